@@ -44,6 +44,11 @@ Prints ONE JSON line on rank 0.  Extra objects:
   scaling_detail  what bounds strong scaling of this path: a pixel's samples are ONE sequential RNG
                 chain, so no rank finishes before prepass + its longest chain x the latency of a lone ray's trip:
                 "floor_ms"; per-rank kernel_ms and the time of the exchange
+
+`--dump-outputs DIR` (rank 0): after the timed steps, the image the last timed step produced -- what a caller of the
+path receives: [H, W, 3] in the render precision -- as DIR/image.npy.  Above DUMP_LIMIT_BYTES a fixed, seeded sample
+of pixels is written instead (DIR/image_sample.npy [K, 3] and their flat pixel indices, DIR/image_sample_pixels.npy).
+The inputs (scene, camera, XORWOW seed 1227) depend on the arguments alone, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -74,6 +79,7 @@ DP_CYCLES, DP_TRANS_CYCLES = 4.0, 8.0
 # driver's clock too (N = 1 only): name -> (scene, W, H, spp, bounces, precision)
 EXTRA_CONFIGS = [("fp64_headline", (3, 1920, 1080, 100, 50, 64)), ("scene1_487_spheres_1080p", (1, 1920, 1080, 100, 50, 32)),
                  ("baseline_config2_scene1_320x192_10spp_25b", (1, 320, 192, 10, 25, 32))]
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: at most this many bytes in all
 PMC_RECORDS = os.environ.get("RTIOW_PMC_RECORDS") or os.path.join(ROOT, "profiles", "pmc_records.json")    # the committed counter records (the override is for tests)
 
 
@@ -101,7 +107,26 @@ def parse():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the extra_configs object (fp64 headline, 487-sphere scene, BASELINE config [1]; N = 1 only)")
     ap.add_argument("--no-scaling-probe", action="store_true",
                     help="skip the 1-pixel lone-ray probe (it launches the main kernel by the same name: keeps rocprofv3 --stats averages clean)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step to DIR/image.npy (a seeded pixel sample above 64 MB)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the [H, W, 3] image of the last timed step, float32 / float64 as rendered."""
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image)
+    assert image.dtype in (np.float32, np.float64) and image.ndim == 3 and image.shape[2] == 3, (image.dtype, image.shape)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), image)
+        return
+    pixels = image.reshape(-1, 3)
+    k = DUMP_LIMIT_BYTES // (pixels.itemsize * 3 + 8)          # sampled pixels + their float64 indices
+    pick = np.sort(np.random.default_rng(1227).choice(len(pixels), size=k, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), pixels[pick])
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), pick.astype(np.float64))
 
 
 def host_cpu():
@@ -532,6 +557,7 @@ def run_group(args, json_fd):
     for m in members:
         m.synchronize()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, g.read_framebuffer())       # untimed: device 0 holds the last step's gathered image
     gs = g.stats()
     sts = [m.stats() for m in members]
     floor = max(float(sts[k]["prepass_ms"]) + chains[k] * (trip_us or 0.0) * 1e-3 for k in range(N))
@@ -642,6 +668,8 @@ def run_ranks(args, json_fd, world, rank, local_rank, distributed, pmc, pmc_note
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if rank == 0:                                      # untimed: the image the last timed step left on rank 0
+        dump_outputs(args.dump_outputs, gather.full.cpu().numpy() if distributed else r.read_framebuffer())
     gather_ms = float(np.mean([a.elapsed_time(b) for a, b in gather_events])) if gather_events else None
 
     st_local = r.stats()
@@ -701,6 +729,8 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.strip_rows <= 0:
         args.strip_rows = 8 if max(world, args.gpus) <= 2 else 2
     if args.gpus > 1 and not distributed:

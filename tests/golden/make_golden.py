@@ -21,6 +21,10 @@ What each fixture is and where it comes from:
                            ppm_diff noise floor of each scene (two oracle renders that differ only
                            in the RNG seed; SURVEY.md A.5 lists the same floors for scenes 1 and 3).
                            Used by the sky-mode / policy pins of the CUDA-semantics oracle.
+  ref_serial_small.npz     the P3 text (bytes) the REFERENCE's serial tracer prints for SMALL_SERIAL_CONFIGS,
+                           compared byte for byte with the oracle's serial port.
+  ref_ppm_tools.json       what the REFERENCE's ppm_diff / scaled_ppm_diff (oracle/_ref/ref_*) write and print
+                           for the seeded images of tests/test_tools.py (+ md5 of those input files).
 No reference source text is stored here: only inputs (flags) and outputs (hashes, arrays).
 """
 import hashlib
@@ -39,11 +43,38 @@ from tests.oracle_lib import Oracle  # noqa: E402
 SERIAL_CONFIGS = [  # scene_id, W, H, S, depth
     (3, 64, 36, 4, 10), (1, 96, 54, 3, 12), (2, 80, 48, 5, 25), (3, 160, 96, 10, 50), (1, 120, 72, 2, 20),
 ]
+SMALL_SERIAL_CONFIGS = [  # scene_id, W, H, S, depth: stored whole (ref_serial_small.npz)
+    (3, 48, 27, 2, 7), (2, 40, 24, 3, 50), (1, 64, 36, 1, 5),
+]
 CUDA_SEM_CONFIGS = [  # name, precision, scene_id, W, H, S, B
     ("cuda_sem_s3_64x40_4spp_10b_f32", 32, 3, 64, 40, 4, 10),
     ("cuda_sem_s1_48x32_2spp_8b_f32", 32, 1, 48, 32, 2, 8),
     ("cuda_sem_s2_48x32_3spp_25b_f64", 64, 2, 48, 32, 3, 25),
 ]
+
+
+def write_ref_serial_small(drv):
+    out = {"configs": np.array(SMALL_SERIAL_CONFIGS, np.int32)}
+    for k, cfg in enumerate(SMALL_SERIAL_CONFIGS):
+        p3 = subprocess.run([drv] + [str(x) for x in cfg], capture_output=True, check=True).stdout
+        out["p3_%d" % k] = np.frombuffer(p3, np.uint8)
+    np.savez_compressed(os.path.join(HERE, "ref_serial_small.npz"), **out)
+
+
+def write_ref_ppm_tools(ref_dir):
+    import tempfile
+    import pathlib
+    import raytracingincuda_amd as rt
+    from tests.test_tools import PPM_TOOL_CASES, _write_images
+    with tempfile.TemporaryDirectory() as tmp:
+        pa, pb, p6, _, _ = _write_images(pathlib.Path(tmp), rt)
+        files = {"a": pa, "b": pb, "b6": p6}
+        data = {"inputs_md5": {k: hashlib.md5(open(f, "rb").read()).hexdigest() for k, f in files.items()}, "outputs": {}}
+        for tool, second in PPM_TOOL_CASES:
+            out = os.path.join(tmp, "ref.ppm")
+            r = subprocess.run([os.path.join(ref_dir, "ref_" + tool), pa, files[second], out], capture_output=True, text=True, check=True)
+            data["outputs"]["%s/%s" % (tool, second)] = {"ppm": open(out).read(), "stdout": r.stdout.replace(out, "{out}")}
+    json.dump(data, open(os.path.join(HERE, "ref_ppm_tools.json"), "w"), indent=1, sort_keys=True)
 
 
 def main():
@@ -63,6 +94,8 @@ def main():
         serial["unmodified_binary"] = {"scene_id": 1, "width": 1280, "height": 768, "samples": 10, "depth": 20,
                                        "md5": hashlib.md5(out).hexdigest(), "bytes": len(out)}
     json.dump(serial, open(path, "w"), indent=1)
+    write_ref_serial_small(drv)
+    write_ref_ppm_tools(os.path.dirname(drv))
 
     from tests.oracle_lib import p3_levels, to_levels, diff_stats, SKY_CURRENT
     orc = Oracle()

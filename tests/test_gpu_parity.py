@@ -972,6 +972,24 @@ def test_bench_prints_one_contract_line(rt):
     assert cb["kind"] in ("reference", "port") and cb["cores"] == 1 and cb["value"] > 0 and cb["unit"] == "Mrays/s" and cb["sample"]
 
 
+@pytest.mark.parametrize("prec", [32, 64])
+def test_bench_dump_outputs_is_the_rendered_image(rt, oracle, tmp_path, prec):
+    """bench.py --dump-outputs DIR writes the image its timed path left after the last step.  The RNG state is not written
+    back, so every step renders the same image: bit for bit the oracle's render of the same scene, camera and seed."""
+    import sys
+    from tests.conftest import ROOT
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "96", "--height", "64",
+                        "--samples", "4", "--bounces", "12", "--precision", str(prec), "--pmc", "off", "--no-cpu-baseline", "--no-extra-configs",
+                        "--no-scaling-probe", "--dump-outputs", str(out)], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(out)) == ["image.npy"]
+    got = np.load(out / "image.npy")
+    assert got.dtype == (np.float32 if prec == 32 else np.float64) and got.shape == (64, 96, 3)
+    want, _ = oracle.render(prec, compact(rt.build_scene(3, prec)), rt.camera(prec, 96, 64, 4, 12), 1227)
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
+
+
 def test_bench_live_counter_passes(rt):
     """The live leg of roofline.frac: rocprofv3 --pmc child passes over the loaded library (skips where the profiler cannot collect counters)."""
     import json, sys

@@ -208,3 +208,21 @@ def test_scaling_table_reads_driver_records(tmp_path):
         assert [r["n_gpus"] for r in rows] == [1, 2, 4, 8]
         assert [r["speedup"] for r in rows] == [1.0, 1.5, 2.0, 2.4] and [r["efficiency"] for r in rows] == [1.0, 0.75, 0.5, 0.3]
         assert rows[3]["ms_over_floor"] == 1.25 and rows[0]["speedup_limit_by_floor"] == 3.0
+
+
+def test_dump_outputs_whole_image_or_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole image up to the size limit, above it the same seeded pixel sample on every run."""
+    import numpy as np
+    import bench
+    img = np.random.default_rng(5).random((40, 30, 3))
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    assert os.listdir(tmp_path / "whole") == ["image.npy"] and np.array_equal(np.load(tmp_path / "whole" / "image.npy"), img)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", img.nbytes // 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), img.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "s1")) == ["image_sample.npy", "image_sample_pixels.npy"]
+    px, pick = np.load(tmp_path / "s1" / "image_sample.npy"), np.load(tmp_path / "s1" / "image_sample_pixels.npy")
+    assert px.dtype == np.float32 and pick.dtype == np.float64 and px.nbytes + pick.nbytes <= img.nbytes // 4
+    assert len(np.unique(pick)) == len(pick) == len(px) > 0
+    assert np.array_equal(px, img.astype(np.float32).reshape(-1, 3)[pick.astype(np.int64)])
+    assert np.array_equal(pick, np.load(tmp_path / "s2" / "image_sample_pixels.npy"))

@@ -3,8 +3,8 @@ checked against the reference's own outputs and against third-party known answer
 
  * serial semantics  == the reference's serial tracer (src/InOneWeekend) byte for byte:
    hashes in tests/golden/serial_ref.json were produced by the reference's sources built
-   by oracle/Makefile (tests/golden/make_golden.py); when oracle/_ref/ is present the
-   binary is also run live.
+   by oracle/Makefile (tests/golden/make_golden.py), and whole P3 texts of small configs in
+   tests/golden/ref_serial_small.npz; when oracle/_ref/ is present the binary is also run live.
  * XORWOW engine + 2^67 jump matrices == rocRAND's host engine (salt=1 known answers).
  * scene tables == the entries SURVEY.md A.3 dumped from the reference's structs.
  * analytic known answers for hit_sphere / reflect / refract / Schlick.
@@ -41,14 +41,19 @@ def test_serial_semantics_matches_reference_hashes(oracle, golden_dir):
         assert stats[0] == g["width"] * g["height"] * g["samples"]
 
 
-def test_serial_semantics_matches_reference_binary_live(oracle):
+def test_serial_semantics_matches_reference_binary_live(oracle, golden_dir):
+    """Byte for byte against the P3 text the reference's serial tracer printed (tests/golden/ref_serial_small.npz);
+    with oracle/_ref built, the binary is also run and must print the same text."""
+    gold = np.load(os.path.join(golden_dir, "ref_serial_small.npz"))
+    configs = [(3, 48, 27, 2, 7), (2, 40, 24, 3, 50), (1, 64, 36, 1, 5)]
+    assert gold["configs"].tolist() == [list(c) for c in configs]
     drv = os.path.join(ROOT, "oracle", "_ref", "ref_serial_driver")
-    if not os.path.exists(drv):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    for cfg in [(3, 48, 27, 2, 7), (2, 40, 24, 3, 50), (1, 64, 36, 1, 5)]:
-        want = subprocess.run([drv] + [str(x) for x in cfg], capture_output=True, check=True).stdout
+    for k, cfg in enumerate(configs):
+        want = gold["p3_%d" % k].tobytes()
         got, _ = oracle.render_serial(*cfg)
         assert got == want, cfg
+        if os.path.exists(drv):
+            assert subprocess.run([drv] + [str(x) for x in cfg], capture_output=True, check=True).stdout == want, cfg
 
 
 def test_unmodified_reference_binary_hash_is_recorded(golden_dir):
@@ -278,19 +283,28 @@ def _ref_images(golden_dir):
     return meta, imgs
 
 
+def _p3_text(levels):
+    """uint8 [H, W, 3] -> the P3 text the reference's serial tracer prints for it (header, one pixel per line)."""
+    H, W, _ = levels.shape
+    return ("P3\n%d %d\n255\n" % (W, H) + "".join("%d %d %d\n" % tuple(p) for p in levels.reshape(-1, 3).tolist())).encode()
+
+
 def test_reference_image_fixtures_are_what_the_reference_prints(golden_dir):
-    """The fixture images are outputs of the reference's serial tracer (make_golden.py); when the
-    binary built from the reference's sources is here, one of them is regenerated and compared."""
+    """The fixture images are outputs of the reference's serial tracer (make_golden.py): each one, printed
+    back as P3 text, has the md5 and length recorded from that tracer's output.  When the binary built
+    from the reference's sources is here, one of them is also regenerated and compared."""
     meta, imgs = _ref_images(golden_dir)
     assert sorted(meta["scenes"]) == ["1", "2", "3"] and imgs["s1"].shape == (192, 320, 3)
     # SURVEY.md A.5 measured the same floors with the reference's ppm_diff (1.408 / 2.490)
     assert abs(meta["scenes"]["3"]["floor_mean"] - 1.408) < 0.05 and abs(meta["scenes"]["1"]["floor_mean"] - 2.490) < 0.08
+    for sid in ("1", "2", "3"):
+        text = _p3_text(imgs["s" + sid])
+        assert len(text) == meta["scenes"][sid]["bytes"] and hashlib.md5(text).hexdigest() == meta["scenes"][sid]["md5"], sid
     drv = os.path.join(ROOT, "oracle", "_ref", "ref_serial_driver")
-    if not os.path.exists(drv):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    out = subprocess.run([drv, "2", "320", "192", "100", "50"], capture_output=True, check=True).stdout
-    assert hashlib.md5(out).hexdigest() == meta["scenes"]["2"]["md5"]
-    assert np.array_equal(p3_levels(out), imgs["s2"])
+    if os.path.exists(drv):
+        out = subprocess.run([drv, "2", "320", "192", "100", "50"], capture_output=True, check=True).stdout
+        assert hashlib.md5(out).hexdigest() == meta["scenes"]["2"]["md5"]
+        assert np.array_equal(p3_levels(out), imgs["s2"])
 
 
 def test_loop_form_is_neutral_with_identical_random_numbers(oracle):

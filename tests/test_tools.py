@@ -1,6 +1,9 @@
 """Harness tools of SURVEY §8(f): ppm_diff / scaled_ppm_diff (same CLI and P3 output as the
-reference's src/ppm_diff tools, pinned against those tools built into oracle/_ref when present)
+reference's src/ppm_diff tools, pinned against what those tools wrote for the same inputs --
+tests/golden/ref_ppm_tools.json -- and against the tools themselves when built into oracle/_ref)
 and csv_avg (process.py's pandas groupby-mean, pinned by the reference's own in->out CSV pairs)."""
+import hashlib
+import json
 import os
 import subprocess
 
@@ -11,6 +14,8 @@ from tests.conftest import ROOT
 
 GOLD = os.path.join(ROOT, "tests", "golden", "csv")
 REF = os.path.join(ROOT, "oracle", "_ref")
+# (tool, second image) of the reference-tool pin; the first image is always "a" (see _write_images)
+PPM_TOOL_CASES = [(tool, second) for tool in ("ppm_diff", "scaled_ppm_diff") for second in ("b", "b6", "a")]
 
 
 def _bin(native, name):
@@ -97,18 +102,25 @@ def test_ppm_diff_output_statistics_and_gate(native, tmp_path):
 
 
 def test_ppm_tools_match_reference_tools_byte_for_byte(native, tmp_path):
-    if not os.path.exists(os.path.join(REF, "ref_ppm_diff")):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    """Our tools against the reference's on the same inputs: what the reference's tools wrote and printed is stored
+    (tests/golden/ref_ppm_tools.json, make_golden.py); with oracle/_ref built they are also run live."""
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_ppm_tools.json")))
     pa, pb, p6, _, _ = _write_images(tmp_path, native)
-    for tool in ("ppm_diff", "scaled_ppm_diff"):
-        for second in (pb, p6, pa):
-            mine, ref = str(tmp_path / "mine.ppm"), str(tmp_path / "ref.ppm")
-            r1 = subprocess.run([_bin(native, tool), pa, second, mine], capture_output=True, text=True)
-            r2 = subprocess.run([os.path.join(REF, "ref_" + tool), pa, second, ref], capture_output=True, text=True)
-            assert r1.returncode == r2.returncode == 0
-            assert open(mine, "rb").read() == open(ref, "rb").read(), (tool, second)
-            # the reference's stdout lines are a prefix set of ours (ppm_diff adds a statistics line)
-            assert r2.stdout.replace(ref, mine).strip().splitlines()[-1] in r1.stdout
+    files = {"a": pa, "b": pb, "b6": p6}
+    assert {k: hashlib.md5(open(f, "rb").read()).hexdigest() for k, f in files.items()} == gold["inputs_md5"]
+    live = os.path.exists(os.path.join(REF, "ref_ppm_diff"))
+    for tool, second in PPM_TOOL_CASES:
+        want = gold["outputs"]["%s/%s" % (tool, second)]
+        mine, ref = str(tmp_path / "mine.ppm"), str(tmp_path / "ref.ppm")
+        r1 = subprocess.run([_bin(native, tool), pa, files[second], mine], capture_output=True, text=True)
+        assert r1.returncode == 0
+        assert open(mine, "rb").read() == want["ppm"].encode(), (tool, second)
+        # the reference's stdout lines are a prefix set of ours (ppm_diff adds a statistics line)
+        assert want["stdout"].replace("{out}", mine).strip().splitlines()[-1] in r1.stdout
+        if live:
+            r2 = subprocess.run([os.path.join(REF, "ref_" + tool), pa, files[second], ref], capture_output=True, text=True)
+            assert r2.returncode == 0 and open(ref, "rb").read() == want["ppm"].encode(), (tool, second)
+            assert r2.stdout.replace(ref, "{out}") == want["stdout"], (tool, second)
 
 
 def test_benchmark_script_writes_reference_csv_schema(native):
