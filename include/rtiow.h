@@ -198,6 +198,24 @@ int rtiow_render_wait(rtiow_handle h, float* kernel_ms);
  * The image it leaves in the framebuffer is identical to rtiow_render's. */
 int rtiow_count_segments(rtiow_handle h, int threads_per_block_row, uint64_t* segments);
 
+/* ---- Progressive rendering: the frame in chunks of samples.  After a reset, rtiow_accumulate(h, k1, ...), rtiow_accumulate(h, k2, ...),
+ * ... each leave in the framebuffer the exact bits rtiow_render leaves with the same camera and samples_per_pixel = k1 + ... + ki (same
+ * seed), whatever the chunk sizes, schedule, scene source or shard layout: a pixel's samples are one sequential RNG chain summed in
+ * sample order, and each chunk resumes every pixel from its exact RNG state and colour sum.  The preview is scaled by (T)1 / (T)n, n = the
+ * samples accumulated so far; the camera's samples_per_pixel and pixel_samples_scale are not used, max_depth and the rest are.
+ *
+ * rtiow_accumulate renders samples [n, n + samples) of every local pixel and writes the preview to the framebuffer (the library's or the
+ * bound one).  Chunks always use the persistent hand-out: threads_per_block_row is accepted and ignored.  kernel_ms as in rtiow_render
+ * (NULL: asynchronous on the handle's stream).  RTIOW_E_BADARG for samples <= 0 or n + samples > INT32_MAX; RTIOW_E_STATE before scene,
+ * camera and RNG are set up.  A handle without local rows launches nothing (n still advances).
+ * n goes back to 0 -- the next chunk starts from the RNG states of rtiow_init_rng -- on rtiow_accumulate_reset, rtiow_set_camera,
+ * rtiow_set_scene, rtiow_set_shard and rtiow_init_rng; rtiow_set_scene_source, rtiow_set_schedule and rtiow_bind_framebuffer keep it.
+ * The accumulation has buffers of its own (48 B fp32 / 64 B fp64 per pixel, twice): rtiow_render and rtiow_count_segments between two
+ * chunks do not disturb it.  Not available on groups (rtiow_group_*). */
+int rtiow_accumulate_reset(rtiow_handle h);
+int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms);
+int rtiow_accumulated_samples(rtiow_handle h, int* samples);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -90,6 +90,7 @@ HIP_SYMBOLS = [
     "rtiow_init_rng", "rtiow_render", "rtiow_count_segments", "rtiow_bind_framebuffer", "rtiow_framebuffer_device_ptr",
     "rtiow_read_framebuffer", "rtiow_read_levels", "rtiow_set_scene_source", "rtiow_set_schedule", "rtiow_get_stats", "rtiow_synchronize",
     "rtiow_render_async", "rtiow_render_wait", "rtiow_stream", "rtiow_device",
+    "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -185,6 +186,9 @@ def load_hip_library(debug=False):
         lib.rtiow_render_wait.argtypes = [H, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_stream.argtypes = [H, ctypes.POINTER(vp)]
         lib.rtiow_device.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
+        lib.rtiow_accumulate_reset.argtypes = [H]
+        lib.rtiow_accumulate.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_accumulated_samples.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -466,6 +470,26 @@ class Renderer:
             return ms.value
         self._check(self._lib.rtiow_render(self._h, int(threads), None))
         return None
+
+    def accumulate(self, samples, threads=0, sync=True):
+        """Progressive rendering: add `samples` samples per pixel to the accumulation and write the preview to the framebuffer (bit for bit
+        what render() gives with samples_per_pixel = accumulated_samples).  Returns the HIP-event kernel time in ms (None when sync=False)."""
+        if sync:
+            ms = ctypes.c_float(0)
+            self._check(self._lib.rtiow_accumulate(self._h, int(samples), int(threads), ctypes.byref(ms)))
+            return ms.value
+        self._check(self._lib.rtiow_accumulate(self._h, int(samples), int(threads), None))
+        return None
+
+    def reset_accumulation(self):
+        """The next accumulate() starts a new image from the RNG states of init_rng."""
+        self._check(self._lib.rtiow_accumulate_reset(self._h))
+
+    @property
+    def accumulated_samples(self):
+        n = ctypes.c_int(0)
+        self._check(self._lib.rtiow_accumulated_samples(self._h, ctypes.byref(n)))
+        return n.value
 
     def count_segments(self, threads=8):
         """Untimed render that also counts path segments (hit_world calls)."""

@@ -1,4 +1,4 @@
-// pixel_io.h -- scene staging into LDS, pixel store, hand-over records of the sorted schedule
+// pixel_io.h -- scene staging into LDS, pixel store, hand-over records of the sorted schedule and of progressive rendering
 // Part of the single gfx950 translation unit rtiow_hip.hip (included there, in this order; internal linkage).
 #pragma once
 #include "vecmath.h"
@@ -104,6 +104,15 @@ __device__ __forceinline__ void unpark_state(const unsigned char* base, size_t l
     for (int k = 0; k < (int)(sizeof(MidState<T>) / 16); ++k) dst[k] = src[k];
     st.rs.v0 = m.v[0]; st.rs.v1 = m.v[1]; st.rs.v2 = m.v[2]; st.rs.v3 = m.v[3]; st.rs.v4 = m.v[4]; st.rs.d = m.d;
     st.acc = {m.acc[0], m.acc[1], m.acc[2]};
+}
+
+// End of a pixel in a progressive chunk (render_accumulate_kernel): park the exact state for the next chunk, record the
+// pixel's segments for that chunk's ranking, and store the preview (pixel_samples_scale = 1 / samples so far).
+template <class T, class COLD>
+__device__ __forceinline__ void accumulate_pixel(const COLD& c, size_t lp, const PathState<T>& st, unsigned int cost) {
+    park_state<T>(c.mid_out, lp, st);
+    c.cost_out[lp] = cost;
+    store_pixel<T>(c, lp, st.acc);
 }
 
 template <class T, class COLD>

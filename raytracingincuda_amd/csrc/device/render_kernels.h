@@ -1,4 +1,4 @@
-// render_kernels.h -- the render kernels: static (reference geometry), persistent / prepass / solo, debug kernels
+// render_kernels.h -- the render kernels: static (reference geometry), persistent / prepass / solo / accumulate (progressive chunks), debug kernels
 // Part of the single gfx950 translation unit rtiow_hip.hip (included there, in this order; internal linkage).
 #pragma once
 #include "shade.h"
@@ -104,7 +104,7 @@ __device__ __forceinline__ void clock_stamp(const RenderParams<T>& p, int slot) 
     }
 }
 
-template <class T, int SRC, bool COUNT, bool SOLO = false, bool BOUND_F32 = false>
+template <class T, int SRC, bool COUNT, bool SOLO = false, bool BOUND_F32 = false, bool ACCUM = false>
 __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
     const T* lds_geom = stage_scene<T, SRC>(p);
     // per-wave scratch for hit_world_coop, behind the staged tables
@@ -214,7 +214,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                         if (c.stage_by_slot) lp = (size_t)slot;      // where this pixel will be stored (ColdParams::stage_by_slot); the state is loaded
                         if (COUNT) ++n_pixels;
                         if (c.s_begin < S) { alive = true; fresh = true; }
-                        else { finish_pixel<T>(c, lp, st, cost); want = true; }   // nothing to render in this launch
+                        else { if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost); want = true; }   // nothing to render in this launch
                     }
                 }
             }
@@ -246,7 +246,8 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                 PATH_STAT(PS_FINISH_PIXEL); \
                 const auto& c_ = cold_of(p); \
                 if (COUNT) atomicMax(c_.seg_counter + 2, (unsigned long long)cost); \
-                finish_pixel<T>(c_, lp, st, cost); alive = false; \
+                if constexpr (ACCUM) accumulate_pixel<T>(c_, lp, st, cost); else finish_pixel<T>(c_, lp, st, cost); \
+                alive = false; \
             } } while (0)
         for (;;) {
             REGION_BEGIN(total);
@@ -397,7 +398,8 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                     o[3] = blockIdx.x * ((blockDim.x + 63) >> 6) + (threadIdx.x >> 6);
                 }
 #endif
-                finish_pixel<T>(c, lp, st, cost); alive = false;
+                if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost);
+                alive = false;
             }
         }
         REGION_END(acc, RG_ACCUMULATE);
@@ -435,6 +437,12 @@ __global__ void __launch_bounds__(1024) render_prepass_kernel(const RenderParams
 // wave-uniform bookkeeping: +1 % measured).
 template <class T, int SRC>
 __global__ void __launch_bounds__(1024) render_solo_kernel(const RenderParams<T> p) { persistent_body<T, SRC, false, true>(p); }
+// Progressive rendering (rtiow_accumulate): one chunk, samples [cold.s_begin, s_end) of every pixel, through the same body.  A pixel starts
+// from cold.rng_in with a zero sum (first chunk after a reset) or from its record in cold.mid_in, and when it finishes parks its state and
+// segment count in cold.mid_out / cold.cost_out and stores its preview in cold.fb (accumulate_pixel).  The records ping-pong between two
+// buffers, so mid_in and mid_out never alias (both are __restrict__).  The plain kernels above compile exactly as before (ACCUM = false).
+template <class T, int SRC, bool BOUND_F32 = false>
+__global__ void __launch_bounds__(1024) RT_MAIN_OCCUPANCY render_accumulate_kernel(const RenderParams<T> p) { persistent_body<T, SRC, false, false, BOUND_F32, true>(p); }
 
 #ifdef RTIOW_DEBUG_API       // kernels behind the test hooks of include/rtiow_debug.h
 // Elementwise arithmetic probes (tests compare these with the host bit for bit).

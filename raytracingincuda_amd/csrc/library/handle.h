@@ -54,6 +54,12 @@ struct rtiow_handle_s {
     int* slot_of = nullptr; size_t slot_of_bytes = 0;            // SCHED_SORTED: pixel -> slot (the inverse of `order`)
     unsigned char* staged = nullptr; size_t staged_bytes = 0;             // SCHED_SORTED: finished pixels in slot order (place_pixels_kernel writes the image)
     unsigned* sort_scratch = nullptr; size_t sort_scratch_bytes = 0;
+    // progressive rendering (rtiow_accumulate): samples accumulated since the last reset, the per-pixel MidState records of the last chunk
+    // (two buffers, ping-pong: acc_mid[acc_cur] holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)
+    int acc_samples = 0;
+    int acc_cur = 0;
+    unsigned char* acc_mid[2] = {nullptr, nullptr}; size_t acc_mid_bytes[2] = {0, 0};
+    uint32_t* acc_cost = nullptr; size_t acc_cost_bytes = 0;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

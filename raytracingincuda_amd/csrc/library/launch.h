@@ -1,4 +1,4 @@
-// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches
+// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -53,20 +53,15 @@ int ensure_buffer(rtiow_handle_s* h, P** ptr, size_t* have, size_t need) {
     return 0;
 }
 
-template <class T, class CAM>
-int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_tiles, unsigned long long* seg_counter = nullptr,
-                  bool prepare_only = false) {
-    RenderParams<T> p = make_params<T>(h, cam);
-    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = wave_tiles;
-    p.cold.seg_counter = seg_counter ? seg_counter + 1 : nullptr;     // [0] prepass launch, [1] main (or only) launch
-    p.lane_cap = 64;
-    const bool persistent = h->schedule != RTIOW_SCHED_STATIC;
-    const int threads = bx * by;
+// LDS layout of a render launch (scene source, screening table and grid -- built at the first launch after rtiow_set_scene --, shade
+// records, drain scratch) into p; lds = dynamic LDS bytes per workgroup.  record_stats: the grid_* fields of rtiow_stats describe it.
+template <class T>
+int layout_lds(rtiow_handle_s* h, RenderParams<T>& p, int threads, bool persistent, bool record_stats, size_t& lds, bool& lds_source, int& effective_source) {
     // A scene whose tables do not fit the CU's LDS next to the drain scratch (several thousand
     // spheres) is read through the scalar cache instead of failing: same image, exact loop.
     size_t coop_scratch = persistent ? (size_t)((threads + 63) / 64) * COOP_SLOTS * sizeof(CoopSlot<T>) : 0;
-    bool lds_source = h->scene_source != RTIOW_SCENE_SCALAR;
-    int effective_source = h->scene_source;
+    lds_source = h->scene_source != RTIOW_SCENE_SCALAR;
+    effective_source = h->scene_source;
     const bool screened = h->scene_source == RTIOW_SCENE_LDS || h->scene_source == RTIOW_SCENE_GRID;
     if (lds_source && (sizeof(T) + (screened ? sizeof(float) : 0)) * 4 * (size_t)h->n_padded + coop_scratch > 160 * 1024) {
         lds_source = false;
@@ -81,12 +76,9 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
     }
     fill_screen_params<T>(p, h);
     if (!lds_source) p.use_screen = 0;
-    size_t lds = lds_source ? sizeof(T) * 4 * (size_t)h->n_padded : 0;
+    lds = lds_source ? sizeof(T) * 4 * (size_t)h->n_padded : 0;
     p.screen_offset = (int)lds;
     if (p.use_screen) lds += sizeof(float) * 4 * (size_t)h->n_padded;
-    p.cold.timeline = nullptr;                                    // set below, once the grid is known
-    p.cold.clock_stamps = (!seg_counter && h->schedule != RTIOW_SCHED_STATIC && h->clock_stamps_dev) ? h->clock_stamps_dev + 4 : nullptr;   // the main (or only) launch; timed renders only
-    p.cold.pixel_times = seg_counter ? h->pixel_times : nullptr;
     // shade records ride along in LDS while a workgroup's share stays within 1/5 of the CU's LDS
     const size_t coop_bytes = coop_scratch;
     const size_t shade_bytes = (sizeof(T) * 12 * (size_t)h->n + 15) / 16 * 16;
@@ -100,7 +92,7 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
     // the grid blob (cells | fp32 AoS table | direct table | direct ids) goes last
     p.grid = GridParams{};
     p.use_grid = 0;
-    if (!seg_counter) { h->stats.grid_nx = h->stats.grid_nz = h->stats.grid_registered = h->stats.grid_direct = 0; h->stats.grid_cell = 0; }
+    if (record_stats) { h->stats.grid_nx = h->stats.grid_nz = h->stats.grid_registered = h->stats.grid_direct = 0; h->stats.grid_cell = 0; }
     if (lds_source && h->scene_source == RTIOW_SCENE_GRID && p.use_screen && h->grid.use_grid && lds + (size_t)h->grid.blob_bytes <= 160 * 1024) {
         p.grid = h->grid;
         p.grid.cells_offset = (int)lds;
@@ -109,9 +101,129 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
         p.grid.direct_ids_offset = p.grid.direct_offset + h->grid_direct_bytes;
         lds += (size_t)h->grid.blob_bytes;
         p.use_grid = 1;
-        if (!seg_counter) { h->stats.grid_nx = h->grid.nx; h->stats.grid_nz = h->grid.nz; h->stats.grid_registered = h->grid_registered; h->stats.grid_direct = h->grid_direct; h->stats.grid_cell = h->grid.cell; }
+        if (record_stats) { h->stats.grid_nx = h->grid.nx; h->stats.grid_nz = h->grid.nz; h->stats.grid_registered = h->grid_registered; h->stats.grid_direct = h->grid_direct; h->stats.grid_cell = h->grid.cell; }
     } else if (effective_source == RTIOW_SCENE_GRID) effective_source = RTIOW_SCENE_LDS;   // no grid for this scene: the screened loop
     if (lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
+    return 0;
+}
+
+// Size a persistent launch of k: the lanes of a wave that take pixels (lane_cap), the workgroups to
+// launch (blocks) and -- fp32, kb = the same kernel with the bounded rejection loop, nullptr otherwise -- whether kb replaces k (bounded_f32).
+template <class T>
+int size_persistent(rtiow_handle_s* h, RenderFn<T>& k, RenderFn<T> kb, int threads, size_t lds, long long tile_slots,
+                    int& lane_cap, bool& bounded_f32, long long& blocks) {
+    const int waves_per_block = (threads + 63) / 64;
+    int per_cu = 0;
+    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, threads, lds));
+    if (per_cu < 1) per_cu = 1;
+    if (h->waves_per_simd > 0) {                       // knob: fewer resident waves, more pixels per lane
+        const int cap = (h->waves_per_simd * 4 + waves_per_block - 1) / waves_per_block;
+        if (cap < per_cu) per_cu = cap;
+    }
+    // Underfilled launch (fewer 64-pixel pools than resident waves: small frames): let only the first
+    // `lane_cap` lanes of every wave take pixels.  More waves are busy, each permanently in the
+    // cooperative mode, where its idle lanes split the sphere loops of the live ones: a trip gets
+    // shorter, and with so little work the frame is as long as its longest chain of trips.
+    // Measured (profiles/archive/r01_lane_cap_sweep.txt): scene 1 320x192x10 2.27 -> 1.06 ms, 640x384x100
+    // 19.4 -> 17.0 ms; frames with at least one pool per wave are unchanged (cap 64).
+    lane_cap = 64;
+    {
+        const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
+        while (lane_cap > 16 && pools * (64 / lane_cap) < waves) lane_cap >>= 1;  // the largest share that keeps every wave busy; not below 16 (with the grid walk 8-lane waves lose: scene 1 320x192x100 6.85 vs 5.96 ms, profiles/archive/r02_lane_cap_sweep.jsonl)
+        lane_cap = tuned("RTIOW_TUNE_LANE_CAP", lane_cap);
+    }
+    // fp32: the bounded rejection loop where throughput binds -- at least four pools per resident wave (1080p: 6.3; 1280 x 720, shards and small
+    // frames end with one chain's latency and keep the blocking loop) -- if that kernel keeps the occupancy this launch was sized for
+    bounded_f32 = false;
+    if (kb) {
+        const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
+#ifdef RTIOW_TUNING
+        const bool want = tuned("RTIOW_TUNE_RUV_BOUNDED", pools >= 4 * waves ? 1 : 0) != 0;
+#else
+        const bool want = pools >= 4 * waves;
+#endif
+        if (want) {
+            if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            int per_cu_b = 0;
+            HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, (const void*)kb, threads, lds));
+            if (per_cu_b >= per_cu) { k = kb; bounded_f32 = true; }
+        }
+    }
+    blocks = (long long)h->num_cus * per_cu;
+    const long long per_block = (long long)waves_per_block * lane_cap;
+    const long long useful = (tile_slots + per_block - 1) / per_block;
+    if (blocks > useful) blocks = useful;               // never more waves than lane_cap-pixel shares of the pools
+    return 0;
+}
+
+// The hand-out order of a cost-sorted launch: the pixels ranked heavy-first by `cost` (segments per local pixel, smoothed over a window)
+// and dealt into balanced pools, written to h->order (slot -> row << 16 | column, -1 for padding; the first solo_slots slots are the top
+// ranks) and, when slot_of is given, its inverse.  Blocks of the order are one "age class" of resident waves wide (see first_pools).
+// Needs h->order, h->cost_rank and h->sort_scratch sized for the frame.
+inline int rank_pixels(rtiow_handle_s* h, const uint32_t* cost, long long blocks, int waves_per_block, int total_pools, int solo_slots, int* slot_of) {
+    const int W = img_w(h), npix = W * h->local_rows;
+    unsigned* hist = h->sort_scratch; unsigned* start = hist + COST_BINS; unsigned* fill = start + COST_BINS;
+    HIP_TRY(h, hipMemsetAsync(hist, 0, COST_BINS * sizeof(unsigned), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->order, 0xff, ((size_t)total_pools * POOL + (size_t)solo_slots) * sizeof(int), h->stream));
+    const int sort_blocks = (npix + 255) / 256;
+    const uint32_t* rank_by = cost;
+    int smooth_hw = 6;                          // 13 x 13 window: profiles/archive/r02_cost_smoothing_sweep.jsonl
+    smooth_hw = tuned("RTIOW_TUNE_SMOOTH", smooth_hw);
+    if (smooth_hw > 0) {
+        if (smooth_hw > 24) smooth_hw = 24;      // 2 x (tile + halo) words of LDS: 37 KB at 24
+        const int smooth_blocks = ((W + SMOOTH_TW - 1) / SMOOTH_TW) * ((h->local_rows + SMOOTH_TH - 1) / SMOOTH_TH);
+        const size_t smooth_lds_bytes = ((size_t)(SMOOTH_TW + 2 * smooth_hw) + SMOOTH_TW) * (size_t)(SMOOTH_TH + 2 * smooth_hw) * sizeof(uint32_t);
+        // one rank: its strips are adjacent in the image, the window may cross them (it did not before: 13 x <= 8 rows)
+        int window_strip = h->nranks == 1 ? (h->local_rows > 0 ? h->local_rows : 1) : h->strip_rows;
+        if (const int ws = tuned("RTIOW_TUNE_SMOOTH_STRIP", -1); ws >= 0) window_strip = ws > 0 ? ws : (h->local_rows > 0 ? h->local_rows : 1);
+        hipLaunchKernelGGL(cost_smooth_kernel, dim3(smooth_blocks), dim3(256), smooth_lds_bytes, h->stream, cost, h->cost_rank, W, h->local_rows, window_strip, smooth_hw, hist);
+        rank_by = h->cost_rank;
+    } else {
+        hipLaunchKernelGGL(cost_hist_kernel, dim3(sort_blocks < 1024 ? sort_blocks : 1024), dim3(256), 0, h->stream, rank_by, npix, hist);
+    }
+    hipLaunchKernelGGL(cost_scan_kernel, dim3(1), dim3(COST_BINS), 0, h->stream, hist, start, fill);
+    const int resident_waves = (int)blocks * waves_per_block;
+    const int age_classes = (int)((blocks + h->num_cus - 1) / h->num_cus);
+    int pools_per_block = (resident_waves + age_classes - 1) / age_classes;
+    if (pools_per_block > total_pools) pools_per_block = total_pools;
+    // Deal granularity: `deal_group` consecutive ranks (= neighbouring pixels of equal cost) stay
+    // in one pool, the groups go round-robin over the block's pools.  Coherent groups mean fewer
+    // distinct spheres pass the screen per wave (8.9 exact blocks per wave-iteration with single
+    // ranks vs 3.6 in tile order); mixed costs in a pool let a heavy pixel finish in the fast
+    // cooperative mode, which is what small shards need.  Measured (profiles/archive/r01_deal_group_sweep.txt):
+    // full frame 24.1 -> 22.5 ms with 16-32, half frame 14.7 -> 14.0 with 8, quarter and eighth
+    // frames are fastest with 1.
+    const double pools_per_wave = (double)total_pools / (double)resident_waves;
+    // With the grid walk (a lane's cost follows ITS ray) coherence pays more: whole pools of 64 neighbouring
+    // ranks, 15.3 -> 14.7 ms on the full frame (profiles/archive/r02_tune_sweep.jsonl) and, once the ranks come from
+    // the smoothed cost, on every frame with at least 2.5 pools per wave (1280x720: 9.3 ms with groups of 1,
+    // 11.4 with 8, 8.7 with 64; profiles/archive/r02_cost_smoothing_sweep.jsonl); smaller shards keep single ranks.
+    int deal_group = pools_per_wave >= 2.5 ? 64 : 1;
+    deal_group = tuned("RTIOW_TUNE_DEAL", deal_group);
+    const int scatter_blocks = ((W + 63) / 64) * ((h->local_rows + 63) / 64);   // one per 64 x 64 super-tile
+    hipLaunchKernelGGL(cost_scatter_kernel, dim3(scatter_blocks), dim3(1024), 0, h->stream, rank_by, W, h->local_rows, start, fill, h->order,
+                       pools_per_block, total_pools, deal_group, solo_slots, slot_of);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+template <class T, class CAM>
+int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_tiles, unsigned long long* seg_counter = nullptr,
+                  bool prepare_only = false) {
+    RenderParams<T> p = make_params<T>(h, cam);
+    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = wave_tiles;
+    p.cold.seg_counter = seg_counter ? seg_counter + 1 : nullptr;     // [0] prepass launch, [1] main (or only) launch
+    p.lane_cap = 64;
+    const bool persistent = h->schedule != RTIOW_SCHED_STATIC;
+    const int threads = bx * by;
+    size_t lds = 0;
+    bool lds_source = false;
+    int effective_source = h->scene_source;
+    int rc0 = layout_lds<T>(h, p, threads, persistent, !seg_counter, lds, lds_source, effective_source);
+    if (rc0) return rc0;
+    p.cold.timeline = nullptr;                                    // set below, once the grid is known
+    p.cold.clock_stamps = (!seg_counter && h->schedule != RTIOW_SCHED_STATIC && h->clock_stamps_dev) ? h->clock_stamps_dev + 4 : nullptr;   // the main (or only) launch; timed renders only
+    p.cold.pixel_times = seg_counter ? h->pixel_times : nullptr;
 #ifdef RTIOW_DEBUG_API
     if (h->probe_n > 0) {                                    // rtiow_debug_hit_world: the tables are laid out, run hit_world on the caller's rays
         if (!lds_source) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_hit_world needs an LDS scene source");
@@ -132,50 +244,15 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
     if (persistent) {
         if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
         HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
-        int per_cu = 0;
-        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, threads, lds));
-        if (per_cu < 1) per_cu = 1;
         const int waves_per_block = (threads + 63) / 64;
-        if (h->waves_per_simd > 0) {                       // knob: fewer resident waves, more pixels per lane
-            const int cap = (h->waves_per_simd * 4 + waves_per_block - 1) / waves_per_block;
-            if (cap < per_cu) per_cu = cap;
-        }
         const long long tile_slots = (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL;
-        // Underfilled launch (fewer 64-pixel pools than resident waves: small frames): let only the first
-        // `lane_cap` lanes of every wave take pixels.  More waves are busy, each permanently in the
-        // cooperative mode, where its idle lanes split the sphere loops of the live ones: a trip gets
-        // shorter, and with so little work the frame is as long as its longest chain of trips.
-        // Measured (profiles/archive/r01_lane_cap_sweep.txt): scene 1 320x192x10 2.27 -> 1.06 ms, 640x384x100
-        // 19.4 -> 17.0 ms; frames with at least one pool per wave are unchanged (cap 64).
         int lane_cap = 64;
-        {
-            const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
-            while (lane_cap > 16 && pools * (64 / lane_cap) < waves) lane_cap >>= 1;  // the largest share that keeps every wave busy; not below 16 (with the grid walk 8-lane waves lose: scene 1 320x192x100 6.85 vs 5.96 ms, profiles/archive/r02_lane_cap_sweep.jsonl)
-            lane_cap = tuned("RTIOW_TUNE_LANE_CAP", lane_cap);
-        }
-        p.lane_cap = lane_cap;
-        // fp32: the bounded rejection loop where throughput binds -- at least four pools per resident wave (1080p: 6.3; 1280 x 720, shards and small
-        // frames end with one chain's latency and keep the blocking loop) -- if that kernel keeps the occupancy this launch was sized for
         bool bounded_f32 = false;
-        if (sizeof(T) == 4 && h->schedule != RTIOW_SCHED_STATIC) {
-            const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
-#ifdef RTIOW_TUNING
-            const bool want = tuned("RTIOW_TUNE_RUV_BOUNDED", pools >= 4 * waves ? 1 : 0) != 0;
-#else
-            const bool want = pools >= 4 * waves;
-#endif
-            if (want) {
-                RenderFn<T> kb = pick_bounded_kernel<T>(false, lds_source, seg_counter != nullptr);
-                if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                int per_cu_b = 0;
-                HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, (const void*)kb, threads, lds));
-                if (per_cu_b >= per_cu) { k = kb; bounded_f32 = true; HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k)); }
-            }
-        }
-        long long blocks = (long long)h->num_cus * per_cu;
-        const long long per_block = (long long)waves_per_block * lane_cap;
-        const long long useful = (tile_slots + per_block - 1) / per_block;
-        if (blocks > useful) blocks = useful;               // never more waves than lane_cap-pixel shares of the pools
+        long long blocks = 0;
+        int rc1 = size_persistent<T>(h, k, pick_bounded_kernel<T>(false, lds_source, seg_counter != nullptr), threads, lds, tile_slots, lane_cap, bounded_f32, blocks);
+        if (rc1) return rc1;
+        if (bounded_f32) HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
+        p.lane_cap = lane_cap;
         grid = dim3((unsigned)blocks);
 
         const int npix = p.cold.W * h->local_rows;
@@ -248,50 +325,9 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
             if (h->time_phases) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
             h->stats.prepass_samples = SA;
             HIP_TRY(h, hipGetLastError());
-            // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools.
-            // Blocks of the order are one "age class" of resident waves wide (see first_pools).
-            unsigned* hist = h->sort_scratch; unsigned* start = hist + COST_BINS; unsigned* fill = start + COST_BINS;
-            HIP_TRY(h, hipMemsetAsync(hist, 0, COST_BINS * sizeof(unsigned), h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->order, 0xff, ((size_t)total_pools * POOL + (size_t)solo_slots) * sizeof(int), h->stream));
-            const int sort_blocks = (npix + 255) / 256;
-            const uint32_t* rank_by = h->cost;
-            int smooth_hw = 6;                          // 13 x 13 window: profiles/archive/r02_cost_smoothing_sweep.jsonl
-            smooth_hw = tuned("RTIOW_TUNE_SMOOTH", smooth_hw);
-            if (smooth_hw > 0) {
-                if (smooth_hw > 24) smooth_hw = 24;      // 2 x (tile + halo) words of LDS: 37 KB at 24
-                const int smooth_blocks = ((p.cold.W + SMOOTH_TW - 1) / SMOOTH_TW) * ((h->local_rows + SMOOTH_TH - 1) / SMOOTH_TH);
-                const size_t smooth_lds_bytes = ((size_t)(SMOOTH_TW + 2 * smooth_hw) + SMOOTH_TW) * (size_t)(SMOOTH_TH + 2 * smooth_hw) * sizeof(uint32_t);
-                // one rank: its strips are adjacent in the image, the window may cross them (it did not before: 13 x <= 8 rows)
-                int window_strip = h->nranks == 1 ? (h->local_rows > 0 ? h->local_rows : 1) : h->strip_rows;
-                if (const int ws = tuned("RTIOW_TUNE_SMOOTH_STRIP", -1); ws >= 0) window_strip = ws > 0 ? ws : (h->local_rows > 0 ? h->local_rows : 1);
-                hipLaunchKernelGGL(cost_smooth_kernel, dim3(smooth_blocks), dim3(256), smooth_lds_bytes, h->stream, h->cost, h->cost_rank, p.cold.W, h->local_rows, window_strip, smooth_hw, hist);
-                rank_by = h->cost_rank;
-            } else {
-                hipLaunchKernelGGL(cost_hist_kernel, dim3(sort_blocks < 1024 ? sort_blocks : 1024), dim3(256), 0, h->stream, rank_by, npix, hist);
-            }
-            hipLaunchKernelGGL(cost_scan_kernel, dim3(1), dim3(COST_BINS), 0, h->stream, hist, start, fill);
+            // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools
+            if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of : nullptr))) return rc;
             const int resident_waves = (int)blocks * waves_per_block;
-            const int age_classes = (int)((blocks + h->num_cus - 1) / h->num_cus);
-            int pools_per_block = (resident_waves + age_classes - 1) / age_classes;
-            if (pools_per_block > total_pools) pools_per_block = total_pools;
-            // Deal granularity: `deal_group` consecutive ranks (= neighbouring pixels of equal cost) stay
-            // in one pool, the groups go round-robin over the block's pools.  Coherent groups mean fewer
-            // distinct spheres pass the screen per wave (8.9 exact blocks per wave-iteration with single
-            // ranks vs 3.6 in tile order); mixed costs in a pool let a heavy pixel finish in the fast
-            // cooperative mode, which is what small shards need.  Measured (profiles/archive/r01_deal_group_sweep.txt):
-            // full frame 24.1 -> 22.5 ms with 16-32, half frame 14.7 -> 14.0 with 8, quarter and eighth
-            // frames are fastest with 1.
-            const double pools_per_wave = (double)total_pools / (double)resident_waves;
-            // With the grid walk (a lane's cost follows ITS ray) coherence pays more: whole pools of 64 neighbouring
-            // ranks, 15.3 -> 14.7 ms on the full frame (profiles/archive/r02_tune_sweep.jsonl) and, once the ranks come from
-            // the smoothed cost, on every frame with at least 2.5 pools per wave (1280x720: 9.3 ms with groups of 1,
-            // 11.4 with 8, 8.7 with 64; profiles/archive/r02_cost_smoothing_sweep.jsonl); smaller shards keep single ranks.
-            int deal_group = pools_per_wave >= 2.5 ? 64 : 1;
-            deal_group = tuned("RTIOW_TUNE_DEAL", deal_group);
-            const int scatter_blocks = ((p.cold.W + 63) / 64) * ((h->local_rows + 63) / 64);   // one per 64 x 64 super-tile
-            hipLaunchKernelGGL(cost_scatter_kernel, dim3(scatter_blocks), dim3(1024), 0, h->stream, rank_by, p.cold.W, h->local_rows, start, fill, h->order,
-                               pools_per_block, total_pools, deal_group, solo_slots, staged_stores ? h->slot_of : nullptr);
-            HIP_TRY(h, hipGetLastError());
             // ---- main launch: samples [SA, S) in that order
             p.cold.s_begin = SA; p.cold.mid_in = h->mid; p.cold.order = h->order;
             p.cold.total_slots = solo_slots + total_pools * POOL;
@@ -342,6 +378,92 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
         h->stats.solo_lanes = phases == 2 && p.cold.solo_waves > 0 ? p.cold.solo_lanes : 0;
         h->stats.staged_stores = p.cold.stage_by_slot;
     }
+    return 0;
+}
+
+// One chunk of progressive rendering (rtiow_accumulate): samples [h->acc_samples, h->acc_samples + samples) of every local pixel through
+// render_accumulate_kernel, always with the persistent hand-out (four-wave workgroups, the sizing of launch_render).  The first chunk after
+// a reset starts from the RNG states of rtiow_init_rng in tile order; under RTIOW_SCHED_SORTED every later chunk ranks the pixels
+// heavy-first by the segments each ran in the previous chunk (same limits as launch_render).  No solo waves, no staged stores: the preview
+// is stored at its pixel.  timed: the start event goes behind the allocations and table builds, in front of the first enqueued work.
+template <class T, class CAM>
+int launch_accumulate(rtiow_handle_s* h, const CAM& cam, int samples, bool timed) {
+    RenderParams<T> p = make_params<T>(h, cam);
+    const int bx = 16, by = 16, threads = bx * by;
+    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = 1;
+    p.cold.seg_counter = nullptr; p.cold.timeline = nullptr; p.cold.pixel_times = nullptr;
+    p.cold.clock_stamps = timed && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
+    size_t lds = 0;
+    bool lds_source = false;
+    int effective_source = h->scene_source;
+    int rc = layout_lds<T>(h, p, threads, true, true, lds, lds_source, effective_source);
+    if (rc) return rc;
+    RenderFn<T> k = lds_source ? (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_LDS> : (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_SCALAR>;
+    RenderFn<T> kb = nullptr;                             // fp32: the same kernel with the bounded rejection loop (fp64 bounds it in every kernel)
+    if constexpr (sizeof(T) == 4) kb = lds_source ? (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_LDS, true> : (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_SCALAR, true>;
+    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int waves_per_block = (threads + 63) / 64;
+    const long long tile_slots = (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL;
+    int lane_cap = 64;
+    bool bounded_f32 = false;
+    long long blocks = 0;
+    if ((rc = size_persistent<T>(h, k, kb, threads, lds, tile_slots, lane_cap, bounded_f32, blocks))) return rc;
+    hipFuncAttributes fa{};
+    HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
+    p.lane_cap = lane_cap;
+
+    // The state records ping-pong: the chunk reads acc_mid[acc_cur] and writes the other buffer.
+    const int npix = p.cold.W * h->local_rows;
+    const int n = h->acc_samples;
+    if ((rc = ensure_buffer(h, &h->acc_mid[0], &h->acc_mid_bytes[0], (size_t)npix * sizeof(MidState<T>)))) return rc;
+    if ((rc = ensure_buffer(h, &h->acc_mid[1], &h->acc_mid_bytes[1], (size_t)npix * sizeof(MidState<T>)))) return rc;
+    if ((rc = ensure_buffer(h, &h->acc_cost, &h->acc_cost_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
+    if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
+    const bool ranked = h->schedule == RTIOW_SCHED_SORTED && n > 0 && npix >= 4096 && p.cold.W < 65536 && h->local_rows < 32768;   // (row << 16 | column)
+    const int total_pools = (npix + POOL - 1) / POOL;
+    if (ranked) {
+        if ((rc = ensure_buffer(h, &h->cost_rank, &h->cost_rank_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure_buffer(h, &h->order, &h->order_bytes, (size_t)total_pools * POOL * sizeof(int)))) return rc;
+        if ((rc = ensure_buffer(h, &h->sort_scratch, &h->sort_scratch_bytes, (size_t)3 * COST_BINS * sizeof(unsigned)))) return rc;
+    }
+    const int in = h->acc_cur, out = n > 0 ? 1 - in : 0;
+    p.cold.s_begin = n; p.s_end = n + samples;
+    p.cold.pixel_samples_scale = (T)1 / (T)(n + samples);   // rtiow_host_camera's 1 / samples_per_pixel at the running total
+    p.cold.rng_in = h->rng;
+    p.cold.mid_in = n > 0 ? h->acc_mid[in] : nullptr;
+    p.cold.mid_out = h->acc_mid[out];
+    p.cold.cost_out = h->acc_cost;
+    p.cold.order = nullptr; p.cold.total_slots = (int)tile_slots; p.cold.first_pools = 0;
+    p.cold.work_counter = h->work_counter;
+    p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
+
+    if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
+    if (ranked) {
+        // the previous chunk's segment counts rank this one (the launch below overwrites them: stream order)
+        if ((rc = rank_pixels(h, h->acc_cost, blocks, waves_per_block, total_pools, 0, nullptr))) return rc;
+        p.cold.order = h->order;
+        p.cold.total_slots = total_pools * POOL;
+        p.cold.work_counter = h->work_counter + 1;
+        p.cold.first_pools = 1;
+        const unsigned counter_start = (unsigned)blocks * (unsigned)waves_per_block * (unsigned)lane_cap;
+        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)(h->work_counter + 1), (int)counter_start, 1, h->stream));
+    }
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, p);
+    HIP_TRY(h, hipGetLastError());
+    h->acc_cur = out;
+    h->stats.vgprs = fa.numRegs;
+    h->stats.sgprs = 0;
+    h->stats.lds_bytes = (int)(lds + fa.sharedSizeBytes);
+    h->stats.block_x = bx; h->stats.block_y = by;
+    h->stats.scene_source = effective_source;
+    h->stats.schedule = h->schedule;
+    h->stats.grid_blocks = (int)blocks;
+    h->stats.phases = 1;
+    h->stats.prepass_samples = 0;
+    h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
+    h->stats.staged_stores = 0;
+    h->stats.primary_rays = (uint64_t)npix * (uint64_t)samples;
     return 0;
 }
 

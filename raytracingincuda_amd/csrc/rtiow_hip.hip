@@ -179,7 +179,8 @@ int rtiow_destroy(rtiow_handle h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->geom_a, h->shade_tbl, h->geom_s, h->grid_blob, h->cost_rank, h->rng, h->jump, h->work_counter, h->mid, h->slot_of, h->staged,
-                    h->cost, h->order, h->sort_scratch, h->levels, h->rng_low_table, h->fb_external ? nullptr : h->fb};
+                    h->cost, h->order, h->sort_scratch, h->levels, h->rng_low_table, h->acc_mid[0], h->acc_mid[1], h->acc_cost,
+                    h->fb_external ? nullptr : h->fb};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->clock_stamps) (void)hipHostFree(h->clock_stamps);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -208,6 +209,7 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (!h) return RTIOW_E_BADARG;
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
+    h->acc_samples = 0;
     if (h->precision == 32) return upload_scene<float>(h, n, (const float*)center_radius, (const float*)albedo_fuzz, (const float*)refraction_index, type, valid);
     return upload_scene<double>(h, n, (const double*)center_radius, (const double*)albedo_fuzz, (const double*)refraction_index, type, valid);
 }
@@ -222,6 +224,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
     h->rng_ready = false;
+    h->acc_samples = 0;
     return 0;
 }
 
@@ -229,6 +232,7 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (!h) return RTIOW_E_BADARG;
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
     h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
+    h->acc_samples = 0;
     if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
     h->rng_ready = false;
     return 0;
@@ -253,6 +257,7 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_init_rng before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
+    h->acc_samples = 0;
     const int W = img_w(h), H = img_h(h);
     int index_bits = 1;                                      // bits of the largest GLOBAL pixel index W*H-1
     while (index_bits < XW_JUMPS && ((uint64_t)W * (uint64_t)H - 1) >> index_bits) ++index_bits;
@@ -372,6 +377,48 @@ int rtiow_render_async(rtiow_handle h, int threads_per_block_row) {
 int rtiow_render_wait(rtiow_handle h, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     return render_wait(h, kernel_ms);
+}
+
+int rtiow_accumulate_reset(rtiow_handle h) {
+    if (!h) return RTIOW_E_BADARG;
+    h->acc_samples = 0;
+    return 0;
+}
+
+int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    (void)threads_per_block_row;                         // chunks always run through the persistent hand-out
+    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_set_scene/rtiow_set_camera");
+    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_init_rng");
+    if (samples <= 0 || samples > 0x7fffffff - h->acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_framebuffer(h);
+    if (rc) return rc;
+    h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
+    if (kernel_ms) *kernel_ms = 0;
+    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->acc_samples += samples; return 0; }
+    const bool timed = kernel_ms != nullptr;
+    if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
+    if (h->precision == 32) rc = launch_accumulate<float>(h, h->cam32, samples, timed);
+    else rc = launch_accumulate<double>(h, h->cam64, samples, timed);
+    if (rc) return rc;
+    h->acc_samples += samples;
+    h->stats.prepass_ms = 0; h->stats.place_ms = 0;
+    if (timed) {
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        HIP_TRY(h, hipEventSynchronize(h->ev1));
+        float ms = 0;
+        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        *kernel_ms = ms;
+        h->stats.render_ms = ms; h->stats.main_ms = ms;
+    }
+    return 0;
+}
+
+int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
+    if (!h || !samples) return RTIOW_E_BADARG;
+    *samples = h->acc_samples;
+    return 0;
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {

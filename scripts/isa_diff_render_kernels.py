@@ -1,0 +1,71 @@
+"""Compare the device code of the existing render kernels between two builds.
+
+    python scripts/isa_diff_render_kernels.py --ref HEAD~1        # the tree at a git ref (exported with git archive) against the working tree
+    python scripts/isa_diff_render_kernels.py BEFORE.s AFTER.s    # two `hipcc -S --cuda-device-only` listings
+
+Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel and render_solo_kernel is cut from its label
+to its .Lfunc_end and compared text for text.  This shows that a change confined to new kernels (e.g. the ACCUM flag of
+persistent_body) leaves the existing ones as they were.  Exit status 1 if any of them differ or is missing.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tarfile
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<")
+
+
+def listing(src_root, out):
+    from raytracingincuda_amd import build as b
+    flags = [f for f in b.HIP_FLAGS if f != "-shared" and not f.startswith("-I")] + ["-I" + os.path.join(src_root, "include")]
+    subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(src_root, "raytracingincuda_amd", "csrc", "rtiow_hip.hip")],
+                   check=True, stderr=subprocess.DEVNULL)
+    return out
+
+
+def bodies(path):
+    text = open(path).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\S+):", text, re.M):
+        out[m.group(1)] = text[m.start():text.index(".Lfunc_end", m.end())]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("listings", nargs="*")
+    ap.add_argument("--ref", default="")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        if a.ref:
+            tar = os.path.join(tmp, "ref.tar")
+            subprocess.run(["git", "-C", ROOT, "archive", "-o", tar, a.ref], check=True)
+            old_root = os.path.join(tmp, "ref")
+            with tarfile.open(tar) as t:
+                t.extractall(old_root)
+            before, after = listing(old_root, os.path.join(tmp, "before.s")), listing(ROOT, os.path.join(tmp, "after.s"))
+        elif len(a.listings) == 2:
+            before, after = a.listings
+        else:
+            ap.error("give --ref REF or two listings")
+        old, new = bodies(before), bodies(after)
+    names = sorted(old)
+    dem = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()))
+    kept = [n for n in names if any(k in dem[n] for k in EXISTING)]
+    diff = [dem[n] for n in kept if old[n] != new.get(n)]
+    print("existing render kernels compared: %d, differing or missing: %d" % (len(kept), len(diff)))
+    for d in diff:
+        print("  DIFF", d)
+    added = [n for n in new if n not in old]
+    for d in subprocess.run(["c++filt"], input="\n".join(added), capture_output=True, text=True, check=True).stdout.splitlines():
+        print("  new", d)
+    return 1 if diff or not kept else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
