@@ -216,6 +216,32 @@ int rtiow_accumulate_reset(rtiow_handle h);
 int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms);
 int rtiow_accumulated_samples(rtiow_handle h, int* samples);
 
+/* ---- Adaptive progressive rendering: every pixel has its own sample count n_p.  Each pixel keeps its colour sum, s2 = the sum of the
+ * squared luminance Y = 0.2126 r + 0.7152 g + 0.0722 b of its samples (in the handle's precision, in sample order) and n_p; after every
+ * adaptive chunk the library computes, in double, err_p = sqrt(var / n) / (m + 1e-3) with m = Y(sum) / n and
+ * var = max(0, (s2 - n m^2) / (n - 1)) -- the relative standard error of the mean luminance; +inf for n < 2 -- and stores it as float.
+ *
+ * rtiow_accumulate_adaptive renders `samples` more samples of every ACTIVE local pixel: one with (n_p < min_samples or
+ * (double)err_p > rel_error) and n_p + samples <= max_samples, err_p being what the previous call left (+inf before the first), so no count
+ * passes max_samples.  Inactive pixels are not traced.  The framebuffer then holds the preview of every local pixel, the exact bits
+ * rtiow_render leaves for that pixel with samples_per_pixel = n_p (same camera and seed): a pixel's samples are one sequential RNG chain
+ * summed in sample order.  The whole image is rewritten by every call.  *active_pixels (may be NULL) receives the number of pixels that
+ * ran: 0 = converged (no render kernel is launched; the preview is still written).  The call blocks once, to read the active count back
+ * before the render launch.  kernel_ms (NULL: not timed) = HIP-event time of the select, render and finish kernels, without that read-back.
+ * rtiow_accumulated_samples reports the largest n_p in this mode.
+ * RTIOW_E_BADARG: samples <= 0, min_samples < 0, max_samples < min_samples, rel_error < 0 or NaN, a frame 65536 or more pixels wide or
+ * a shard of 32768 or more local rows (the hand-out order packs a pixel as row << 16 | column).  RTIOW_E_STATE before scene, camera
+ * and RNG are set up.  A handle without local rows launches nothing.
+ * The first chunk after a reset fixes the mode: rtiow_accumulate after adaptive chunks, and rtiow_accumulate_adaptive after plain ones,
+ * return RTIOW_E_STATE until rtiow_accumulate_reset.  Resets, isolation from rtiow_render and the state kept by set_scene_source,
+ * set_schedule and bind_framebuffer are those of rtiow_accumulate.  The adaptive chunk always uses the persistent hand-out (the schedule
+ * does not change the image).  Not available on groups.
+ *
+ * rtiow_read_adaptive_state copies n_p and err_p of every local pixel (row-major local order) to host memory; either pointer may be NULL.
+ * npix must equal local_rows x width (RTIOW_E_BADARG).  Before an adaptive chunk: n = 0 and err = +inf. */
+int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels);
+int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

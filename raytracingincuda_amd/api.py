@@ -90,7 +90,7 @@ HIP_SYMBOLS = [
     "rtiow_init_rng", "rtiow_render", "rtiow_count_segments", "rtiow_bind_framebuffer", "rtiow_framebuffer_device_ptr",
     "rtiow_read_framebuffer", "rtiow_read_levels", "rtiow_set_scene_source", "rtiow_set_schedule", "rtiow_get_stats", "rtiow_synchronize",
     "rtiow_render_async", "rtiow_render_wait", "rtiow_stream", "rtiow_device",
-    "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples",
+    "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples", "rtiow_accumulate_adaptive", "rtiow_read_adaptive_state",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -189,6 +189,9 @@ def load_hip_library(debug=False):
         lib.rtiow_accumulate_reset.argtypes = [H]
         lib.rtiow_accumulate.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_accumulated_samples.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
+        lib.rtiow_accumulate_adaptive.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
+        lib.rtiow_read_adaptive_state.argtypes = [H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -490,6 +493,31 @@ class Renderer:
         n = ctypes.c_int(0)
         self._check(self._lib.rtiow_accumulated_samples(self._h, ctypes.byref(n)))
         return n.value
+
+    def accumulate_adaptive(self, samples, rel_error, min_samples=0, max_samples=2 ** 31 - 1, sync=True):
+        """Adaptive progressive rendering: `samples` more samples for every pixel that is still active -- its count below min_samples
+        or its relative error (adaptive_state) above rel_error, and count + samples <= max_samples -- and the preview of every pixel in
+        the framebuffer (bit for bit what render() gives that pixel with samples_per_pixel = its count).  Returns (kernel ms or None when
+        sync=False, active pixels); 0 active pixels means converged.  The call blocks once to read the active count back."""
+        active = ctypes.c_int(0)
+        if sync:
+            ms = ctypes.c_float(0)
+            self._check(self._lib.rtiow_accumulate_adaptive(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
+                                                            ctypes.byref(ms), ctypes.byref(active)))
+            return ms.value, active.value
+        self._check(self._lib.rtiow_accumulate_adaptive(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
+                                                        None, ctypes.byref(active)))
+        return None, active.value
+
+    def adaptive_state(self):
+        """(counts, rel_err): each pixel's sample count (int32) and relative standard error of its mean luminance (float32, +inf below
+        two samples), local_rows x width."""
+        rows, w = self.local_rows, self.width
+        counts = np.zeros((rows, w), np.int32)
+        err = np.zeros((rows, w), np.float32)
+        self._check(self._lib.rtiow_read_adaptive_state(self._h, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                        err.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows * w))
+        return counts, err
 
     def count_segments(self, threads=8):
         """Untimed render that also counts path segments (hit_world calls)."""

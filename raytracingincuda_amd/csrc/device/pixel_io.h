@@ -115,6 +115,70 @@ __device__ __forceinline__ void accumulate_pixel(const COLD& c, size_t lp, const
     store_pixel<T>(c, lp, st.acc);
 }
 
+// ---- Adaptive progressive rendering (rtiow_accumulate_adaptive).  The path state of the adaptive body also carries s2, the sum of the
+// squared luminance of the pixel's samples in sample order; its record keeps s2 in the padding of MidState (fp32: pad[0]; fp64: pad[0..1],
+// a double at offset 24), so the records stay 48 / 64 bytes.  The pixel's sample count is not in the record: it lives in the handle's
+// count array, which adaptive_select_kernel advances for the active pixels.  Carried through the path loop, or re-read at the end of the
+// pixel to be parked next to s2, it cost the fp64 kernels 1-3 SGPR spills beyond the plain persistent kernel's (compiler metadata).
+template <class T> struct AdaptPathState : PathState<T> { T s2; };
+
+// Luminance of a colour (Rec. 709 weights), in T, as three products and two additions in this order (-ffp-contract=off: nothing is fused).
+// fp64: the weights are not inline constants; made opaque VGPR values where they are used, they are built there instead of being hoisted
+// out of the path loop into three SGPR pairs live across it (which cost the fp64 kernels SGPR spills beyond the plain persistent kernel's).
+template <class T>
+__device__ __forceinline__ T luminance(V3<T> c) {
+    T wr = (T)0.2126, wg = (T)0.7152, wb = (T)0.0722;
+    if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(wr), "+v"(wg), "+v"(wb));
+    const T r = wr * c.x, g = wg * c.y, b = wb * c.z;
+    return (r + g) + b;
+}
+
+// s2 and, in the next word (fp32 pad[1], fp64 pad2[0]), the samples the pixel ran in the chunk that parked the record (0: select kernel).
+// Nothing reads that word; storing the live sample counter there rather than a constant happens to keep the fp64 kernels at the plain
+// persistent kernel's SGPR spills.
+template <class T> __device__ __forceinline__ void set_s2(MidState<T>& m, T s2, uint32_t ran);
+template <> __device__ __forceinline__ void set_s2<float>(MidState<float>& m, float s2, uint32_t ran) { m.pad[0] = __float_as_uint(s2); m.pad[1] = ran; m.pad[2] = 0; }
+template <> __device__ __forceinline__ void set_s2<double>(MidState<double>& m, double s2, uint32_t ran) { __builtin_memcpy(m.pad, &s2, 8); m.pad2[0] = ran; m.pad2[1] = 0; }
+template <class T> __device__ __forceinline__ T adapt_s2(const MidState<T>& m);
+template <> __device__ __forceinline__ float adapt_s2<float>(const MidState<float>& m) { return __uint_as_float(m.pad[0]); }
+template <> __device__ __forceinline__ double adapt_s2<double>(const MidState<double>& m) { double s; __builtin_memcpy(&s, m.pad, 8); return s; }
+
+template <class T>
+__device__ __forceinline__ MidState<T> load_record(const unsigned char* base, size_t lp) {
+    MidState<T> m;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const u4* src = reinterpret_cast<const u4*>(base + lp * sizeof(MidState<T>));
+    u4* dst = reinterpret_cast<u4*>(&m);
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(MidState<T>) / 16); ++k) dst[k] = src[k];
+    return m;
+}
+template <class T>
+__device__ __forceinline__ void store_record(unsigned char* base, size_t lp, const MidState<T>& m) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const u4* src = reinterpret_cast<const u4*>(&m);
+    u4* dst = reinterpret_cast<u4*>(base + lp * sizeof(MidState<T>));
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(MidState<T>) / 16); ++k) dst[k] = src[k];
+}
+template <class T>
+__device__ __forceinline__ void unpark_adaptive(const unsigned char* base, size_t lp, AdaptPathState<T>& st) {
+    const MidState<T> m = load_record<T>(base, lp);
+    st.rs.v0 = m.v[0]; st.rs.v1 = m.v[1]; st.rs.v2 = m.v[2]; st.rs.v3 = m.v[3]; st.rs.v4 = m.v[4]; st.rs.d = m.d;
+    st.acc = {m.acc[0], m.acc[1], m.acc[2]};
+    st.s2 = adapt_s2<T>(m);
+}
+// End of a pixel in an adaptive chunk (render_adaptive_kernel): park the exact state with s2.  No preview here: adaptive_finish_kernel
+// writes every pixel's.
+template <class T, class COLD>
+__device__ __forceinline__ void adaptive_pixel(const COLD& c, size_t lp, const AdaptPathState<T>& st) {
+    MidState<T> m;
+    m.v[0] = st.rs.v0; m.v[1] = st.rs.v1; m.v[2] = st.rs.v2; m.v[3] = st.rs.v3; m.v[4] = st.rs.v4; m.d = st.rs.d;
+    m.acc[0] = st.acc.x; m.acc[1] = st.acc.y; m.acc[2] = st.acc.z;
+    set_s2<T>(m, st.s2, (uint32_t)st.sample);
+    store_record<T>(c.mid_out, lp, m);
+}
+
 template <class T, class COLD>
 __device__ __forceinline__ void finish_pixel(const COLD& c, size_t lp, const PathState<T>& st, unsigned int cost) {
     if (c.mid_out) {

@@ -1,4 +1,4 @@
-// render_kernels.h -- the render kernels: static (reference geometry), persistent / prepass / solo / accumulate (progressive chunks), debug kernels
+// render_kernels.h -- the render kernels: static (reference geometry), persistent / prepass / solo / accumulate (progressive chunks) / adaptive, debug kernels
 // Part of the single gfx950 translation unit rtiow_hip.hip (included there, in this order; internal linkage).
 #pragma once
 #include "shade.h"
@@ -104,7 +104,7 @@ __device__ __forceinline__ void clock_stamp(const RenderParams<T>& p, int slot) 
     }
 }
 
-template <class T, int SRC, bool COUNT, bool SOLO = false, bool BOUND_F32 = false, bool ACCUM = false>
+template <class T, int SRC, bool COUNT, bool SOLO = false, bool BOUND_F32 = false, bool ACCUM = false, bool ADAPT = false>
 __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
     const T* lds_geom = stage_scene<T, SRC>(p);
     // per-wave scratch for hit_world_coop, behind the staged tables
@@ -114,8 +114,9 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
     const int S = p.s_end;                       // this launch renders samples [cold.s_begin, p.s_end)
     clock_stamp(p, 0);                           // ColdParams::clock_stamps: one lane of the launch, here and behind the loop
 
-    PathState<T> st;
+    std::conditional_t<ADAPT, AdaptPathState<T>, PathState<T>> st;   // ADAPT: with s2, the sum of squared sample luminance
     st.acc = {0, 0, 0};
+    if constexpr (ADAPT) st.s2 = 0;
     st.sample = 0; st.depth = 0;
     unsigned int cost = 0;                       // segments of the lane's current pixel in this launch
 #ifndef RTIOW_RUV_BOUNDED_F64
@@ -199,12 +200,15 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                         want = false;
                         j = c.nranks == 1 ? jl : global_row(jl, c.strip_rows, c.nranks, c.rank);
                         lp = (size_t)jl * c.W + i;
-                        if (c.mid_in) unpark_state<T>(c.mid_in, lp, st);
-                        else {
+                        if (c.mid_in) {
+                            if constexpr (ADAPT) unpark_adaptive<T>(c.mid_in, lp, st);
+                            else unpark_state<T>(c.mid_in, lp, st);
+                        } else {
                             const size_t npix = (size_t)c.W * c.local_rows;
                             st.rs.v0 = c.rng_in[0 * npix + lp]; st.rs.v1 = c.rng_in[1 * npix + lp]; st.rs.v2 = c.rng_in[2 * npix + lp];
                             st.rs.v3 = c.rng_in[3 * npix + lp]; st.rs.v4 = c.rng_in[4 * npix + lp]; st.rs.d = c.rng_in[5 * npix + lp];
                             st.acc = {0, 0, 0};
+                            if constexpr (ADAPT) st.s2 = 0;
                         }
                         st.sample = c.s_begin; st.depth = 0;
                         cost = 0;
@@ -214,7 +218,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                         if (c.stage_by_slot) lp = (size_t)slot;      // where this pixel will be stored (ColdParams::stage_by_slot); the state is loaded
                         if (COUNT) ++n_pixels;
                         if (c.s_begin < S) { alive = true; fresh = true; }
-                        else { if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost); want = true; }   // nothing to render in this launch
+                        else { if constexpr (ADAPT) adaptive_pixel<T>(c, lp, st); else if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost); want = true; }   // nothing to render in this launch
                     }
                 }
             }
@@ -246,7 +250,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                 PATH_STAT(PS_FINISH_PIXEL); \
                 const auto& c_ = cold_of(p); \
                 if (COUNT) atomicMax(c_.seg_counter + 2, (unsigned long long)cost); \
-                if constexpr (ACCUM) accumulate_pixel<T>(c_, lp, st, cost); else finish_pixel<T>(c_, lp, st, cost); \
+                if constexpr (ADAPT) adaptive_pixel<T>(c_, lp, st); else if constexpr (ACCUM) accumulate_pixel<T>(c_, lp, st, cost); else finish_pixel<T>(c_, lp, st, cost); \
                 alive = false; \
             } } while (0)
         for (;;) {
@@ -280,6 +284,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                 }
                 if (terminated) {
                     st.acc = {st.acc.x + col.x, st.acc.y + col.y, st.acc.z + col.z};   // camera.h:160
+                    if constexpr (ADAPT) { const T y = luminance<T>(col); st.s2 = st.s2 + y * y; }
                     RT_END_SAMPLE();
                 }
             }
@@ -382,6 +387,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
         REGION_BEGIN(acc);
         if (alive && terminated) {
             st.acc = {st.acc.x + col.x, st.acc.y + col.y, st.acc.z + col.z};       // camera.h:160
+            if constexpr (ADAPT) { const T y = luminance<T>(col); st.s2 = st.s2 + y * y; }
             ++st.sample;
             st.depth = 0;
             if (st.sample < S) fresh = true;
@@ -398,7 +404,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                     o[3] = blockIdx.x * ((blockDim.x + 63) >> 6) + (threadIdx.x >> 6);
                 }
 #endif
-                if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost);
+                if constexpr (ADAPT) adaptive_pixel<T>(c, lp, st); else if constexpr (ACCUM) accumulate_pixel<T>(c, lp, st, cost); else finish_pixel<T>(c, lp, st, cost);
                 alive = false;
             }
         }
@@ -443,6 +449,13 @@ __global__ void __launch_bounds__(1024) render_solo_kernel(const RenderParams<T>
 // buffers, so mid_in and mid_out never alias (both are __restrict__).  The plain kernels above compile exactly as before (ACCUM = false).
 template <class T, int SRC, bool BOUND_F32 = false>
 __global__ void __launch_bounds__(1024) RT_MAIN_OCCUPANCY render_accumulate_kernel(const RenderParams<T> p) { persistent_body<T, SRC, false, false, BOUND_F32, true>(p); }
+// Adaptive progressive rendering (rtiow_accumulate_adaptive): samples [0, s_end) of the chunk for the active pixels only, which
+// adaptive_select_kernel listed in cold.order ((row << 16 | column), -1 padding; explicit order, no tile order).  A pixel starts from
+// cold.rng_in with zero sums (first chunk after a reset) or from its record in cold.mid_in, adds Y(colour)^2 of every sample to s2 next to
+// the colour sum and parks both with its new count in cold.mid_out (adaptive_pixel).  No preview and no cost record: adaptive_finish_kernel
+// writes every pixel's preview.  The kernels above compile exactly as before (ADAPT = false).
+template <class T, int SRC, bool BOUND_F32 = false>
+__global__ void __launch_bounds__(1024) RT_MAIN_OCCUPANCY render_adaptive_kernel(const RenderParams<T> p) { persistent_body<T, SRC, false, false, BOUND_F32, false, true>(p); }
 
 #ifdef RTIOW_DEBUG_API       // kernels behind the test hooks of include/rtiow_debug.h
 // Elementwise arithmetic probes (tests compare these with the host bit for bit).

@@ -3,6 +3,8 @@
 #pragma once
 #include "../device/params.h"
 
+enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive
+
 struct rtiow_handle_s {
     int device = 0;
     int precision = 32;
@@ -60,6 +62,12 @@ struct rtiow_handle_s {
     int acc_cur = 0;
     unsigned char* acc_mid[2] = {nullptr, nullptr}; size_t acc_mid_bytes[2] = {0, 0};
     uint32_t* acc_cost = nullptr; size_t acc_cost_bytes = 0;
+    // adaptive progressive rendering (rtiow_accumulate_adaptive): the mode the first chunk after a reset fixed (ACC_MODE_*), the
+    // per-pixel count and relative error the last adaptive chunk left, and {active pixels, largest count} of that chunk
+    int acc_mode = 0;
+    int32_t* adapt_counts = nullptr; size_t adapt_counts_bytes = 0;
+    float* adapt_err = nullptr; size_t adapt_err_bytes = 0;
+    unsigned* adapt_ctr = nullptr; size_t adapt_ctr_bytes = 0;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

@@ -1,8 +1,9 @@
-// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering
+// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering; launch_adaptive: one adaptive chunk
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
 #include "../device/render_kernels.h"
+#include "../device/adaptive.h"
 #include "../device/cost_sort.h"
 
 namespace {
@@ -464,6 +465,99 @@ int launch_accumulate(rtiow_handle_s* h, const CAM& cam, int samples, bool timed
     h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
     h->stats.staged_stores = 0;
     h->stats.primary_rays = (uint64_t)npix * (uint64_t)samples;
+    return 0;
+}
+
+// One adaptive chunk (rtiow_accumulate_adaptive): adaptive_select_kernel lists the active pixels in h->order and copies the records of the
+// others, the host reads the active count back (the call blocks here once), render_adaptive_kernel renders `samples` more samples of the
+// active pixels with a persistent grid sized from the active slots (four-wave workgroups, the sizing of launch_render), and
+// adaptive_finish_kernel writes every pixel's preview, count and error.  The records ping-pong between h->acc_mid[0/1] like
+// launch_accumulate's.  No ranking by previous cost and no solo waves.  timed: ev0 -> ev_a (select) plus ev_b -> ev1 (render and finish):
+// the read-back between them is not counted.  The caller has checked W < 65536 and local_rows < 32768 (the order's encoding).
+template <class T, class CAM>
+int launch_adaptive(rtiow_handle_s* h, const CAM& cam, int samples, int min_samples, double rel_error, int max_samples, bool timed, int& active) {
+    RenderParams<T> p = make_params<T>(h, cam);
+    const int bx = 16, by = 16, threads = bx * by;
+    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = 1;
+    p.cold.seg_counter = nullptr; p.cold.timeline = nullptr; p.cold.pixel_times = nullptr;
+    p.cold.clock_stamps = timed && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
+    size_t lds = 0;
+    bool lds_source = false;
+    int effective_source = h->scene_source;
+    int rc = layout_lds<T>(h, p, threads, true, true, lds, lds_source, effective_source);
+    if (rc) return rc;
+    RenderFn<T> k = lds_source ? (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_LDS> : (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_SCALAR>;
+    RenderFn<T> kb = nullptr;                             // fp32: the same kernel with the bounded rejection loop (fp64 bounds it in every kernel)
+    if constexpr (sizeof(T) == 4) kb = lds_source ? (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_LDS, true> : (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_SCALAR, true>;
+    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+
+    const int W = p.cold.W, npix = W * h->local_rows;
+    const int total_pools = (npix + POOL - 1) / POOL;
+    if ((rc = ensure_buffer(h, &h->acc_mid[0], &h->acc_mid_bytes[0], (size_t)npix * sizeof(MidState<T>)))) return rc;
+    if ((rc = ensure_buffer(h, &h->acc_mid[1], &h->acc_mid_bytes[1], (size_t)npix * sizeof(MidState<T>)))) return rc;
+    if ((rc = ensure_buffer(h, &h->adapt_counts, &h->adapt_counts_bytes, (size_t)npix * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_buffer(h, &h->adapt_err, &h->adapt_err_bytes, (size_t)npix * sizeof(float)))) return rc;
+    if ((rc = ensure_buffer(h, &h->adapt_ctr, &h->adapt_ctr_bytes, 2 * sizeof(unsigned)))) return rc;
+    if ((rc = ensure_buffer(h, &h->order, &h->order_bytes, (size_t)total_pools * POOL * sizeof(int)))) return rc;
+    if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
+    const bool first = h->acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
+    const int in = h->acc_cur, out = first ? 0 : 1 - in;
+    const unsigned char* mid_in = first ? nullptr : h->acc_mid[in];
+    unsigned char* mid_out = h->acc_mid[out];
+
+    if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->adapt_ctr, 0, 2 * sizeof(unsigned), h->stream));
+    const int tiles = ((W + 7) / 8) * ((h->local_rows + 7) / 8);
+    hipLaunchKernelGGL(adaptive_select_kernel<T>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, h->stream, FrameShape{W, h->local_rows},
+                       samples, min_samples, max_samples, rel_error, h->adapt_counts, h->adapt_err, h->rng, mid_in, mid_out, h->order, h->adapt_ctr);
+    HIP_TRY(h, hipGetLastError());
+    if (timed) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
+    unsigned n_active = 0;
+    HIP_TRY(h, hipMemcpyAsync(&n_active, h->adapt_ctr, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    active = (int)n_active;
+    if (timed) HIP_TRY(h, hipEventRecord(h->ev_b, h->stream));
+
+    const long long active_slots = ((long long)n_active + POOL - 1) / POOL * POOL;
+    long long blocks = 0;
+    hipFuncAttributes fa{};
+    if (n_active > 0) {
+        int lane_cap = 64;
+        bool bounded_f32 = false;
+        if ((rc = size_persistent<T>(h, k, kb, threads, lds, active_slots, lane_cap, bounded_f32, blocks))) return rc;
+        HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
+        p.lane_cap = lane_cap;
+        p.cold.s_begin = 0; p.s_end = samples;            // the chunk's own sample numbering: adaptive_pixel adds it to the pixel's count
+        p.cold.pixel_samples_scale = (T)0;                // not read: no preview in the render
+        p.cold.rng_in = h->rng;
+        p.cold.mid_in = mid_in;
+        p.cold.mid_out = mid_out;
+        p.cold.cost_out = nullptr;
+        p.cold.order = h->order; p.cold.total_slots = (int)active_slots; p.cold.first_pools = 0;
+        p.cold.work_counter = h->work_counter;
+        p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
+        if (active_slots > (long long)n_active)           // the tail of the last pool: -1, no pixel
+            HIP_TRY(h, hipMemsetAsync(h->order + n_active, 0xff, (size_t)(active_slots - n_active) * sizeof(int), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (size_t)npix, (const unsigned char*)mid_out,
+                       p.cold.fb, h->adapt_counts, h->adapt_err, h->adapt_ctr + 1);
+    HIP_TRY(h, hipGetLastError());
+    h->acc_cur = out;
+    h->stats.vgprs = fa.numRegs;
+    h->stats.sgprs = 0;
+    h->stats.lds_bytes = n_active > 0 ? (int)(lds + fa.sharedSizeBytes) : 0;
+    h->stats.block_x = bx; h->stats.block_y = by;
+    h->stats.scene_source = effective_source;
+    h->stats.schedule = h->schedule;
+    h->stats.grid_blocks = (int)blocks;
+    h->stats.phases = 1;
+    h->stats.prepass_samples = 0;
+    h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
+    h->stats.staged_stores = 0;
+    h->stats.primary_rays = (uint64_t)n_active * (uint64_t)samples;
     return 0;
 }
 

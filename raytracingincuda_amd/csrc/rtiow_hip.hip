@@ -180,6 +180,7 @@ int rtiow_destroy(rtiow_handle h) {
     (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->geom_a, h->shade_tbl, h->geom_s, h->grid_blob, h->cost_rank, h->rng, h->jump, h->work_counter, h->mid, h->slot_of, h->staged,
                     h->cost, h->order, h->sort_scratch, h->levels, h->rng_low_table, h->acc_mid[0], h->acc_mid[1], h->acc_cost,
+                    h->adapt_counts, h->adapt_err, h->adapt_ctr,
                     h->fb_external ? nullptr : h->fb};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->clock_stamps) (void)hipHostFree(h->clock_stamps);
@@ -209,7 +210,7 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (!h) return RTIOW_E_BADARG;
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->acc_samples = 0;
+    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
     if (h->precision == 32) return upload_scene<float>(h, n, (const float*)center_radius, (const float*)albedo_fuzz, (const float*)refraction_index, type, valid);
     return upload_scene<double>(h, n, (const double*)center_radius, (const double*)albedo_fuzz, (const double*)refraction_index, type, valid);
 }
@@ -224,7 +225,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
     h->rng_ready = false;
-    h->acc_samples = 0;
+    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
     return 0;
 }
 
@@ -232,7 +233,7 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (!h) return RTIOW_E_BADARG;
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
     h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
-    h->acc_samples = 0;
+    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
     if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
     h->rng_ready = false;
     return 0;
@@ -257,7 +258,7 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_init_rng before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->acc_samples = 0;
+    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
     const int W = img_w(h), H = img_h(h);
     int index_bits = 1;                                      // bits of the largest GLOBAL pixel index W*H-1
     while (index_bits < XW_JUMPS && ((uint64_t)W * (uint64_t)H - 1) >> index_bits) ++index_bits;
@@ -381,7 +382,7 @@ int rtiow_render_wait(rtiow_handle h, float* kernel_ms) {
 
 int rtiow_accumulate_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
-    h->acc_samples = 0;
+    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
     return 0;
 }
 
@@ -391,18 +392,20 @@ int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, flo
     if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_set_scene/rtiow_set_camera");
     if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_init_rng");
     if (samples <= 0 || samples > 0x7fffffff - h->acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
+    if (h->acc_mode == ACC_MODE_ADAPTIVE) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate after rtiow_accumulate_adaptive: reset the accumulation first");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
     if (kernel_ms) *kernel_ms = 0;
-    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->acc_samples += samples; return 0; }
+    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->acc_samples += samples; h->acc_mode = ACC_MODE_PLAIN; return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
     if (h->precision == 32) rc = launch_accumulate<float>(h, h->cam32, samples, timed);
     else rc = launch_accumulate<double>(h, h->cam64, samples, timed);
     if (rc) return rc;
     h->acc_samples += samples;
+    h->acc_mode = ACC_MODE_PLAIN;
     h->stats.prepass_ms = 0; h->stats.place_ms = 0;
     if (timed) {
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -417,7 +420,69 @@ int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, flo
 
 int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
     if (!h || !samples) return RTIOW_E_BADARG;
+    if (h->acc_mode == ACC_MODE_ADAPTIVE) {             // the largest per-pixel count, kept on the device by adaptive_finish_kernel
+        unsigned mx = 0;
+        if (h->local_rows > 0) {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMemcpyAsync(&mx, h->adapt_ctr + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        *samples = (int)mx;
+        return 0;
+    }
     *samples = h->acc_samples;
+    return 0;
+}
+
+int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (active_pixels) *active_pixels = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive before rtiow_set_scene/rtiow_set_camera");
+    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive before rtiow_init_rng");
+    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
+    if (img_w(h) >= 65536 || h->local_rows >= 32768) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
+    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_framebuffer(h);
+    if (rc) return rc;
+    h->render_pending = false;                           // the chunk reuses the events of rtiow_render_async
+    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->stats.primary_rays = 0; h->acc_mode = ACC_MODE_ADAPTIVE; return 0; }
+    const bool timed = kernel_ms != nullptr;
+    if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
+    int active = 0;
+    if (h->precision == 32) rc = launch_adaptive<float>(h, h->cam32, samples, min_samples, rel_error, max_samples, timed, active);
+    else rc = launch_adaptive<double>(h, h->cam64, samples, min_samples, rel_error, max_samples, timed, active);
+    if (rc) return rc;
+    h->acc_mode = ACC_MODE_ADAPTIVE;
+    if (active_pixels) *active_pixels = active;
+    h->stats.prepass_ms = 0; h->stats.place_ms = 0;
+    if (timed) {
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        HIP_TRY(h, hipEventSynchronize(h->ev1));
+        float a = 0, b = 0;
+        HIP_TRY(h, hipEventElapsedTime(&a, h->ev0, h->ev_a));
+        HIP_TRY(h, hipEventElapsedTime(&b, h->ev_b, h->ev1));
+        *kernel_ms = a + b;
+        h->stats.render_ms = a + b; h->stats.main_ms = a + b;
+    }
+    return 0;
+}
+
+int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_adaptive_state before rtiow_set_camera");
+    const size_t want = (size_t)img_w(h) * (size_t)h->local_rows;
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_adaptive_state: npix must be local_rows x width");
+    if (h->acc_mode != ACC_MODE_ADAPTIVE || want == 0) {  // no adaptive chunk since the reset: n = 0, err = +inf
+        for (size_t k = 0; k < want; ++k) { if (counts) counts[k] = 0; if (rel_err) rel_err[k] = HUGE_VALF; }
+        return 0;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, h->adapt_counts, want * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (rel_err) HIP_TRY(h, hipMemcpyAsync(rel_err, h->adapt_err, want * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 

@@ -3,9 +3,9 @@
     python scripts/isa_diff_render_kernels.py --ref HEAD~1        # the tree at a git ref (exported with git archive) against the working tree
     python scripts/isa_diff_render_kernels.py BEFORE.s AFTER.s    # two `hipcc -S --cuda-device-only` listings
 
-Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel and render_solo_kernel is cut from its label
-to its .Lfunc_end and compared text for text.  This shows that a change confined to new kernels (e.g. the ACCUM flag of
-persistent_body) leaves the existing ones as they were.  Exit status 1 if any of them differ or is missing.
+Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel, render_solo_kernel and render_accumulate_kernel
+is cut from its label to its .Lfunc_end and compared text for text.  This shows that a change confined to new kernels (e.g. the ACCUM
+or ADAPT flag of persistent_body) leaves the existing ones as they were.  A kernel the older build lacks is listed as new.  Exit status 1 if any of them differ or is missing.
 """
 import argparse
 import os
@@ -17,7 +17,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<")
+EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<", "render_accumulate_kernel<")
 
 
 def listing(src_root, out):
