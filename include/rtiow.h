@@ -242,6 +242,42 @@ int rtiow_accumulated_samples(rtiow_handle h, int* samples);
 int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels);
 int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix);
 
+/* ---- Denoised previews of progressive rendering.  Every value below is computed in T, left to right as
+ * written, with plain * + - / and a correctly rounded sqrt (no fused multiply-add), so a restatement in numpy gives the same bits.
+ *
+ * rtiow_read_linear copies the linear (pre-gamma) mean colour of the current accumulation, local_rows x width x 3 T:
+ * c_p = n_p > 0 ? acc_p * ((T)1 / (T)n_p) : 0 per channel, n_p = rtiow_accumulated_samples (plain chunks) or the pixel's own count
+ * (adaptive chunks).  (c > 0 ? sqrt(c) : 0) is the preview's bits.  RTIOW_E_STATE when no chunk has run since the last reset.
+ *
+ * rtiow_render_guides computes first-hit guide buffers for the handle's camera, scene and shard.  Local pixel (i, jl), global row j,
+ * has the ray O = camera centre, D = ((pixel00 + i du) + j dv) - O (no jitter, no defocus) and (t, k) = hit_world(O, D).  On a hit:
+ * P = O + t D, outward = (P - C_k) * ((T)1 / r_k), normal = ((D.x o.x + D.y o.y) + D.z o.z) < 0 ? outward : -outward, albedo = the
+ * material's {r,g,b} (lambertian, metal) or {1,1,1} (dielectric), depth = t; on a miss all zero.  kernel_ms as in rtiow_render.
+ * rtiow_read_guides copies them as planes (npix = local_rows x width; normal and albedo npix x 3 T, depth npix T; each may be NULL).
+ * The guides go stale on rtiow_set_scene, rtiow_set_camera and rtiow_set_shard: rtiow_read_guides then returns RTIOW_E_STATE.
+ *
+ * rtiow_denoise filters the linear colour c of the current accumulation with `levels` levels of an edge-avoiding a-trous filter
+ * (Dammertz et al. 2010) into a buffer of its own: level k (step s = 1 << k) gives every pixel p, over the taps q = p + (dx s, dy s),
+ * dy then dx in -2..2, those outside the frame skipped: kern = K[dx+2] K[dy+2], K = {1/16, 1/4, 3/8, 1/4, 1/16};
+ * e = ((ec ic_k + en i_n) + ea i_a) + ez i_z with ec = (d.x d.x + d.y d.y) + d.z d.z of colour q - p, en and ea likewise of normal and
+ * albedo, ez = dz dz of depth; w = kern / (1 + e); out_p = (sum w c_q) / (sum w) per channel, sums in tap order from 0.
+ * ic_k = (T)((1 / (sigma_color^2)) 4^k), i_n = (T)(1 / sigma_normal^2), i_a and i_z likewise (computed in double); sigma = +inf turns
+ * its term off.  The output is the last level gamma-encoded like the preview (x > 0 ? sqrt(x) : 0).  Stale guides are rendered first,
+ * inside kernel_ms (NULL: asynchronous).  RTIOW_E_BADARG: levels outside 1..8, a sigma <= 0 or NaN.  RTIOW_E_STATE: no chunk since the
+ * last reset, or a sharded handle (nranks > 1: its strips are not image neighbours).  The framebuffer, the accumulation and the next
+ * chunk's bits are untouched.  rtiow_read_denoised copies the output (local_rows x width x 3 T); rtiow_denoised_device_ptr gives its
+ * device address (valid until a later rtiow_denoise on a larger frame).  Both return RTIOW_E_STATE before an rtiow_denoise or after
+ * rtiow_set_scene / _camera / _shard.  All these buffers are allocated at first use.  Not available on groups. */
+/* Linear (pre-gamma) mean colour of the current accumulation, local_rows x width x 3 T. */
+int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes);
+/* First-hit guide buffers for the handle's camera, scene and shard. */
+int rtiow_render_guides(rtiow_handle h, float* kernel_ms);
+int rtiow_read_guides(rtiow_handle h, void* normal /* npix*3 T */, void* albedo /* npix*3 T */, void* depth /* npix T */, size_t npix);
+/* Edge-avoiding a-trous filter of the current accumulation into a buffer of its own. */
+int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms);
+int rtiow_read_denoised(rtiow_handle h, void* host_rgb, size_t bytes);
+int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

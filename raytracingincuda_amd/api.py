@@ -91,6 +91,7 @@ HIP_SYMBOLS = [
     "rtiow_read_framebuffer", "rtiow_read_levels", "rtiow_set_scene_source", "rtiow_set_schedule", "rtiow_get_stats", "rtiow_synchronize",
     "rtiow_render_async", "rtiow_render_wait", "rtiow_stream", "rtiow_device",
     "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples", "rtiow_accumulate_adaptive", "rtiow_read_adaptive_state",
+    "rtiow_read_linear", "rtiow_render_guides", "rtiow_read_guides", "rtiow_denoise", "rtiow_read_denoised", "rtiow_denoised_device_ptr",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -192,6 +193,12 @@ def load_hip_library(debug=False):
         lib.rtiow_accumulate_adaptive.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
         lib.rtiow_read_adaptive_state.argtypes = [H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
+        lib.rtiow_read_linear.argtypes = [H, vp, ctypes.c_size_t]
+        lib.rtiow_render_guides.argtypes = [H, ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_read_guides.argtypes = [H, vp, vp, vp, ctypes.c_size_t]
+        lib.rtiow_denoise.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_read_denoised.argtypes = [H, vp, ctypes.c_size_t]
+        lib.rtiow_denoised_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -359,6 +366,15 @@ def place_rows(full_rgb, local_rgb, rank, nranks, strip_rows):
     return full_rgb
 
 
+# Renderer.denoise defaults: the best of scripts/denoise_probe.py --sweep, i.e. the smallest worse-of-two MSE ratio on scenes 1 and 3
+# at 320 x 180 and 16 samples against 1024 (profiles/denoise/denoise_probe.json).
+DENOISE_LEVELS = 5
+DENOISE_SIGMA_COLOR = 0.1
+DENOISE_SIGMA_NORMAL = 0.1
+DENOISE_SIGMA_ALBEDO = 0.2
+DENOISE_SIGMA_DEPTH = 0.05
+
+
 class Renderer:
     """One GPU's render state behind the C-ABI handle (include/rtiow.h)."""
 
@@ -518,6 +534,61 @@ class Renderer:
         self._check(self._lib.rtiow_read_adaptive_state(self._h, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                                         err.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows * w))
         return counts, err
+
+    def read_linear(self):
+        """The linear (pre-gamma) mean colour of the accumulation, [local_rows, W, 3]: acc * ((T)1 / (T)n) per pixel, n its count."""
+        out = np.empty((self.local_rows, self.width, 3), self.dtype)
+        self._check(self._lib.rtiow_read_linear(self._h, out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def render_guides(self, sync=True):
+        """First-hit guide buffers for the current camera, scene and shard; returns the kernel ms (None when sync=False)."""
+        if sync:
+            ms = ctypes.c_float(0)
+            self._check(self._lib.rtiow_render_guides(self._h, ctypes.byref(ms)))
+            return ms.value
+        self._check(self._lib.rtiow_render_guides(self._h, None))
+        return None
+
+    def guides(self):
+        """(normal [rows, W, 3], albedo [rows, W, 3], depth [rows, W]) of the first hit of each pixel's centre ray (zeros on a miss);
+        renders them first when they are stale (after set_scene, set_camera or set_shard)."""
+        rows, w = self.local_rows, self.width
+        normal = np.empty((rows, w, 3), self.dtype)
+        albedo = np.empty((rows, w, 3), self.dtype)
+        depth = np.empty((rows, w), self.dtype)
+        rc = self._lib.rtiow_read_guides(self._h, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, rows * w)
+        if rc == -2:                                     # RTIOW_E_STATE: stale or never rendered
+            self.render_guides()
+            rc = self._lib.rtiow_read_guides(self._h, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, rows * w)
+        self._check(rc)
+        return normal, albedo, depth
+
+    def denoise(self, levels=DENOISE_LEVELS, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, sync=True):
+        """Edge-avoiding a-trous filter of the accumulation: returns the gamma-encoded denoised image
+        [rows, W, 3] (sync=True), or None after enqueueing the work (sync=False; read_denoised() / denoised_device_ptr() later).
+        The framebuffer and the accumulation are untouched.  sigma = float("inf") turns a term off."""
+        if not sync:
+            self._check(self._lib.rtiow_denoise(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
+                                                float(sigma_depth), None))
+            return None
+        ms = ctypes.c_float(0)
+        self._check(self._lib.rtiow_denoise(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
+                                            float(sigma_depth), ctypes.byref(ms)))
+        return self.read_denoised()
+
+    def read_denoised(self):
+        out = np.empty((self.local_rows, self.width, 3), self.dtype)
+        self._check(self._lib.rtiow_read_denoised(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def denoised_device_ptr(self):
+        """(device address, bytes) of the last denoise() output."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.rtiow_denoised_device_ptr(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
 
     def count_segments(self, threads=8):
         """Untimed render that also counts path segments (hit_world calls)."""

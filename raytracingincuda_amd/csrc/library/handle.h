@@ -68,6 +68,16 @@ struct rtiow_handle_s {
     int32_t* adapt_counts = nullptr; size_t adapt_counts_bytes = 0;
     float* adapt_err = nullptr; size_t adapt_err_bytes = 0;
     unsigned* adapt_ctr = nullptr; size_t adapt_ctr_bytes = 0;
+    // denoised previews (rtiow_render_guides / rtiow_read_linear / rtiow_denoise), all allocated at first use: the guides ({normal, depth}
+    // and {albedo, 0}, 4 T per pixel each; guides_ok: they belong to the current scene, camera and shard), the linear image, the filter's
+    // two ping-pong colour buffers and its gamma-encoded output (denoised_ok: rtiow_denoise has filled it since the last set_*)
+    void* guide_nd = nullptr; size_t guide_nd_bytes = 0;
+    void* guide_alb = nullptr; size_t guide_alb_bytes = 0;
+    bool guides_ok = false;
+    void* linear = nullptr; size_t linear_bytes = 0;
+    void* dn_tmp[2] = {nullptr, nullptr}; size_t dn_tmp_bytes[2] = {0, 0};
+    void* denoised = nullptr; size_t denoised_bytes = 0;
+    bool denoised_ok = false;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

@@ -1,10 +1,11 @@
-// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering; launch_adaptive: one adaptive chunk
+// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering; launch_adaptive: one adaptive chunk; launch_guides / launch_linear / launch_denoise: the denoised previews
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
 #include "../device/render_kernels.h"
 #include "../device/adaptive.h"
 #include "../device/cost_sort.h"
+#include "../device/denoise.h"
 
 namespace {
 
@@ -558,6 +559,81 @@ int launch_adaptive(rtiow_handle_s* h, const CAM& cam, int samples, int min_samp
     h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
     h->stats.staged_stores = 0;
     h->stats.primary_rays = (uint64_t)n_active * (uint64_t)samples;
+    return 0;
+}
+
+// First-hit guides of every local pixel (rtiow_render_guides) into h->guide_nd / h->guide_alb: guide_kernel with the scene staged as
+// the render launches stage it (layout_lds of a non-persistent launch: no drain scratch), one 8x8 tile per wave, four waves a workgroup.
+template <class T, class CAM>
+int launch_guides(rtiow_handle_s* h, const CAM& cam) {
+    RenderParams<T> p = make_params<T>(h, cam);
+    const int threads = 256;
+    size_t lds = 0;
+    bool lds_source = false;
+    int effective_source = h->scene_source;
+    int rc = layout_lds<T>(h, p, threads, false, false, lds, lds_source, effective_source);
+    if (rc) return rc;
+    const size_t npix = (size_t)p.cold.W * h->local_rows;
+    if ((rc = ensure_buffer(h, &h->guide_nd, &h->guide_nd_bytes, npix * 4 * sizeof(T)))) return rc;
+    if ((rc = ensure_buffer(h, &h->guide_alb, &h->guide_alb_bytes, npix * 4 * sizeof(T)))) return rc;
+    const void* k = lds_source ? (const void*)guide_kernel<T, RTIOW_SCENE_LDS> : (const void*)guide_kernel<T, RTIOW_SCENE_SCALAR>;
+    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int tiles = ((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
+    const dim3 grid((unsigned)((tiles + 3) / 4));
+    if (lds_source) hipLaunchKernelGGL((guide_kernel<T, RTIOW_SCENE_LDS>), grid, dim3(threads), lds, h->stream, p, (T*)h->guide_nd, (T*)h->guide_alb);
+    else hipLaunchKernelGGL((guide_kernel<T, RTIOW_SCENE_SCALAR>), grid, dim3(threads), lds, h->stream, p, (T*)h->guide_nd, (T*)h->guide_alb);
+    HIP_TRY(h, hipGetLastError());
+    h->guides_ok = true;
+    return 0;
+}
+
+// The accumulation's current records and counts: plain mode one count for all (counts = nullptr), adaptive mode the per-pixel array.
+inline void accumulation_source(const rtiow_handle_s* h, const unsigned char*& mid, const int32_t*& counts, int& n_uniform) {
+    mid = h->acc_mid[h->acc_cur];
+    counts = h->acc_mode == ACC_MODE_ADAPTIVE ? h->adapt_counts : nullptr;
+    n_uniform = h->acc_mode == ACC_MODE_ADAPTIVE ? 0 : h->acc_samples;
+}
+
+// The linear image of the accumulation into h->linear (rtiow_read_linear).  The caller has checked that a chunk has run.
+template <class T>
+int launch_linear(rtiow_handle_s* h) {
+    const size_t npix = (size_t)img_w(h) * h->local_rows;
+    int rc = ensure_buffer(h, &h->linear, &h->linear_bytes, npix * 3 * sizeof(T));
+    if (rc) return rc;
+    const unsigned char* mid; const int32_t* counts; int n_uniform;
+    accumulation_source(h, mid, counts, n_uniform);
+    hipLaunchKernelGGL(linear_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, npix, mid, counts, n_uniform, (T*)h->linear);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// `levels` launches of denoise_level_kernel over the accumulation (rtiow_denoise): level 0 reads the records, the levels ping-pong through
+// h->dn_tmp[0/1], the last writes the gamma-encoded image to h->denoised.  inv2[4] = 1 / sigma^2 of colour, normal, albedo, depth (double);
+// the colour term of level k is scaled by 4^k and every weight is rounded to T here.  The caller has checked state and arguments and
+// made the guides current.
+template <class T>
+int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    int rc = ensure_buffer(h, &h->denoised, &h->denoised_bytes, npix * 3 * sizeof(T));
+    if (rc) return rc;
+    for (int b = 0; b < 2 && b < levels - 1; ++b)
+        if ((rc = ensure_buffer(h, &h->dn_tmp[b], &h->dn_tmp_bytes[b], npix * 3 * sizeof(T)))) return rc;
+    const unsigned char* mid; const int32_t* counts; int n_uniform;
+    accumulation_source(h, mid, counts, n_uniform);
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    for (int k = 0; k < levels; ++k) {
+        FilterWeights<T> fw;
+        fw.ic = (T)(inv2[0] * std::ldexp(1.0, 2 * k));
+        fw.in = (T)inv2[1]; fw.ia = (T)inv2[2]; fw.iz = (T)inv2[3];
+        const bool last = k == levels - 1;
+        const T* cin = k == 0 ? nullptr : (const T*)h->dn_tmp[(k - 1) & 1];
+        T* cout = last ? (T*)h->denoised : (T*)h->dn_tmp[k & 1];
+        hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
+                           counts, n_uniform, cin, (const T*)h->guide_nd, (const T*)h->guide_alb, cout, last ? 1 : 0);
+        HIP_TRY(h, hipGetLastError());
+    }
+    h->denoised_ok = true;
     return 0;
 }
 

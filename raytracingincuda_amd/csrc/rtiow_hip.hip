@@ -61,6 +61,7 @@
 #include "device/pixel_io.h"
 #include "device/render_kernels.h"
 #include "device/cost_sort.h"
+#include "device/denoise.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -181,6 +182,7 @@ int rtiow_destroy(rtiow_handle h) {
     void* bufs[] = {h->geom_a, h->shade_tbl, h->geom_s, h->grid_blob, h->cost_rank, h->rng, h->jump, h->work_counter, h->mid, h->slot_of, h->staged,
                     h->cost, h->order, h->sort_scratch, h->levels, h->rng_low_table, h->acc_mid[0], h->acc_mid[1], h->acc_cost,
                     h->adapt_counts, h->adapt_err, h->adapt_ctr,
+                    h->guide_nd, h->guide_alb, h->linear, h->dn_tmp[0], h->dn_tmp[1], h->denoised,
                     h->fb_external ? nullptr : h->fb};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->clock_stamps) (void)hipHostFree(h->clock_stamps);
@@ -211,6 +213,7 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
     h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
+    h->guides_ok = false; h->denoised_ok = false;
     if (h->precision == 32) return upload_scene<float>(h, n, (const float*)center_radius, (const float*)albedo_fuzz, (const float*)refraction_index, type, valid);
     return upload_scene<double>(h, n, (const double*)center_radius, (const double*)albedo_fuzz, (const double*)refraction_index, type, valid);
 }
@@ -226,6 +229,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->stats.local_rows = h->local_rows;
     h->rng_ready = false;
     h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
+    h->guides_ok = false; h->denoised_ok = false;
     return 0;
 }
 
@@ -234,6 +238,7 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
     h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
     h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
+    h->guides_ok = false; h->denoised_ok = false;
     if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
     h->rng_ready = false;
     return 0;
@@ -483,6 +488,113 @@ int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, s
     if (counts) HIP_TRY(h, hipMemcpyAsync(counts, h->adapt_counts, want * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (rel_err) HIP_TRY(h, hipMemcpyAsync(rel_err, h->adapt_err, want * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- Denoised previews
+namespace {
+// kernel_ms: events around the work enqueued between timed_begin and timed_end (NULL: asynchronous, nothing recorded).
+int timed_begin(rtiow_handle_s* h, float* kernel_ms) {
+    h->render_pending = false;                           // the call reuses the start / stop events of rtiow_render_async
+    if (kernel_ms) { *kernel_ms = 0; HIP_TRY(h, hipEventRecord(h->ev0, h->stream)); }
+    return 0;
+}
+int timed_end(rtiow_handle_s* h, float* kernel_ms) {
+    if (!kernel_ms) return 0;
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipEventSynchronize(h->ev1));
+    HIP_TRY(h, hipEventElapsedTime(kernel_ms, h->ev0, h->ev1));
+    return 0;
+}
+int render_guides(rtiow_handle_s* h) {
+    return h->precision == 32 ? launch_guides<float>(h, h->cam32) : launch_guides<double>(h, h->cam64);
+}
+// D2H copy of `bytes` from a device buffer on the handle's stream, then wait.
+int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
+    if (!bytes) return 0;
+    HIP_TRY(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+}  // namespace
+
+int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->have_camera || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_linear: no chunk since the last reset");
+    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    if (bytes != need || (need && !host_rgb)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_linear: bytes must be local_rows x width x 3 x sizeof(T)");
+    if (need == 0) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = h->precision == 32 ? launch_linear<float>(h) : launch_linear<double>(h);
+    if (rc) return rc;
+    return copy_out(h, host_rgb, h->linear, need);
+}
+
+int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render_guides before rtiow_set_scene/rtiow_set_camera");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->local_rows == 0) { h->guides_ok = true; return 0; }
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if ((rc = render_guides(h))) return rc;
+    return timed_end(h, kernel_ms);
+}
+
+int rtiow_read_guides(rtiow_handle h, void* normal, void* albedo, void* depth, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->have_camera || !h->guides_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_guides: no guides for the current scene, camera and shard (rtiow_render_guides)");
+    const size_t want = (size_t)img_w(h) * (size_t)h->local_rows;
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_guides: npix must be local_rows x width");
+    if (want == 0 || (!normal && !albedo && !depth)) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h);
+    std::vector<unsigned char> nd(normal || depth ? want * 4 * es : 0), alb(albedo ? want * 4 * es : 0);
+    if (normal || depth) HIP_TRY(h, hipMemcpyAsync(nd.data(), h->guide_nd, nd.size(), hipMemcpyDeviceToHost, h->stream));
+    if (albedo) HIP_TRY(h, hipMemcpyAsync(alb.data(), h->guide_alb, alb.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < want; ++k) {                  // {n.xyz, depth} and {albedo.rgb, 0} -> planes
+        if (normal) std::memcpy((unsigned char*)normal + 3 * k * es, nd.data() + 4 * k * es, 3 * es);
+        if (depth) std::memcpy((unsigned char*)depth + k * es, nd.data() + (4 * k + 3) * es, es);
+        if (albedo) std::memcpy((unsigned char*)albedo + 3 * k * es, alb.data() + 4 * k * es, 3 * es);
+    }
+    return 0;
+}
+
+int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
+    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise: levels must be 1..8");
+    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise: every sigma must be > 0 (+inf turns its term off)");
+    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise: no chunk since the last reset");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise: not on a sharded handle (the strips of a shard are not image neighbours)");
+    double inv2[4];
+    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    rc = h->precision == 32 ? launch_denoise<float>(h, levels, inv2) : launch_denoise<double>(h, levels, inv2);
+    if (rc) return rc;
+    return timed_end(h, kernel_ms);
+}
+
+int rtiow_read_denoised(rtiow_handle h, void* host_rgb, size_t bytes) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_denoised before rtiow_denoise");
+    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    if (bytes != need || !host_rgb) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_denoised: bytes must be local_rows x width x 3 x sizeof(T)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return copy_out(h, host_rgb, h->denoised, need);
+}
+
+int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
+    if (!h || !device_ptr || !bytes) return RTIOW_E_BADARG;
+    if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoised_device_ptr before rtiow_denoise");
+    *device_ptr = h->denoised;
+    *bytes = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
     return 0;
 }
 

@@ -3,7 +3,8 @@
     python scripts/isa_diff_render_kernels.py --ref HEAD~1        # the tree at a git ref (exported with git archive) against the working tree
     python scripts/isa_diff_render_kernels.py BEFORE.s AFTER.s    # two `hipcc -S --cuda-device-only` listings
 
-Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel, render_solo_kernel and render_accumulate_kernel
+Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel, render_solo_kernel, render_accumulate_kernel,
+render_adaptive_kernel, adaptive_select_kernel and adaptive_finish_kernel
 is cut from its label to its .Lfunc_end and compared text for text.  This shows that a change confined to new kernels (e.g. the ACCUM
 or ADAPT flag of persistent_body) leaves the existing ones as they were.  A kernel the older build lacks is listed as new.  Exit status 1 if any of them differ or is missing.
 """
@@ -17,7 +18,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<", "render_accumulate_kernel<")
+EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<", "render_accumulate_kernel<",
+            "render_adaptive_kernel<", "adaptive_select_kernel<", "adaptive_finish_kernel<")
 
 
 def listing(src_root, out):
