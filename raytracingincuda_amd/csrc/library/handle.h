@@ -1,7 +1,37 @@
-// handle.h -- rtiow_handle_s and the small helpers every host file uses (error text, scratch, shard rows, operand-range checks, make_params)
+// handle.h -- rtiow_handle_s, the device buffers it owns (DeviceBuffer) and the small helpers every host file uses (error text, frame size,
+// shard rows, operand-range checks, make_params)
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "../device/params.h"
+
+// A device allocation owned by the handle or by one call: freed when it goes out of scope.  ensure() grows it to at least `bytes`
+// and never shrinks it; the old allocation is freed before the new one is made, so its contents are lost.
+template <class E = unsigned char>
+class DeviceBuffer {
+  public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : ptr_(o.ptr_), bytes_(o.bytes_) { o.ptr_ = nullptr; o.bytes_ = 0; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { std::swap(ptr_, o.ptr_); std::swap(bytes_, o.bytes_); return *this; }
+    ~DeviceBuffer() { (void)reset(); }
+    hipError_t ensure(size_t bytes) {
+        if (ptr_ && bytes_ >= bytes) return hipSuccess;
+        if (hipError_t e = reset()) return e;
+        if (hipError_t e = hipMalloc((void**)&ptr_, bytes)) return e;
+        bytes_ = bytes;
+        return hipSuccess;
+    }
+    hipError_t reset() {
+        if (!ptr_) return hipSuccess;
+        const hipError_t e = hipFree(ptr_);
+        ptr_ = nullptr; bytes_ = 0;
+        return e;
+    }
+    operator E*() const { return ptr_; }
+    template <class U> U* as() const { return (U*)ptr_; }       // buffers whose element type is the handle's precision
+  private:
+    E* ptr_ = nullptr;
+    size_t bytes_ = 0;
+};
 
 enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive
 
@@ -17,13 +47,13 @@ struct rtiow_handle_s {
 
     // scene
     int n = 0, n_padded = 0;
-    void *geom_a = nullptr, *shade_tbl = nullptr;
-    void* geom_s = nullptr;                       // screening table (built lazily at the first render of a scene)
+    DeviceBuffer<> geom_a, shade_tbl;
+    DeviceBuffer<float> geom_s;                   // screening table (built lazily at the first render of a scene)
     std::vector<double> host_cr;                  // compact {cx,cy,cz,r} kept for building it
     bool screen_dirty = true;
     double ctr[3] = {0, 0, 0}, omax2 = 0;
     // uniform grid over the small spheres (RTIOW_SCENE_GRID; built with the screening table)
-    void* grid_blob = nullptr;
+    DeviceBuffer<> grid_blob;
     GridParams grid{};                            // offsets are relative to the blob until launch_render places it in LDS
     int grid_cells_bytes = 0, grid_aos_bytes = 0, grid_direct_bytes = 0, grid_ids_bytes = 0;
     int grid_direct = 0, grid_registered = 0;
@@ -35,61 +65,58 @@ struct rtiow_handle_s {
     int rank = 0, nranks = 1, strip_rows = 8;
     int local_rows = 0;
     // rng
-    uint32_t* rng = nullptr;
-    size_t rng_pixels = 0;
+    DeviceBuffer<uint32_t> rng;
     bool rng_ready = false;
-    uint32_t* rng_low_table = nullptr;            // J^lo * s0 for lo < 2^XW_LOW_BITS (xw_low_table_kernel), per rtiow_init_rng
-    uint32_t* jump = nullptr;
+    DeviceBuffer<uint32_t> rng_low_table;         // J^lo * s0 for lo < 2^XW_LOW_BITS (xw_low_table_kernel), per rtiow_init_rng
+    DeviceBuffer<uint32_t> jump;
     int jump_count = 0;                           // matrices of `jump` that are filled: enough for the bits of the largest pixel index so far
-    // framebuffer
+    // framebuffer: allocated here (freed by rtiow_destroy) or the caller's (fb_external: rtiow_bind_framebuffer, never freed here)
     void* fb = nullptr;
     size_t fb_bytes = 0;
     bool fb_external = false;
     // knobs / stats
     int scene_source = RTIOW_SCENE_GRID;
     int schedule = RTIOW_SCHED_SORTED;
-    unsigned char* mid = nullptr; size_t mid_bytes = 0;          // SCHED_SORTED: MidState records parked between the launches
-    uint32_t* cost = nullptr; size_t cost_bytes = 0;
-    unsigned char* levels = nullptr; size_t levels_bytes = 0;     // rtiow_read_levels: one byte per channel + an 8-byte NaN counter behind them
-    uint32_t* cost_rank = nullptr; size_t cost_rank_bytes = 0;    // the smoothed cost the sort ranks by
-    int* order = nullptr; size_t order_bytes = 0;
-    int* slot_of = nullptr; size_t slot_of_bytes = 0;            // SCHED_SORTED: pixel -> slot (the inverse of `order`)
-    unsigned char* staged = nullptr; size_t staged_bytes = 0;             // SCHED_SORTED: finished pixels in slot order (place_pixels_kernel writes the image)
-    unsigned* sort_scratch = nullptr; size_t sort_scratch_bytes = 0;
+    DeviceBuffer<> mid;                           // SCHED_SORTED: MidState records parked between the launches
+    DeviceBuffer<uint32_t> cost;
+    DeviceBuffer<> levels;                        // rtiow_read_levels: one byte per channel + an 8-byte NaN counter behind them
+    DeviceBuffer<uint32_t> cost_rank;             // the smoothed cost the sort ranks by
+    DeviceBuffer<int> order;
+    DeviceBuffer<int> slot_of;                    // SCHED_SORTED: pixel -> slot (the inverse of `order`)
+    DeviceBuffer<> staged;                        // SCHED_SORTED: finished pixels in slot order (place_pixels_kernel writes the image)
+    DeviceBuffer<unsigned> sort_scratch;
     // progressive rendering (rtiow_accumulate): samples accumulated since the last reset, the per-pixel MidState records of the last chunk
     // (two buffers, ping-pong: acc_mid[acc_cur] holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)
     int acc_samples = 0;
     int acc_cur = 0;
-    unsigned char* acc_mid[2] = {nullptr, nullptr}; size_t acc_mid_bytes[2] = {0, 0};
-    uint32_t* acc_cost = nullptr; size_t acc_cost_bytes = 0;
+    DeviceBuffer<> acc_mid[2];
+    DeviceBuffer<uint32_t> acc_cost;
     // adaptive progressive rendering (rtiow_accumulate_adaptive): the mode the first chunk after a reset fixed (ACC_MODE_*), the
     // per-pixel count and relative error the last adaptive chunk left, and {active pixels, largest count} of that chunk
     int acc_mode = 0;
-    int32_t* adapt_counts = nullptr; size_t adapt_counts_bytes = 0;
-    float* adapt_err = nullptr; size_t adapt_err_bytes = 0;
-    unsigned* adapt_ctr = nullptr; size_t adapt_ctr_bytes = 0;
+    DeviceBuffer<int32_t> adapt_counts;
+    DeviceBuffer<float> adapt_err;
+    DeviceBuffer<unsigned> adapt_ctr;
     // denoised previews (rtiow_render_guides / rtiow_read_linear / rtiow_denoise), all allocated at first use: the guides ({normal, depth}
     // and {albedo, 0}, 4 T per pixel each; guides_ok: they belong to the current scene, camera and shard), the linear image, the filter's
     // two ping-pong colour buffers and its gamma-encoded output (denoised_ok: rtiow_denoise has filled it since the last set_*)
-    void* guide_nd = nullptr; size_t guide_nd_bytes = 0;
-    void* guide_alb = nullptr; size_t guide_alb_bytes = 0;
+    DeviceBuffer<> guide_nd, guide_alb;
     bool guides_ok = false;
-    void* linear = nullptr; size_t linear_bytes = 0;
-    void* dn_tmp[2] = {nullptr, nullptr}; size_t dn_tmp_bytes[2] = {0, 0};
-    void* denoised = nullptr; size_t denoised_bytes = 0;
+    DeviceBuffer<> linear;
+    DeviceBuffer<> dn_tmp[2];
+    DeviceBuffer<> denoised;
     bool denoised_ok = false;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;
     size_t timeline_cap_waves = 0;            // waves the debug timeline buffer holds
-    unsigned int* work_counter = nullptr;
+    DeviceBuffer<unsigned int> work_counter;      // the persistent hand-out's two slot counters (persistent_setup)
     int warmup_us = 0;                               // RTIOW_CLOCK_WARMUP_US: busy kernel in front of the handle's FIRST timed render (before its start event), see clock_warmup_kernel
     bool warmed = false;
     unsigned long long* clock_stamps = nullptr;      // pinned + mapped host memory, 8 words: {memtime, realtime} x {start, end} of the prepass [0..3] and the main launch [4..7]
     unsigned long long* clock_stamps_dev = nullptr;  // its device address
     unsigned long long* timeline = nullptr;   // debug: set only during rtiow_debug_timeline
     uint32_t* pixel_times = nullptr;          // debug: set only during rtiow_debug_pixel_times
-    int probe_n = 0; const void* probe_rays = nullptr; void* probe_t = nullptr; int* probe_idx = nullptr;   // debug: set only during rtiow_debug_hit_world
     rtiow_stats stats{};
 };
 
@@ -108,16 +135,6 @@ int fail_arg(rtiow_handle_s* h, int code, const char* msg) { if (h) h->err = msg
 
 #define HIP_TRY(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail((h), e_, __FILE__, __LINE__); } while (0)
 
-// Device memory of one call: released on every return path (HIP_TRY returns early).
-struct DeviceScratch {
-    void* ptr = nullptr;
-    hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes); }
-    ~DeviceScratch() { if (ptr) (void)hipFree(ptr); }
-    DeviceScratch() = default;
-    DeviceScratch(const DeviceScratch&) = delete;
-    DeviceScratch& operator=(const DeviceScratch&) = delete;
-};
-
 int compute_local_rows(int H, int rank, int nranks, int strip_rows) {
     int rows = 0;
     const int nstrips = (H + strip_rows - 1) / strip_rows;
@@ -130,9 +147,20 @@ int compute_local_rows(int H, int rank, int nranks, int strip_rows) {
 
 int img_w(const rtiow_handle_s* h) { return h->precision == 64 ? h->cam64.img_width : h->cam32.img_width; }
 int img_h(const rtiow_handle_s* h) { return h->precision == 64 ? h->cam64.img_height : h->cam32.img_height; }
+// The camera in precision T, and f(T()) for the handle's precision: the one place a call picks float or double.
+template <class T>
+const auto& camera(const rtiow_handle_s* h) {
+    if constexpr (sizeof(T) == 4) return h->cam32;
+    else return h->cam64;
+}
+template <class F>
+auto by_precision(const rtiow_handle_s* h, F f) { return h->precision == 32 ? f(float()) : f(double()); }
+
+size_t local_pixels(const rtiow_handle_s* h) { return (size_t)img_w(h) * h->local_rows; }
+size_t image_bytes(const rtiow_handle_s* h) { return local_pixels(h) * 3 * elem_size(h); }          // the local image, 3 T per pixel
 
 int ensure_framebuffer(rtiow_handle_s* h) {
-    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    const size_t need = image_bytes(h);
     if (h->fb_external) {
         if (h->fb_bytes < need) return fail_arg(h, RTIOW_E_BADARG, "bound framebuffer too small");
         return 0;
@@ -181,9 +209,12 @@ int scene_in_range(const rtiow_handle_s* h, const CAM& c) {
     return !h->host_cr.empty() && std::isfinite(reach) && reach < 0x1p18;
 }
 
-template <class T, class CAM>
-RenderParams<T> make_params(const rtiow_handle_s* h, const CAM& c) {
-    RenderParams<T> p;
+// The parameters of a single-phase launch of the whole local frame in tile order, every field defined: samples [0, S) from the states of
+// rtiow_init_rng, no hand-out order, no solo waves, no staging.  Each launch sets what it changes.
+template <class T>
+RenderParams<T> make_params(const rtiow_handle_s* h) {
+    const auto& c = camera<T>(h);
+    RenderParams<T> p{};
     p.range_flags = primary_rays_in_range(c) | (scene_in_range(h, c) << 1);
     p.cold.W = c.img_width; p.cold.H = c.img_height; p.cold.S = c.samples_per_pixel; p.B = c.max_depth;
     p.cold.pixel_samples_scale = c.pixel_samples_scale;
@@ -195,9 +226,10 @@ RenderParams<T> make_params(const rtiow_handle_s* h, const CAM& c) {
     p.cam.ddu = {c.defocus_disk_u[0], c.defocus_disk_u[1], c.defocus_disk_u[2]};
     p.cam.ddv = {c.defocus_disk_v[0], c.defocus_disk_v[1], c.defocus_disk_v[2]};
     p.n = h->n; p.n_padded = h->n_padded;
-    p.geom_a = (const T*)h->geom_a; p.screen.shade_tbl = (const T*)h->shade_tbl;
+    p.geom_a = h->geom_a.as<const T>(); p.screen.shade_tbl = h->shade_tbl.as<const T>();
     p.cold.rng = h->rng; p.cold.fb = (T*)h->fb;
     p.cold.local_rows = h->local_rows; p.cold.rank = h->rank; p.cold.nranks = h->nranks; p.cold.strip_rows = h->strip_rows;
+    p.cold.s_begin = 0; p.s_end = p.cold.S; p.cold.rng_in = h->rng; p.cold.solo_lanes = 1;
     return p;
 }
 

@@ -1,4 +1,6 @@
-// launch.h -- launch_render: LDS layout, schedule (static / persistent / sorted with prepass + cost sort + solo waves), kernel launches; launch_accumulate: one chunk of progressive rendering; launch_adaptive: one adaptive chunk; launch_guides / launch_linear / launch_denoise: the denoised previews
+// launch.h -- the render-family launches on one shared setup (layout_lds, persistent_setup, size_persistent, record_launch): launch_render
+// (static / persistent / sorted with prepass + cost sort + solo waves), launch_accumulate (one chunk of progressive rendering),
+// launch_adaptive (one adaptive chunk); launch_guides / launch_linear / launch_denoise: the denoised previews
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -21,44 +23,47 @@ inline int tuned(const char* name, int builtin) {
 
 template <class T> using RenderFn = void (*)(const RenderParams<T>);
 
-template <class T, int SRC, bool COUNT>
-RenderFn<T> pick_sched(bool persistent) {
-    return persistent ? render_persistent_kernel<T, SRC, COUNT> : render_kernel<T, SRC, COUNT>;
-}
-template <class T>
-RenderFn<T> pick_prepass_kernel(bool lds, bool count) {
-    if (lds) return count ? (RenderFn<T>)render_prepass_kernel<T, RTIOW_SCENE_LDS, true> : (RenderFn<T>)render_prepass_kernel<T, RTIOW_SCENE_LDS, false>;
-    return count ? (RenderFn<T>)render_prepass_kernel<T, RTIOW_SCENE_SCALAR, true> : (RenderFn<T>)render_prepass_kernel<T, RTIOW_SCENE_SCALAR, false>;
-}
-// The fp32 persistent kernels with the bounded rejection loop (render_kernels.h, BOUND_F32); fp64 bounds its loop in every kernel.
-template <class T> RenderFn<T> pick_bounded_kernel(bool prepass, bool lds, bool count) { (void)prepass; (void)lds; (void)count; return nullptr; }
-template <> RenderFn<float> pick_bounded_kernel<float>(bool prepass, bool lds, bool count) {
-#define RT_PICK(K) (lds ? (count ? (RenderFn<float>)K<float, RTIOW_SCENE_LDS, true, true> : (RenderFn<float>)K<float, RTIOW_SCENE_LDS, false, true>) \
-                        : (count ? (RenderFn<float>)K<float, RTIOW_SCENE_SCALAR, true, true> : (RenderFn<float>)K<float, RTIOW_SCENE_SCALAR, false, true>))
-    return prepass ? RT_PICK(render_prepass_kernel) : RT_PICK(render_persistent_kernel);
-#undef RT_PICK
+// f(std::integral_constant<int, SRC>()) for the kernels' scene-source template argument: RTIOW_SCENE_LDS when the launch stages the
+// scene in LDS (layout_lds), RTIOW_SCENE_SCALAR otherwise.
+template <class F>
+auto by_source(bool lds_source, F f) {
+    if (lds_source) return f(std::integral_constant<int, RTIOW_SCENE_LDS>());
+    return f(std::integral_constant<int, RTIOW_SCENE_SCALAR>());
 }
 
-template <class T>
-RenderFn<T> pick_kernel(bool persistent, bool lds, bool count) {
-    if (lds) return count ? pick_sched<T, RTIOW_SCENE_LDS, true>(persistent) : pick_sched<T, RTIOW_SCENE_LDS, false>(persistent);
-    return count ? pick_sched<T, RTIOW_SCENE_SCALAR, true>(persistent) : pick_sched<T, RTIOW_SCENE_SCALAR, false>(persistent);
+// A kernel launched with more than 64 KB of dynamic LDS must be allowed it first (also before occupancy queries).
+template <class K>
+hipError_t allow_lds(K k, size_t lds) {
+    return lds > 64 * 1024 ? hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
 }
 
-// (Re)allocates a device buffer kept in the handle when it is too small.
-template <class P>
-int ensure_buffer(rtiow_handle_s* h, P** ptr, size_t* have, size_t need) {
-    if (*ptr && *have >= need) return 0;
-    if (*ptr) { HIP_TRY(h, hipFree(*ptr)); *ptr = nullptr; *have = 0; }
-    HIP_TRY(h, hipMalloc((void**)ptr, need));
-    *have = need;
-    return 0;
-}
+// Hand-out orders store a pixel as row << 16 | column.
+inline bool order_fits(const rtiow_handle_s* h) { return img_w(h) < 65536 && h->local_rows < 32768; }
+// The cost-sorted hand-out: the schedule asks for it, the frame is large enough to repay the ranking, and its order fits.
+inline bool sorted_handout(const rtiow_handle_s* h) { return h->schedule == RTIOW_SCHED_SORTED && local_pixels(h) >= 4096 && order_fits(h); }
+
+// A render-family launch: parameters and LDS layout (layout_lds), kernel and sizing (persistent_setup, size_persistent).
+template <class T>
+struct Launch {
+    RenderParams<T> p;
+    size_t lds = 0;                    // dynamic LDS bytes per workgroup
+    bool lds_source = false;           // the kernel reads the scene from LDS
+    int effective_source = 0;          // rtiow_stats::scene_source
+    RenderFn<T> k = nullptr;
+    RenderFn<T> kb = nullptr;          // fp32: k with the bounded rejection loop (render_kernels.h, BOUND_F32); fp64 bounds it in every kernel
+    hipFuncAttributes fa{};            // k's
+    long long blocks = 0;              // workgroups launched
+    bool bounded_f32 = false;          // k is kb
+};
 
 // LDS layout of a render launch (scene source, screening table and grid -- built at the first launch after rtiow_set_scene --, shade
-// records, drain scratch) into p; lds = dynamic LDS bytes per workgroup.  record_stats: the grid_* fields of rtiow_stats describe it.
+// records, drain scratch) into L.p, L.lds, L.lds_source and L.effective_source.  record_stats: the grid_* fields of rtiow_stats describe it.
 template <class T>
-int layout_lds(rtiow_handle_s* h, RenderParams<T>& p, int threads, bool persistent, bool record_stats, size_t& lds, bool& lds_source, int& effective_source) {
+int layout_lds(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bool record_stats) {
+    RenderParams<T>& p = L.p;
+    size_t& lds = L.lds;
+    bool& lds_source = L.lds_source;
+    int& effective_source = L.effective_source;
     // A scene whose tables do not fit the CU's LDS next to the drain scratch (several thousand
     // spheres) is read through the scalar cache instead of failing: same image, exact loop.
     size_t coop_scratch = persistent ? (size_t)((threads + 63) / 64) * COOP_SLOTS * sizeof(CoopSlot<T>) : 0;
@@ -109,14 +114,28 @@ int layout_lds(rtiow_handle_s* h, RenderParams<T>& p, int threads, bool persiste
     return 0;
 }
 
-// Size a persistent launch of k: the lanes of a wave that take pixels (lane_cap), the workgroups to
-// launch (blocks) and -- fp32, kb = the same kernel with the bounded rejection loop, nullptr otherwise -- whether kb replaces k (bounded_f32).
+// The setup the persistent launches share (launch_render's dynamic schedules, launch_accumulate, launch_adaptive): four-wave 16 x 16
+// workgroups, the main launch's clock stamps (stamp_clock), the LDS layout with drain scratch, the kernel pick(src, bounded) -- bounded:
+// std::true_type for fp32's bounded twin only -- allowed its LDS, and the two hand-out counters.
+template <class T, class Pick>
+int persistent_setup(rtiow_handle_s* h, Launch<T>& L, bool stamp_clock, bool record_stats, Pick pick) {
+    L.p.cold.bx = 16; L.p.cold.by = 16; L.p.cold.wave_tiles = 1;
+    L.p.cold.clock_stamps = stamp_clock && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
+    if (int rc = layout_lds<T>(h, L, 256, true, record_stats)) return rc;
+    L.k = by_source(L.lds_source, [&](auto src) { return pick(src, std::false_type()); });
+    if constexpr (sizeof(T) == 4) L.kb = by_source(L.lds_source, [&](auto src) { return pick(src, std::true_type()); });
+    HIP_TRY(h, allow_lds(L.k, L.lds));
+    HIP_TRY(h, h->work_counter.ensure(2 * sizeof(unsigned int)));
+    return 0;
+}
+
+// Size L's persistent launch over `slots` hand-out slots, taken from h->work_counter in tile order: the lanes of a wave that take pixels
+// (p.lane_cap), the workgroups to launch (blocks) and whether the fp32 bounded twin kb replaces k (bounded_f32); then k's attributes.
 template <class T>
-int size_persistent(rtiow_handle_s* h, RenderFn<T>& k, RenderFn<T> kb, int threads, size_t lds, long long tile_slots,
-                    int& lane_cap, bool& bounded_f32, long long& blocks) {
-    const int waves_per_block = (threads + 63) / 64;
+int size_persistent(rtiow_handle_s* h, Launch<T>& L, long long slots) {
+    const int threads = L.p.cold.bx * L.p.cold.by, waves_per_block = (threads + 63) / 64;
     int per_cu = 0;
-    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, threads, lds));
+    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)L.k, threads, L.lds));
     if (per_cu < 1) per_cu = 1;
     if (h->waves_per_simd > 0) {                       // knob: fewer resident waves, more pixels per lane
         const int cap = (h->waves_per_simd * 4 + waves_per_block - 1) / waves_per_block;
@@ -128,33 +147,34 @@ int size_persistent(rtiow_handle_s* h, RenderFn<T>& k, RenderFn<T> kb, int threa
     // shorter, and with so little work the frame is as long as its longest chain of trips.
     // Measured (profiles/archive/r01_lane_cap_sweep.txt): scene 1 320x192x10 2.27 -> 1.06 ms, 640x384x100
     // 19.4 -> 17.0 ms; frames with at least one pool per wave are unchanged (cap 64).
-    lane_cap = 64;
-    {
-        const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
-        while (lane_cap > 16 && pools * (64 / lane_cap) < waves) lane_cap >>= 1;  // the largest share that keeps every wave busy; not below 16 (with the grid walk 8-lane waves lose: scene 1 320x192x100 6.85 vs 5.96 ms, profiles/archive/r02_lane_cap_sweep.jsonl)
-        lane_cap = tuned("RTIOW_TUNE_LANE_CAP", lane_cap);
-    }
+    int lane_cap = 64;
+    const long long pools = slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
+    while (lane_cap > 16 && pools * (64 / lane_cap) < waves) lane_cap >>= 1;  // the largest share that keeps every wave busy; not below 16 (with the grid walk 8-lane waves lose: scene 1 320x192x100 6.85 vs 5.96 ms, profiles/archive/r02_lane_cap_sweep.jsonl)
+    lane_cap = tuned("RTIOW_TUNE_LANE_CAP", lane_cap);
     // fp32: the bounded rejection loop where throughput binds -- at least four pools per resident wave (1080p: 6.3; 1280 x 720, shards and small
     // frames end with one chain's latency and keep the blocking loop) -- if that kernel keeps the occupancy this launch was sized for
-    bounded_f32 = false;
-    if (kb) {
-        const long long pools = tile_slots / POOL, waves = (long long)h->num_cus * per_cu * waves_per_block;
+    L.bounded_f32 = false;
+    if (L.kb) {
 #ifdef RTIOW_TUNING
         const bool want = tuned("RTIOW_TUNE_RUV_BOUNDED", pools >= 4 * waves ? 1 : 0) != 0;
 #else
         const bool want = pools >= 4 * waves;
 #endif
         if (want) {
-            if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(h, allow_lds(L.kb, L.lds));
             int per_cu_b = 0;
-            HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, (const void*)kb, threads, lds));
-            if (per_cu_b >= per_cu) { k = kb; bounded_f32 = true; }
+            HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, (const void*)L.kb, threads, L.lds));
+            if (per_cu_b >= per_cu) { L.k = L.kb; L.bounded_f32 = true; }
         }
     }
-    blocks = (long long)h->num_cus * per_cu;
+    L.blocks = (long long)h->num_cus * per_cu;
     const long long per_block = (long long)waves_per_block * lane_cap;
-    const long long useful = (tile_slots + per_block - 1) / per_block;
-    if (blocks > useful) blocks = useful;               // never more waves than lane_cap-pixel shares of the pools
+    const long long useful = (slots + per_block - 1) / per_block;
+    if (L.blocks > useful) L.blocks = useful;               // never more waves than lane_cap-pixel shares of the pools
+    L.p.lane_cap = lane_cap;
+    L.p.cold.total_slots = (int)slots;
+    L.p.cold.work_counter = h->work_counter;
+    HIP_TRY(h, hipFuncGetAttributes(&L.fa, (const void*)L.k));
     return 0;
 }
 
@@ -209,52 +229,67 @@ inline int rank_pixels(rtiow_handle_s* h, const uint32_t* cost, long long blocks
     return 0;
 }
 
-template <class T, class CAM>
-int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_tiles, unsigned long long* seg_counter = nullptr,
-                  bool prepare_only = false) {
-    RenderParams<T> p = make_params<T>(h, cam);
-    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = wave_tiles;
+// The main launch of a ranked hand-out takes its slots from h->order (rank_pixels): the first solo_slots go to the solo waves, every other
+// resident wave starts with a pool of its own (ColdParams::first_pools), and the second counter hands out the rest.
+template <class T>
+int hand_out_ranked(rtiow_handle_s* h, Launch<T>& L, int total_pools, int solo_slots, int solo_waves) {
+    L.p.cold.order = h->order;
+    L.p.cold.total_slots = solo_slots + total_pools * POOL;
+    L.p.cold.work_counter = h->work_counter + 1;
+    L.p.cold.first_pools = 1;
+    const int resident_waves = (int)L.blocks * ((L.p.cold.bx * L.p.cold.by + 63) / 64);
+    const unsigned counter_start = (unsigned)solo_slots + (unsigned)(resident_waves - solo_waves) * (unsigned)L.p.lane_cap;
+    HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)(h->work_counter + 1), (int)counter_start, 1, h->stream));
+    return 0;
+}
+
+// rtiow_stats of a render-family launch (not of a counting run).  A launch of no workgroups (an adaptive chunk without active pixels)
+// reports no kernel resources.
+template <class T>
+void record_launch(rtiow_handle_s* h, const Launch<T>& L, int phases = 1, int solo_waves = 0, int solo_lanes = 0, int staged_stores = 0) {
+    h->stats.vgprs = L.fa.numRegs;
+    h->stats.sgprs = 0;
+    h->stats.lds_bytes = L.blocks > 0 ? (int)(L.lds + L.fa.sharedSizeBytes) : 0;
+    h->stats.block_x = L.p.cold.bx; h->stats.block_y = L.p.cold.by;
+    h->stats.scene_source = L.effective_source;
+    h->stats.schedule = h->schedule;
+    h->stats.grid_blocks = (int)L.blocks;
+    h->stats.phases = phases;
+    if (phases == 1) h->stats.prepass_samples = 0;
+    h->stats.solo_waves = solo_waves;
+    h->stats.solo_lanes = solo_lanes;
+    h->stats.staged_stores = staged_stores;
+}
+
+template <class T>
+int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned long long* seg_counter = nullptr, bool prepare_only = false) {
+    const bool count = seg_counter != nullptr;
+    Launch<T> L{make_params<T>(h)};
+    RenderParams<T>& p = L.p;
+    const dim3 block(bx * by);
     p.cold.seg_counter = seg_counter ? seg_counter + 1 : nullptr;     // [0] prepass launch, [1] main (or only) launch
-    p.lane_cap = 64;
-    const bool persistent = h->schedule != RTIOW_SCHED_STATIC;
-    const int threads = bx * by;
-    size_t lds = 0;
-    bool lds_source = false;
-    int effective_source = h->scene_source;
-    int rc0 = layout_lds<T>(h, p, threads, persistent, !seg_counter, lds, lds_source, effective_source);
-    if (rc0) return rc0;
-    p.cold.timeline = nullptr;                                    // set below, once the grid is known
-    p.cold.clock_stamps = (!seg_counter && h->schedule != RTIOW_SCHED_STATIC && h->clock_stamps_dev) ? h->clock_stamps_dev + 4 : nullptr;   // the main (or only) launch; timed renders only
     p.cold.pixel_times = seg_counter ? h->pixel_times : nullptr;
-#ifdef RTIOW_DEBUG_API
-    if (h->probe_n > 0) {                                    // rtiow_debug_hit_world: the tables are laid out, run hit_world on the caller's rays
-        if (!lds_source) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_hit_world needs an LDS scene source");
-        if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)hit_probe_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int blocks = std::min(2048, (h->probe_n + 255) / 256);
-        hipLaunchKernelGGL(hit_probe_kernel<T>, dim3(blocks), dim3(256), lds, h->stream, p, (const T*)h->probe_rays, h->probe_n, (T*)h->probe_t, h->probe_idx);
-        HIP_TRY(h, hipGetLastError());
-        if (!seg_counter) h->stats.scene_source = effective_source;
-        return 0;
-    }
-#endif
-    RenderFn<T> k = pick_kernel<T>(persistent, lds_source, seg_counter != nullptr);
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipFuncAttributes fa{};
-    HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
-    dim3 grid, block(threads);
     int phases = 1;
-    if (persistent) {
-        if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
+    dim3 grid;
+    if (h->schedule == RTIOW_SCHED_STATIC) {
+        p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = wave_tiles;
+        p.lane_cap = 64;
+        if (int rc = layout_lds<T>(h, L, bx * by, false, !count)) return rc;
+        L.k = by_source(L.lds_source, [&](auto src) { return count ? render_kernel<T, src, true> : render_kernel<T, src, false>; });
+        HIP_TRY(h, allow_lds(L.k, L.lds));
+        HIP_TRY(h, hipFuncGetAttributes(&L.fa, (const void*)L.k));
+        grid = dim3((p.cold.W + bx - 1) / bx, (h->local_rows + by - 1) / by);
+        L.blocks = (long long)grid.x * grid.y;
+    } else {
+        int rc = persistent_setup(h, L, !count, !count, [&](auto src, auto bounded) {
+            return count ? render_persistent_kernel<T, src, true, bounded> : render_persistent_kernel<T, src, false, bounded>;
+        });
+        if (rc) return rc;
         HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
-        const int waves_per_block = (threads + 63) / 64;
-        const long long tile_slots = (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL;
-        int lane_cap = 64;
-        bool bounded_f32 = false;
-        long long blocks = 0;
-        int rc1 = size_persistent<T>(h, k, pick_bounded_kernel<T>(false, lds_source, seg_counter != nullptr), threads, lds, tile_slots, lane_cap, bounded_f32, blocks);
-        if (rc1) return rc1;
-        if (bounded_f32) HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
-        p.lane_cap = lane_cap;
+        const int waves_per_block = 4;
+        if ((rc = size_persistent<T>(h, L, (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL))) return rc;
+        const long long blocks = L.blocks;
+        const int lane_cap = p.lane_cap;
         grid = dim3((unsigned)blocks);
 
         const int npix = p.cold.W * h->local_rows;
@@ -262,17 +297,12 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
         // prepass length: enough samples to rank the pixels, a small share of the frame
         int SA = S >= 64 ? 3 : (S >= 24 ? 2 : 0);
         SA = tuned("RTIOW_TUNE_SA", SA);       // measured on the headline config: 1 -> 25.5 ms, 2 -> 22.5, 3 -> 22.1, 4 -> 22.4, 8 -> 23.1
-        p.cold.work_counter = h->work_counter;
-        p.cold.s_begin = 0; p.s_end = S; p.cold.rng_in = h->rng; p.cold.mid_in = nullptr; p.cold.mid_out = nullptr;
-        p.cold.cost_out = nullptr; p.cold.order = nullptr; p.cold.total_slots = (int)tile_slots; p.cold.first_pools = 0;
-        p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
-        if (h->schedule == RTIOW_SCHED_SORTED && SA > 0 && npix >= 4096 && p.cold.W < 65536 && h->local_rows < 32768) {   // (the order's entries are row << 16 | column)
+        if (SA > 0 && sorted_handout(h)) {
             phases = 2;
             const int total_pools = (npix + POOL - 1) / POOL;
-            int rc;
-            if ((rc = ensure_buffer(h, &h->mid, &h->mid_bytes, (size_t)npix * sizeof(MidState<T>)))) return rc;
-            if ((rc = ensure_buffer(h, &h->cost, &h->cost_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
-            if ((rc = ensure_buffer(h, &h->cost_rank, &h->cost_rank_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
+            HIP_TRY(h, h->mid.ensure((size_t)npix * sizeof(MidState<T>)));
+            HIP_TRY(h, h->cost.ensure((size_t)npix * sizeof(uint32_t)));
+            HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
             // Solo waves (ColdParams::solo_*, render_solo_kernel).  A shard or small frame ends with its longest sample
             // chains (one pixel = one sequential chain), and a chain advances at the pace of its wave: 2452 segments at
             // ~3 us per trip among 63 other pixels.  Two heavy pixels alone in a wave share every sphere loop with the
@@ -289,19 +319,19 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
             solo_waves = tuned("RTIOW_TUNE_SOLO_WAVES", solo_waves);
             solo_lanes = tuned("RTIOW_TUNE_SOLO_LANES", solo_lanes);
             if (solo_lanes < 1) solo_lanes = 1;
-            RenderFn<T> k_solo = lds_source ? (RenderFn<T>)render_solo_kernel<T, RTIOW_SCENE_LDS> : (RenderFn<T>)render_solo_kernel<T, RTIOW_SCENE_SCALAR>;
+            const RenderFn<T> k_solo = by_source(L.lds_source, [](auto src) { return render_solo_kernel<T, src>; });
             if (solo_waves > 0) {
-                if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k_solo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                HIP_TRY(h, allow_lds(k_solo, L.lds));
                 int per_cu_solo = 0;
-                HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_solo, (const void*)k_solo, threads, lds));
+                HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_solo, (const void*)k_solo, 256, L.lds));
                 if ((long long)per_cu_solo * h->num_cus < blocks) solo_waves = 0;   // its workgroups must all be resident, as the first pools assume
             }
             if (solo_lanes > lane_cap) solo_lanes = lane_cap;
             if (solo_waves > (int)blocks) solo_waves = (int)blocks;
             if ((long long)solo_waves * solo_lanes > npix / 2) solo_waves = npix / 2 / solo_lanes;
             const int solo_slots = solo_waves * solo_lanes;
-            if ((rc = ensure_buffer(h, &h->order, &h->order_bytes, ((size_t)total_pools * POOL + (size_t)solo_slots) * sizeof(int)))) return rc;
-            if ((rc = ensure_buffer(h, &h->sort_scratch, &h->sort_scratch_bytes, (size_t)3 * COST_BINS * sizeof(unsigned)))) return rc;
+            HIP_TRY(h, h->order.ensure(((size_t)total_pools * POOL + (size_t)solo_slots) * sizeof(int)));
+            HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
             // finished pixels go to their slot in a staging buffer and place_pixels_kernel writes the image (ColdParams::stage_by_slot)
 #ifdef RTIOW_DIRECT_STORES
             const bool staged_stores = false;           // A/B build: every lane stores its pixel at its place in the image when it finishes
@@ -310,8 +340,8 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
 #endif
             const size_t total_slots = (size_t)total_pools * POOL + (size_t)solo_slots;
             if (staged_stores) {
-                if ((rc = ensure_buffer(h, &h->slot_of, &h->slot_of_bytes, (size_t)npix * sizeof(int)))) return rc;
-                if ((rc = ensure_buffer(h, &h->staged, &h->staged_bytes, total_slots * 3 * sizeof(T)))) return rc;
+                HIP_TRY(h, h->slot_of.ensure((size_t)npix * sizeof(int)));
+                HIP_TRY(h, h->staged.ensure(total_slots * 3 * sizeof(T)));
             }
             if (prepare_only) return 0;                  // every table and buffer of this configuration now exists
             // ---- prepass: samples [0, SA) in tile order through the same persistent body (the static
@@ -321,196 +351,145 @@ int launch_render(rtiow_handle_s* h, const CAM& cam, int bx, int by, int wave_ti
             pa.s_end = SA; pa.cold.mid_out = h->mid; pa.cold.cost_out = h->cost;
             pa.cold.seg_counter = seg_counter;
             if (pa.cold.clock_stamps) pa.cold.clock_stamps = h->clock_stamps_dev;          // the prepass's four words
-            RenderFn<T> kp = bounded_f32 ? pick_bounded_kernel<T>(true, lds_source, seg_counter != nullptr) : pick_prepass_kernel<T>(lds_source, seg_counter != nullptr);
-            if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kp, grid, block, lds, h->stream, pa);
+            const RenderFn<T> kp = by_source(L.lds_source, [&](auto src) -> RenderFn<T> {
+                if constexpr (sizeof(T) == 4)
+                    if (L.bounded_f32) return count ? render_prepass_kernel<T, src, true, true> : render_prepass_kernel<T, src, false, true>;
+                return count ? render_prepass_kernel<T, src, true> : render_prepass_kernel<T, src, false>;
+            });
+            HIP_TRY(h, allow_lds(kp, L.lds));
+            hipLaunchKernelGGL(kp, grid, block, L.lds, h->stream, pa);
             if (h->time_phases) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
             h->stats.prepass_samples = SA;
             HIP_TRY(h, hipGetLastError());
             // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools
-            if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of : nullptr))) return rc;
-            const int resident_waves = (int)blocks * waves_per_block;
+            if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of.as<int>() : nullptr))) return rc;
             // ---- main launch: samples [SA, S) in that order
-            p.cold.s_begin = SA; p.cold.mid_in = h->mid; p.cold.order = h->order;
-            p.cold.total_slots = solo_slots + total_pools * POOL;
-            p.cold.work_counter = h->work_counter + 1;
-            p.cold.first_pools = 1;
+            p.cold.s_begin = SA; p.cold.mid_in = h->mid;
             p.cold.solo_waves = solo_waves; p.cold.solo_lanes = solo_lanes;
-            if (staged_stores) { p.cold.stage_by_slot = 1; p.cold.fb = (T*)h->staged; }
+            if (staged_stores) { p.cold.stage_by_slot = 1; p.cold.fb = h->staged.as<T>(); }
             if (solo_waves > 0) {
-                k = k_solo;
-                HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
+                L.k = k_solo;
+                HIP_TRY(h, hipFuncGetAttributes(&L.fa, (const void*)L.k));
             }
-            const unsigned counter_start = (unsigned)solo_slots + (unsigned)(resident_waves - solo_waves) * (unsigned)lane_cap;
-            HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)(h->work_counter + 1), (int)counter_start, 1, h->stream));
+            if ((rc = hand_out_ranked(h, L, total_pools, solo_slots, solo_waves))) return rc;
         }
-    } else {
-        grid = dim3((p.cold.W + bx - 1) / bx, (h->local_rows + by - 1) / by);
-        p.cold.s_begin = 0; p.s_end = p.cold.S; p.cold.rng_in = h->rng; p.cold.mid_in = nullptr; p.cold.mid_out = nullptr;
-        p.cold.cost_out = nullptr; p.cold.order = nullptr; p.cold.total_slots = 0; p.cold.first_pools = 0; p.cold.work_counter = nullptr;
-        p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
     }
     if (prepare_only) return 0;
     if (seg_counter) {
-        h->last_count_blocks = (int)(grid.x * grid.y);
-        h->last_count_waves_per_block = (threads + 63) / 64;
+        h->last_count_blocks = (int)L.blocks;
+        h->last_count_waves_per_block = (int)((block.x + 63) / 64);
         // the kernel writes 8 words per wave: hand the buffer over only if it holds every wave of this launch
         if (h->timeline && (size_t)h->last_count_blocks * h->last_count_waves_per_block <= h->timeline_cap_waves) p.cold.timeline = h->timeline;
     }
     if (h->time_phases && phases == 2) HIP_TRY(h, hipEventRecord(h->ev_b, h->stream));
-    hipLaunchKernelGGL(k, grid, block, lds, h->stream, p);
+    hipLaunchKernelGGL(L.k, grid, block, L.lds, h->stream, p);
     HIP_TRY(h, hipGetLastError());
     if (p.cold.stage_by_slot) {                             // slot order -> image, in whole lines
         if (h->time_phases) HIP_TRY(h, hipEventRecord(h->ev_c, h->stream));
         const int npix = p.cold.W * h->local_rows;
-        hipLaunchKernelGGL(place_pixels_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (const T*)h->staged, h->slot_of, (T*)h->fb, npix);
+        hipLaunchKernelGGL(place_pixels_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, h->staged.as<const T>(), h->slot_of, (T*)h->fb, npix);
         HIP_TRY(h, hipGetLastError());
     }
-    if (!seg_counter) {
-        h->stats.vgprs = fa.numRegs;
-        h->stats.sgprs = 0;
-        h->stats.lds_bytes = (int)(lds + fa.sharedSizeBytes);
-        h->stats.block_x = bx; h->stats.block_y = by;
-        h->stats.scene_source = effective_source;
-        h->stats.schedule = h->schedule;
-        h->stats.grid_blocks = (int)(grid.x * grid.y);
-        h->stats.phases = phases;
-        if (phases == 1) h->stats.prepass_samples = 0;
-        h->stats.solo_waves = phases == 2 ? p.cold.solo_waves : 0;
-        h->stats.solo_lanes = phases == 2 && p.cold.solo_waves > 0 ? p.cold.solo_lanes : 0;
-        h->stats.staged_stores = p.cold.stage_by_slot;
+    if (!count) {
+        record_launch(h, L, phases, p.cold.solo_waves, p.cold.solo_waves > 0 ? p.cold.solo_lanes : 0, p.cold.stage_by_slot);
+        h->stats.primary_rays = (uint64_t)h->local_rows * p.cold.W * (uint64_t)p.cold.S;
     }
     return 0;
 }
 
+#ifdef RTIOW_DEBUG_API
+// rtiow_debug_hit_world: hit_world on n caller rays {O, D} (device memory) with the scene laid out as the persistent launches lay it out.
+template <class T>
+int launch_probe(rtiow_handle_s* h, int n, const T* rays, T* t_out, int* index_out) {
+    Launch<T> L{make_params<T>(h)};
+    if (int rc = layout_lds<T>(h, L, 256, true, true)) return rc;
+    if (!L.lds_source) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_hit_world needs an LDS scene source");
+    HIP_TRY(h, allow_lds(hit_probe_kernel<T>, L.lds));
+    const int blocks = std::min(2048, (n + 255) / 256);
+    hipLaunchKernelGGL(hit_probe_kernel<T>, dim3(blocks), dim3(256), L.lds, h->stream, L.p, rays, n, t_out, index_out);
+    HIP_TRY(h, hipGetLastError());
+    h->stats.scene_source = L.effective_source;
+    return 0;
+}
+#endif
+
 // One chunk of progressive rendering (rtiow_accumulate): samples [h->acc_samples, h->acc_samples + samples) of every local pixel through
-// render_accumulate_kernel, always with the persistent hand-out (four-wave workgroups, the sizing of launch_render).  The first chunk after
-// a reset starts from the RNG states of rtiow_init_rng in tile order; under RTIOW_SCHED_SORTED every later chunk ranks the pixels
-// heavy-first by the segments each ran in the previous chunk (same limits as launch_render).  No solo waves, no staged stores: the preview
-// is stored at its pixel.  timed: the start event goes behind the allocations and table builds, in front of the first enqueued work.
-template <class T, class CAM>
-int launch_accumulate(rtiow_handle_s* h, const CAM& cam, int samples, bool timed) {
-    RenderParams<T> p = make_params<T>(h, cam);
-    const int bx = 16, by = 16, threads = bx * by;
-    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = 1;
-    p.cold.seg_counter = nullptr; p.cold.timeline = nullptr; p.cold.pixel_times = nullptr;
-    p.cold.clock_stamps = timed && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
-    size_t lds = 0;
-    bool lds_source = false;
-    int effective_source = h->scene_source;
-    int rc = layout_lds<T>(h, p, threads, true, true, lds, lds_source, effective_source);
+// render_accumulate_kernel, always with the persistent hand-out.  The first chunk after a reset starts from the RNG states of rtiow_init_rng
+// in tile order; under RTIOW_SCHED_SORTED every later chunk ranks the pixels heavy-first by the segments each ran in the previous chunk
+// (same limits as launch_render).  No solo waves, no staged stores: the preview is stored at its pixel.  timed: the start event goes
+// behind the allocations and table builds, in front of the first enqueued work.
+template <class T>
+int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
+    Launch<T> L{make_params<T>(h)};
+    RenderParams<T>& p = L.p;
+    int rc = persistent_setup(h, L, timed, true, [](auto src, auto bounded) { return render_accumulate_kernel<T, src, bounded>; });
     if (rc) return rc;
-    RenderFn<T> k = lds_source ? (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_LDS> : (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_SCALAR>;
-    RenderFn<T> kb = nullptr;                             // fp32: the same kernel with the bounded rejection loop (fp64 bounds it in every kernel)
-    if constexpr (sizeof(T) == 4) kb = lds_source ? (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_LDS, true> : (RenderFn<T>)render_accumulate_kernel<T, RTIOW_SCENE_SCALAR, true>;
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int waves_per_block = (threads + 63) / 64;
-    const long long tile_slots = (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL;
-    int lane_cap = 64;
-    bool bounded_f32 = false;
-    long long blocks = 0;
-    if ((rc = size_persistent<T>(h, k, kb, threads, lds, tile_slots, lane_cap, bounded_f32, blocks))) return rc;
-    hipFuncAttributes fa{};
-    HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
-    p.lane_cap = lane_cap;
+    if ((rc = size_persistent<T>(h, L, (long long)((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8) * POOL))) return rc;
 
     // The state records ping-pong: the chunk reads acc_mid[acc_cur] and writes the other buffer.
     const int npix = p.cold.W * h->local_rows;
     const int n = h->acc_samples;
-    if ((rc = ensure_buffer(h, &h->acc_mid[0], &h->acc_mid_bytes[0], (size_t)npix * sizeof(MidState<T>)))) return rc;
-    if ((rc = ensure_buffer(h, &h->acc_mid[1], &h->acc_mid_bytes[1], (size_t)npix * sizeof(MidState<T>)))) return rc;
-    if ((rc = ensure_buffer(h, &h->acc_cost, &h->acc_cost_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
-    if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
-    const bool ranked = h->schedule == RTIOW_SCHED_SORTED && n > 0 && npix >= 4096 && p.cold.W < 65536 && h->local_rows < 32768;   // (row << 16 | column)
+    for (auto& b : h->acc_mid) HIP_TRY(h, b.ensure((size_t)npix * sizeof(MidState<T>)));
+    HIP_TRY(h, h->acc_cost.ensure((size_t)npix * sizeof(uint32_t)));
+    const bool ranked = n > 0 && sorted_handout(h);
     const int total_pools = (npix + POOL - 1) / POOL;
     if (ranked) {
-        if ((rc = ensure_buffer(h, &h->cost_rank, &h->cost_rank_bytes, (size_t)npix * sizeof(uint32_t)))) return rc;
-        if ((rc = ensure_buffer(h, &h->order, &h->order_bytes, (size_t)total_pools * POOL * sizeof(int)))) return rc;
-        if ((rc = ensure_buffer(h, &h->sort_scratch, &h->sort_scratch_bytes, (size_t)3 * COST_BINS * sizeof(unsigned)))) return rc;
+        HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
+        HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
+        HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
     }
     const int in = h->acc_cur, out = n > 0 ? 1 - in : 0;
     p.cold.s_begin = n; p.s_end = n + samples;
     p.cold.pixel_samples_scale = (T)1 / (T)(n + samples);   // rtiow_host_camera's 1 / samples_per_pixel at the running total
-    p.cold.rng_in = h->rng;
-    p.cold.mid_in = n > 0 ? h->acc_mid[in] : nullptr;
+    if (n > 0) p.cold.mid_in = h->acc_mid[in];
     p.cold.mid_out = h->acc_mid[out];
     p.cold.cost_out = h->acc_cost;
-    p.cold.order = nullptr; p.cold.total_slots = (int)tile_slots; p.cold.first_pools = 0;
-    p.cold.work_counter = h->work_counter;
-    p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
 
     if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
     if (ranked) {
         // the previous chunk's segment counts rank this one (the launch below overwrites them: stream order)
-        if ((rc = rank_pixels(h, h->acc_cost, blocks, waves_per_block, total_pools, 0, nullptr))) return rc;
-        p.cold.order = h->order;
-        p.cold.total_slots = total_pools * POOL;
-        p.cold.work_counter = h->work_counter + 1;
-        p.cold.first_pools = 1;
-        const unsigned counter_start = (unsigned)blocks * (unsigned)waves_per_block * (unsigned)lane_cap;
-        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)(h->work_counter + 1), (int)counter_start, 1, h->stream));
+        if ((rc = rank_pixels(h, h->acc_cost, L.blocks, 4, total_pools, 0, nullptr))) return rc;
+        if ((rc = hand_out_ranked(h, L, total_pools, 0, 0))) return rc;
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, p);
+    hipLaunchKernelGGL(L.k, dim3((unsigned)L.blocks), dim3(256), L.lds, h->stream, p);
     HIP_TRY(h, hipGetLastError());
     h->acc_cur = out;
-    h->stats.vgprs = fa.numRegs;
-    h->stats.sgprs = 0;
-    h->stats.lds_bytes = (int)(lds + fa.sharedSizeBytes);
-    h->stats.block_x = bx; h->stats.block_y = by;
-    h->stats.scene_source = effective_source;
-    h->stats.schedule = h->schedule;
-    h->stats.grid_blocks = (int)blocks;
-    h->stats.phases = 1;
-    h->stats.prepass_samples = 0;
-    h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
-    h->stats.staged_stores = 0;
+    record_launch(h, L);
     h->stats.primary_rays = (uint64_t)npix * (uint64_t)samples;
     return 0;
 }
 
 // One adaptive chunk (rtiow_accumulate_adaptive): adaptive_select_kernel lists the active pixels in h->order and copies the records of the
 // others, the host reads the active count back (the call blocks here once), render_adaptive_kernel renders `samples` more samples of the
-// active pixels with a persistent grid sized from the active slots (four-wave workgroups, the sizing of launch_render), and
-// adaptive_finish_kernel writes every pixel's preview, count and error.  The records ping-pong between h->acc_mid[0/1] like
-// launch_accumulate's.  No ranking by previous cost and no solo waves.  timed: ev0 -> ev_a (select) plus ev_b -> ev1 (render and finish):
-// the read-back between them is not counted.  The caller has checked W < 65536 and local_rows < 32768 (the order's encoding).
-template <class T, class CAM>
-int launch_adaptive(rtiow_handle_s* h, const CAM& cam, int samples, int min_samples, double rel_error, int max_samples, bool timed, int& active) {
-    RenderParams<T> p = make_params<T>(h, cam);
-    const int bx = 16, by = 16, threads = bx * by;
-    p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = 1;
-    p.cold.seg_counter = nullptr; p.cold.timeline = nullptr; p.cold.pixel_times = nullptr;
-    p.cold.clock_stamps = timed && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
-    size_t lds = 0;
-    bool lds_source = false;
-    int effective_source = h->scene_source;
-    int rc = layout_lds<T>(h, p, threads, true, true, lds, lds_source, effective_source);
+// active pixels with a persistent grid sized from the active slots, and adaptive_finish_kernel writes every pixel's preview, count and
+// error.  The records ping-pong between h->acc_mid[0/1] like launch_accumulate's.  No ranking by previous cost and no solo waves.
+// timed: ev0 -> ev_a (select) plus ev_b -> ev1 (render and finish): the read-back between them is not counted.  The caller has checked
+// order_fits.
+template <class T>
+int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_error, int max_samples, bool timed, int& active) {
+    Launch<T> L{make_params<T>(h)};
+    RenderParams<T>& p = L.p;
+    int rc = persistent_setup(h, L, timed, true, [](auto src, auto bounded) { return render_adaptive_kernel<T, src, bounded>; });
     if (rc) return rc;
-    RenderFn<T> k = lds_source ? (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_LDS> : (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_SCALAR>;
-    RenderFn<T> kb = nullptr;                             // fp32: the same kernel with the bounded rejection loop (fp64 bounds it in every kernel)
-    if constexpr (sizeof(T) == 4) kb = lds_source ? (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_LDS, true> : (RenderFn<T>)render_adaptive_kernel<T, RTIOW_SCENE_SCALAR, true>;
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
     const int W = p.cold.W, npix = W * h->local_rows;
     const int total_pools = (npix + POOL - 1) / POOL;
-    if ((rc = ensure_buffer(h, &h->acc_mid[0], &h->acc_mid_bytes[0], (size_t)npix * sizeof(MidState<T>)))) return rc;
-    if ((rc = ensure_buffer(h, &h->acc_mid[1], &h->acc_mid_bytes[1], (size_t)npix * sizeof(MidState<T>)))) return rc;
-    if ((rc = ensure_buffer(h, &h->adapt_counts, &h->adapt_counts_bytes, (size_t)npix * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_buffer(h, &h->adapt_err, &h->adapt_err_bytes, (size_t)npix * sizeof(float)))) return rc;
-    if ((rc = ensure_buffer(h, &h->adapt_ctr, &h->adapt_ctr_bytes, 2 * sizeof(unsigned)))) return rc;
-    if ((rc = ensure_buffer(h, &h->order, &h->order_bytes, (size_t)total_pools * POOL * sizeof(int)))) return rc;
-    if (!h->work_counter) HIP_TRY(h, hipMalloc((void**)&h->work_counter, 2 * sizeof(unsigned int)));
+    for (auto& b : h->acc_mid) HIP_TRY(h, b.ensure((size_t)npix * sizeof(MidState<T>)));
+    HIP_TRY(h, h->adapt_counts.ensure((size_t)npix * sizeof(int32_t)));
+    HIP_TRY(h, h->adapt_err.ensure((size_t)npix * sizeof(float)));
+    HIP_TRY(h, h->adapt_ctr.ensure(2 * sizeof(unsigned)));
+    HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
     const bool first = h->acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
     const int in = h->acc_cur, out = first ? 0 : 1 - in;
-    const unsigned char* mid_in = first ? nullptr : h->acc_mid[in];
-    unsigned char* mid_out = h->acc_mid[out];
+    if (!first) p.cold.mid_in = h->acc_mid[in];
+    p.cold.mid_out = h->acc_mid[out];
 
     if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->adapt_ctr, 0, 2 * sizeof(unsigned), h->stream));
     const int tiles = ((W + 7) / 8) * ((h->local_rows + 7) / 8);
     hipLaunchKernelGGL(adaptive_select_kernel<T>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, h->stream, FrameShape{W, h->local_rows},
-                       samples, min_samples, max_samples, rel_error, h->adapt_counts, h->adapt_err, h->rng, mid_in, mid_out, h->order, h->adapt_ctr);
+                       samples, min_samples, max_samples, rel_error, h->adapt_counts, h->adapt_err, h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
     HIP_TRY(h, hipGetLastError());
     if (timed) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
     unsigned n_active = 0;
@@ -519,69 +498,42 @@ int launch_adaptive(rtiow_handle_s* h, const CAM& cam, int samples, int min_samp
     active = (int)n_active;
     if (timed) HIP_TRY(h, hipEventRecord(h->ev_b, h->stream));
 
-    const long long active_slots = ((long long)n_active + POOL - 1) / POOL * POOL;
-    long long blocks = 0;
-    hipFuncAttributes fa{};
     if (n_active > 0) {
-        int lane_cap = 64;
-        bool bounded_f32 = false;
-        if ((rc = size_persistent<T>(h, k, kb, threads, lds, active_slots, lane_cap, bounded_f32, blocks))) return rc;
-        HIP_TRY(h, hipFuncGetAttributes(&fa, (const void*)k));
-        p.lane_cap = lane_cap;
-        p.cold.s_begin = 0; p.s_end = samples;            // the chunk's own sample numbering: adaptive_pixel adds it to the pixel's count
+        const long long active_slots = ((long long)n_active + POOL - 1) / POOL * POOL;
+        if ((rc = size_persistent<T>(h, L, active_slots))) return rc;
+        p.s_end = samples;                                // the chunk's own sample numbering: adaptive_pixel adds it to the pixel's count
         p.cold.pixel_samples_scale = (T)0;                // not read: no preview in the render
-        p.cold.rng_in = h->rng;
-        p.cold.mid_in = mid_in;
-        p.cold.mid_out = mid_out;
-        p.cold.cost_out = nullptr;
-        p.cold.order = h->order; p.cold.total_slots = (int)active_slots; p.cold.first_pools = 0;
-        p.cold.work_counter = h->work_counter;
-        p.cold.solo_waves = 0; p.cold.solo_lanes = 1; p.cold.stage_by_slot = 0;
+        p.cold.order = h->order;
         if (active_slots > (long long)n_active)           // the tail of the last pool: -1, no pixel
             HIP_TRY(h, hipMemsetAsync(h->order + n_active, 0xff, (size_t)(active_slots - n_active) * sizeof(int), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, p);
+        hipLaunchKernelGGL(L.k, dim3((unsigned)L.blocks), dim3(256), L.lds, h->stream, p);
         HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (size_t)npix, (const unsigned char*)mid_out,
+    hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (size_t)npix, (const unsigned char*)p.cold.mid_out,
                        p.cold.fb, h->adapt_counts, h->adapt_err, h->adapt_ctr + 1);
     HIP_TRY(h, hipGetLastError());
     h->acc_cur = out;
-    h->stats.vgprs = fa.numRegs;
-    h->stats.sgprs = 0;
-    h->stats.lds_bytes = n_active > 0 ? (int)(lds + fa.sharedSizeBytes) : 0;
-    h->stats.block_x = bx; h->stats.block_y = by;
-    h->stats.scene_source = effective_source;
-    h->stats.schedule = h->schedule;
-    h->stats.grid_blocks = (int)blocks;
-    h->stats.phases = 1;
-    h->stats.prepass_samples = 0;
-    h->stats.solo_waves = 0; h->stats.solo_lanes = 0;
-    h->stats.staged_stores = 0;
+    record_launch(h, L);
     h->stats.primary_rays = (uint64_t)n_active * (uint64_t)samples;
     return 0;
 }
 
 // First-hit guides of every local pixel (rtiow_render_guides) into h->guide_nd / h->guide_alb: guide_kernel with the scene staged as
 // the render launches stage it (layout_lds of a non-persistent launch: no drain scratch), one 8x8 tile per wave, four waves a workgroup.
-template <class T, class CAM>
-int launch_guides(rtiow_handle_s* h, const CAM& cam) {
-    RenderParams<T> p = make_params<T>(h, cam);
+template <class T>
+int launch_guides(rtiow_handle_s* h) {
+    Launch<T> L{make_params<T>(h)};
     const int threads = 256;
-    size_t lds = 0;
-    bool lds_source = false;
-    int effective_source = h->scene_source;
-    int rc = layout_lds<T>(h, p, threads, false, false, lds, lds_source, effective_source);
+    int rc = layout_lds<T>(h, L, threads, false, false);
     if (rc) return rc;
-    const size_t npix = (size_t)p.cold.W * h->local_rows;
-    if ((rc = ensure_buffer(h, &h->guide_nd, &h->guide_nd_bytes, npix * 4 * sizeof(T)))) return rc;
-    if ((rc = ensure_buffer(h, &h->guide_alb, &h->guide_alb_bytes, npix * 4 * sizeof(T)))) return rc;
-    const void* k = lds_source ? (const void*)guide_kernel<T, RTIOW_SCENE_LDS> : (const void*)guide_kernel<T, RTIOW_SCENE_SCALAR>;
-    if (lds > 64 * 1024) HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int tiles = ((p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
-    const dim3 grid((unsigned)((tiles + 3) / 4));
-    if (lds_source) hipLaunchKernelGGL((guide_kernel<T, RTIOW_SCENE_LDS>), grid, dim3(threads), lds, h->stream, p, (T*)h->guide_nd, (T*)h->guide_alb);
-    else hipLaunchKernelGGL((guide_kernel<T, RTIOW_SCENE_SCALAR>), grid, dim3(threads), lds, h->stream, p, (T*)h->guide_nd, (T*)h->guide_alb);
+    const size_t npix = local_pixels(h);
+    HIP_TRY(h, h->guide_nd.ensure(npix * 4 * sizeof(T)));
+    HIP_TRY(h, h->guide_alb.ensure(npix * 4 * sizeof(T)));
+    const auto k = by_source(L.lds_source, [](auto src) { return guide_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, L.lds));
+    const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
+    hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_nd.as<T>(), h->guide_alb.as<T>());
     HIP_TRY(h, hipGetLastError());
     h->guides_ok = true;
     return 0;
@@ -597,12 +549,11 @@ inline void accumulation_source(const rtiow_handle_s* h, const unsigned char*& m
 // The linear image of the accumulation into h->linear (rtiow_read_linear).  The caller has checked that a chunk has run.
 template <class T>
 int launch_linear(rtiow_handle_s* h) {
-    const size_t npix = (size_t)img_w(h) * h->local_rows;
-    int rc = ensure_buffer(h, &h->linear, &h->linear_bytes, npix * 3 * sizeof(T));
-    if (rc) return rc;
+    const size_t npix = local_pixels(h);
+    HIP_TRY(h, h->linear.ensure(npix * 3 * sizeof(T)));
     const unsigned char* mid; const int32_t* counts; int n_uniform;
     accumulation_source(h, mid, counts, n_uniform);
-    hipLaunchKernelGGL(linear_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, npix, mid, counts, n_uniform, (T*)h->linear);
+    hipLaunchKernelGGL(linear_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, npix, mid, counts, n_uniform, h->linear.as<T>());
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -615,10 +566,8 @@ template <class T>
 int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
     const int W = img_w(h), rows = h->local_rows;
     const size_t npix = (size_t)W * rows;
-    int rc = ensure_buffer(h, &h->denoised, &h->denoised_bytes, npix * 3 * sizeof(T));
-    if (rc) return rc;
-    for (int b = 0; b < 2 && b < levels - 1; ++b)
-        if ((rc = ensure_buffer(h, &h->dn_tmp[b], &h->dn_tmp_bytes[b], npix * 3 * sizeof(T)))) return rc;
+    HIP_TRY(h, h->denoised.ensure(npix * 3 * sizeof(T)));
+    for (int b = 0; b < 2 && b < levels - 1; ++b) HIP_TRY(h, h->dn_tmp[b].ensure(npix * 3 * sizeof(T)));
     const unsigned char* mid; const int32_t* counts; int n_uniform;
     accumulation_source(h, mid, counts, n_uniform);
     const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
@@ -627,10 +576,10 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
         fw.ic = (T)(inv2[0] * std::ldexp(1.0, 2 * k));
         fw.in = (T)inv2[1]; fw.ia = (T)inv2[2]; fw.iz = (T)inv2[3];
         const bool last = k == levels - 1;
-        const T* cin = k == 0 ? nullptr : (const T*)h->dn_tmp[(k - 1) & 1];
-        T* cout = last ? (T*)h->denoised : (T*)h->dn_tmp[k & 1];
+        const T* cin = k == 0 ? nullptr : h->dn_tmp[(k - 1) & 1].as<const T>();
+        T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
         hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
-                           counts, n_uniform, cin, (const T*)h->guide_nd, (const T*)h->guide_alb, cout, last ? 1 : 0);
+                           counts, n_uniform, cin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
     h->denoised_ok = true;

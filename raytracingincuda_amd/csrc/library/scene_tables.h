@@ -38,10 +38,10 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
     for (int i = 0; i < n; ++i)
         if (!valid || valid[i]) for (int k = 0; k < 4; ++k) h->host_cr.push_back((double)cr[4 * i + k]);
     h->screen_dirty = true;
-    void** bufs[] = {&h->geom_a, &h->shade_tbl};
-    for (void** b : bufs) if (*b) { HIP_TRY(h, hipFree(*b)); *b = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->geom_a, sizeof(T) * 4 * mp));
-    HIP_TRY(h, hipMalloc(&h->shade_tbl, sizeof(T) * 12 * m));
+    HIP_TRY(h, h->geom_a.reset());
+    HIP_TRY(h, h->shade_tbl.reset());
+    HIP_TRY(h, h->geom_a.ensure(sizeof(T) * 4 * mp));
+    HIP_TRY(h, h->shade_tbl.ensure(sizeof(T) * 12 * m));
     HIP_TRY(h, hipMemcpy(h->geom_a, ga.data(), sizeof(T) * 4 * mp, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->shade_tbl, st.data(), sizeof(T) * 12 * m, hipMemcpyHostToDevice));
     h->n = m; h->n_padded = mp;
@@ -90,8 +90,8 @@ int build_screen_table(rtiow_handle_s* h) {
             for (int k = 0; k < 4; ++k) { pi[8 * q + 2 * k] = lin[8 * q + k]; pi[8 * q + 2 * k + 1] = lin[8 * q + 4 + k]; }
         lin.swap(pi);
     }
-    if (h->geom_s) { HIP_TRY(h, hipFree(h->geom_s)); h->geom_s = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->geom_s, lin.size() * sizeof(S)));
+    HIP_TRY(h, h->geom_s.reset());
+    HIP_TRY(h, h->geom_s.ensure(lin.size() * sizeof(S)));
     HIP_TRY(h, hipMemcpy(h->geom_s, lin.data(), lin.size() * sizeof(S), hipMemcpyHostToDevice));
     h->screen_dirty = false;
     return 0;
@@ -213,7 +213,7 @@ template <class T>
 int build_grid_tables(rtiow_handle_s* h) {
     GridParams& g = h->grid;
     g = GridParams{};
-    if (h->grid_blob) { HIP_TRY(h, hipFree(h->grid_blob)); h->grid_blob = nullptr; }
+    HIP_TRY(h, h->grid_blob.reset());
     const int m = h->n;
     const std::vector<double>& cr = h->host_cr;
     const GridPlan best = plan_grid(m, cr, h->ctr);
@@ -261,7 +261,7 @@ int build_grid_tables(rtiow_handle_s* h) {
     if (!aos.empty()) std::memcpy(blob.data() + cells_bytes, aos.data(), aos.size() * sizeof(float));
     std::memcpy(blob.data() + cells_bytes + aos_bytes, dtab.data(), dtab.size() * sizeof(T));
     std::memcpy(blob.data() + cells_bytes + aos_bytes + dtab_bytes, ids.data(), ids.size() * sizeof(int));
-    HIP_TRY(h, hipMalloc(&h->grid_blob, blob.size()));
+    HIP_TRY(h, h->grid_blob.ensure(blob.size()));
     HIP_TRY(h, hipMemcpy(h->grid_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
     h->grid_cells_bytes = (int)cells_bytes; h->grid_aos_bytes = (int)aos_bytes; h->grid_direct_bytes = (int)dtab_bytes; h->grid_ids_bytes = (int)ids_bytes;
     h->grid_direct = nd; h->grid_registered = registered;
@@ -274,14 +274,14 @@ int build_grid_tables(rtiow_handle_s* h) {
     g.rmax2 = (float)(rmax_g * rmax_g * 1.0001);
     g.cmax = (float)(cmax_g * 1.0001);
     g.n_direct_padded = ndp;
-    g.blob = (const unsigned char*)h->grid_blob;
+    g.blob = h->grid_blob;
     g.blob_bytes = (int)blob.size();
     return 0;
 }
 
 template <class T>
 void fill_screen_params(RenderParams<T>& p, const rtiow_handle_s* h) {
-    p.screen.geom_s = (const float*)h->geom_s;
+    p.screen.geom_s = h->geom_s;
     p.use_screen = ((h->scene_source == RTIOW_SCENE_LDS || h->scene_source == RTIOW_SCENE_GRID) && h->geom_s) ? 1 : 0;
     p.screen.ctr_x = (T)h->ctr[0]; p.screen.ctr_y = (T)h->ctr[1]; p.screen.ctr_z = (T)h->ctr[2]; p.screen.omax2 = (T)h->omax2;
 }

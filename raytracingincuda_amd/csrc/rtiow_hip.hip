@@ -114,6 +114,43 @@ static void release_stream(int device, hipStream_t s) {
     std::lock_guard<std::mutex> lock(g_idle_streams_mu);
     g_idle_streams.emplace_back(device, s);
 }
+
+// Preconditions of the calls that render; `call` names the caller in the message.
+int need_scene(rtiow_handle_s* h, const char* call) {
+    if (h->have_camera && h->n != 0) return 0;
+    return fail_arg(h, RTIOW_E_STATE, (std::string(call) + " before rtiow_set_scene/rtiow_set_camera").c_str());
+}
+int need_rng(rtiow_handle_s* h, const char* call) {
+    if (h->rng_ready) return 0;
+    return fail_arg(h, RTIOW_E_STATE, (std::string(call) + " before rtiow_init_rng").c_str());
+}
+
+// What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
+// and (clear_rng: camera, shard) the RNG states.
+void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
+void invalidate_frame(rtiow_handle_s* h, bool clear_rng) {
+    reset_accumulation(h);
+    h->guides_ok = false; h->denoised_ok = false;
+    if (clear_rng) h->rng_ready = false;
+}
+
+// The times a render call on a shard without rows reports.
+void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
+
+// kernel_ms: events around the work enqueued between timed_begin (or a launch that records ev0 itself) and timed_end (NULL: asynchronous,
+// nothing recorded).
+int timed_begin(rtiow_handle_s* h, float* kernel_ms) {
+    h->render_pending = false;                           // the call reuses the start / stop events of rtiow_render_async
+    if (kernel_ms) { *kernel_ms = 0; HIP_TRY(h, hipEventRecord(h->ev0, h->stream)); }
+    return 0;
+}
+int timed_end(rtiow_handle_s* h, float* kernel_ms) {
+    if (!kernel_ms) return 0;
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipEventSynchronize(h->ev1));
+    HIP_TRY(h, hipEventElapsedTime(kernel_ms, h->ev0, h->ev1));
+    return 0;
+}
 }  // namespace
 
 int rtiow_create(int device, int precision, rtiow_handle* out) {
@@ -179,12 +216,7 @@ int rtiow_destroy(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->geom_a, h->shade_tbl, h->geom_s, h->grid_blob, h->cost_rank, h->rng, h->jump, h->work_counter, h->mid, h->slot_of, h->staged,
-                    h->cost, h->order, h->sort_scratch, h->levels, h->rng_low_table, h->acc_mid[0], h->acc_mid[1], h->acc_cost,
-                    h->adapt_counts, h->adapt_err, h->adapt_ctr,
-                    h->guide_nd, h->guide_alb, h->linear, h->dn_tmp[0], h->dn_tmp[1], h->denoised,
-                    h->fb_external ? nullptr : h->fb};
-    for (void* b : bufs) if (b) (void)hipFree(b);
+    if (h->fb && !h->fb_external) (void)hipFree(h->fb);
     if (h->clock_stamps) (void)hipHostFree(h->clock_stamps);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -192,7 +224,7 @@ int rtiow_destroy(rtiow_handle h) {
     if (h->ev_b) (void)hipEventDestroy(h->ev_b);
     if (h->ev_c) (void)hipEventDestroy(h->ev_c);
     if (h->own_stream && h->stream) release_stream(h->device, h->stream);     // synchronised above
-    delete h;
+    delete h;                                                                  // frees the handle's device buffers
     return 0;
 }
 
@@ -212,10 +244,11 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (!h) return RTIOW_E_BADARG;
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
-    h->guides_ok = false; h->denoised_ok = false;
-    if (h->precision == 32) return upload_scene<float>(h, n, (const float*)center_radius, (const float*)albedo_fuzz, (const float*)refraction_index, type, valid);
-    return upload_scene<double>(h, n, (const double*)center_radius, (const double*)albedo_fuzz, (const double*)refraction_index, type, valid);
+    invalidate_frame(h, false);
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        return upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid);
+    });
 }
 
 int rtiow_set_camera(rtiow_handle h, const void* camera) {
@@ -227,9 +260,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->have_camera = true;
     h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
-    h->rng_ready = false;
-    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
-    h->guides_ok = false; h->denoised_ok = false;
+    invalidate_frame(h, true);
     return 0;
 }
 
@@ -237,10 +268,8 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (!h) return RTIOW_E_BADARG;
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
     h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
-    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
-    h->guides_ok = false; h->denoised_ok = false;
     if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
-    h->rng_ready = false;
+    invalidate_frame(h, true);
     return 0;
 }
 
@@ -263,23 +292,19 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_init_rng before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
+    reset_accumulation(h);
     const int W = img_w(h), H = img_h(h);
     int index_bits = 1;                                      // bits of the largest GLOBAL pixel index W*H-1
     while (index_bits < XW_JUMPS && ((uint64_t)W * (uint64_t)H - 1) >> index_bits) ++index_bits;
     if (index_bits < XW_LOW_BITS) index_bits = XW_LOW_BITS;   // xw_low_table_kernel applies the first XW_LOW_BITS matrices whatever the frame size
     if (h->jump_count < index_bits) {                        // 31 squarings for all 32 matrices take 2.4 ms on the host; a 1080p frame needs 21
         std::vector<uint32_t> m = build_sequence_jump_matrices(false, index_bits);
-        if (!h->jump) HIP_TRY(h, hipMalloc((void**)&h->jump, (size_t)XW_JUMPS * XW_MAT_WORDS * sizeof(uint32_t)));
+        HIP_TRY(h, h->jump.ensure((size_t)XW_JUMPS * XW_MAT_WORDS * sizeof(uint32_t)));
         HIP_TRY(h, hipMemcpy(h->jump, m.data(), m.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         h->jump_count = index_bits;
     }
-    const size_t npix = (size_t)W * h->local_rows;
-    if (h->rng_pixels < npix) {
-        if (h->rng) { HIP_TRY(h, hipFree(h->rng)); h->rng = nullptr; h->rng_pixels = 0; }
-        if (npix) HIP_TRY(h, hipMalloc((void**)&h->rng, npix * 6 * sizeof(uint32_t)));
-        h->rng_pixels = npix;
-    }
+    const size_t npix = local_pixels(h);
+    if (npix) HIP_TRY(h, h->rng.ensure(npix * 6 * sizeof(uint32_t)));
     // cuRAND's published seed scrambling for curandStateXORWOW_t (curand_init).
     const uint32_t x0 = (uint32_t)seed ^ 0xaad26b49u, x1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
     const uint32_t t0 = 1099087573u * x0, t1 = 2591861531u * x1;
@@ -290,7 +315,7 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
         const int threads = 256;
         const unsigned blocks = (unsigned)((npix + threads - 1) / threads);
         // J^lo * s0 for the 2^XW_LOW_BITS low parts of a pixel index (once per seed), then every pixel from its entry (device/xorwow.h)
-        if (!h->rng_low_table) HIP_TRY(h, hipMalloc((void**)&h->rng_low_table, sizeof(uint32_t) * XW_WORDS * ((size_t)1 << XW_LOW_BITS)));
+        HIP_TRY(h, h->rng_low_table.ensure(sizeof(uint32_t) * XW_WORDS * ((size_t)1 << XW_LOW_BITS)));
         hipLaunchKernelGGL(xw_low_table_kernel, dim3((1u << XW_LOW_BITS) / 256), dim3(256), 0, h->stream, h->rng_low_table, h->jump, s0, s1, s2, s3, s4);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(rng_init_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->rng, h->jump, (const uint32_t*)h->rng_low_table, d0,
@@ -310,35 +335,31 @@ namespace {
 // First half of rtiow_render: everything up to and including the stop event, nothing that blocks
 // the host (main.cu:334-339 without the synchronisation).
 static int render_begin(rtiow_handle_s* h, int T, bool timed) {
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_set_scene/rtiow_set_camera");
-    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_init_rng");
+    if (int rc = need_scene(h, "rtiow_render")) return rc;
+    if (int rc = need_rng(h, "rtiow_render")) return rc;
     if (T < 0 || T > 32) return fail_arg(h, RTIOW_E_BADARG, "rtiow_render: threads_per_block_row must be 0..32");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;
-    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; return 0; }
+    if (h->local_rows == 0) { zero_times(h); return 0; }
     int bx, by, wave_tiles;
     block_shape(T, h->schedule == RTIOW_SCHED_STATIC, bx, by, wave_tiles);
     // allocations and table builds of a first render happen BEFORE the start event: the reference's
     // timed region holds the kernel only (its buffers are allocated at main.cu:133-134, 301-330)
-    if (h->precision == 32) rc = launch_render<float>(h, h->cam32, bx, by, wave_tiles, nullptr, true);
-    else rc = launch_render<double>(h, h->cam64, bx, by, wave_tiles, nullptr, true);
-    if (rc) return rc;
+    auto render = [&](bool prepare_only) { return by_precision(h, [&](auto t) { return launch_render<decltype(t)>(h, bx, by, wave_tiles, nullptr, prepare_only); }); };
+    if ((rc = render(true))) return rc;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));     // a render that stamps nothing (static schedule) reports no clock, not the last one's
     if (timed && h->warmup_us > 0 && !h->warmed) {        // study knob: the chip's clock ramps under load; this load comes BEFORE the start event
-        hipLaunchKernelGGL(clock_warmup_kernel, dim3((unsigned)h->num_cus * 8u), dim3(256), 0, h->stream, (unsigned long long)h->warmup_us * 100ull, (float*)h->work_counter);
+        hipLaunchKernelGGL(clock_warmup_kernel, dim3((unsigned)h->num_cus * 8u), dim3(256), 0, h->stream, (unsigned long long)h->warmup_us * 100ull, h->work_counter.as<float>());
         HIP_TRY(h, hipGetLastError());
         h->warmed = true;
     }
     if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));                         // main.cu:334
     h->time_phases = timed;
-    if (h->precision == 32) rc = launch_render<float>(h, h->cam32, bx, by, wave_tiles);
-    else rc = launch_render<double>(h, h->cam64, bx, by, wave_tiles);
+    rc = render(false);
     h->time_phases = false;
     if (rc) return rc;
-    const int S = h->precision == 32 ? h->cam32.samples_per_pixel : h->cam64.samples_per_pixel;
-    h->stats.primary_rays = (uint64_t)h->local_rows * img_w(h) * (uint64_t)S;
     if (timed) { HIP_TRY(h, hipEventRecord(h->ev1, h->stream)); h->render_pending = true; }   // main.cu:339
     return 0;
 }
@@ -387,15 +408,15 @@ int rtiow_render_wait(rtiow_handle h, float* kernel_ms) {
 
 int rtiow_accumulate_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
-    h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE;
+    reset_accumulation(h);
     return 0;
 }
 
 int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     (void)threads_per_block_row;                         // chunks always run through the persistent hand-out
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_set_scene/rtiow_set_camera");
-    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_render before rtiow_init_rng");
+    if (int rc = need_scene(h, "rtiow_accumulate")) return rc;
+    if (int rc = need_rng(h, "rtiow_accumulate")) return rc;
     if (samples <= 0 || samples > 0x7fffffff - h->acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
     if (h->acc_mode == ACC_MODE_ADAPTIVE) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate after rtiow_accumulate_adaptive: reset the accumulation first");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -403,22 +424,16 @@ int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, flo
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
     if (kernel_ms) *kernel_ms = 0;
-    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->acc_samples += samples; h->acc_mode = ACC_MODE_PLAIN; return 0; }
+    if (h->local_rows == 0) { zero_times(h); h->acc_samples += samples; h->acc_mode = ACC_MODE_PLAIN; return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
-    if (h->precision == 32) rc = launch_accumulate<float>(h, h->cam32, samples, timed);
-    else rc = launch_accumulate<double>(h, h->cam64, samples, timed);
-    if (rc) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_accumulate<decltype(t)>(h, samples, timed); }))) return rc;
     h->acc_samples += samples;
     h->acc_mode = ACC_MODE_PLAIN;
     h->stats.prepass_ms = 0; h->stats.place_ms = 0;
-    if (timed) {
-        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(h, hipEventSynchronize(h->ev1));
-        float ms = 0;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        *kernel_ms = ms;
-        h->stats.render_ms = ms; h->stats.main_ms = ms;
+    if (timed) {                                         // the start event: launch_accumulate, behind its allocations
+        if ((rc = timed_end(h, kernel_ms))) return rc;
+        h->stats.render_ms = *kernel_ms; h->stats.main_ms = *kernel_ms;
     }
     return 0;
 }
@@ -443,22 +458,21 @@ int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, doub
     if (!h) return RTIOW_E_BADARG;
     if (active_pixels) *active_pixels = 0;
     if (kernel_ms) *kernel_ms = 0;
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive before rtiow_set_scene/rtiow_set_camera");
-    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive before rtiow_init_rng");
+    if (int rc = need_scene(h, "rtiow_accumulate_adaptive")) return rc;
+    if (int rc = need_rng(h, "rtiow_accumulate_adaptive")) return rc;
     if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
         return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
-    if (img_w(h) >= 65536 || h->local_rows >= 32768) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
+    if (!order_fits(h)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
     if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the events of rtiow_render_async
-    if (h->local_rows == 0) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; h->stats.primary_rays = 0; h->acc_mode = ACC_MODE_ADAPTIVE; return 0; }
+    if (h->local_rows == 0) { zero_times(h); h->stats.primary_rays = 0; h->acc_mode = ACC_MODE_ADAPTIVE; return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
     int active = 0;
-    if (h->precision == 32) rc = launch_adaptive<float>(h, h->cam32, samples, min_samples, rel_error, max_samples, timed, active);
-    else rc = launch_adaptive<double>(h, h->cam64, samples, min_samples, rel_error, max_samples, timed, active);
+    rc = by_precision(h, [&](auto t) { return launch_adaptive<decltype(t)>(h, samples, min_samples, rel_error, max_samples, timed, active); });
     if (rc) return rc;
     h->acc_mode = ACC_MODE_ADAPTIVE;
     if (active_pixels) *active_pixels = active;
@@ -478,7 +492,7 @@ int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, doub
 int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_adaptive_state before rtiow_set_camera");
-    const size_t want = (size_t)img_w(h) * (size_t)h->local_rows;
+    const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_adaptive_state: npix must be local_rows x width");
     if (h->acc_mode != ACC_MODE_ADAPTIVE || want == 0) {  // no adaptive chunk since the reset: n = 0, err = +inf
         for (size_t k = 0; k < want; ++k) { if (counts) counts[k] = 0; if (rel_err) rel_err[k] = HUGE_VALF; }
@@ -493,21 +507,8 @@ int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, s
 
 // ---- Denoised previews
 namespace {
-// kernel_ms: events around the work enqueued between timed_begin and timed_end (NULL: asynchronous, nothing recorded).
-int timed_begin(rtiow_handle_s* h, float* kernel_ms) {
-    h->render_pending = false;                           // the call reuses the start / stop events of rtiow_render_async
-    if (kernel_ms) { *kernel_ms = 0; HIP_TRY(h, hipEventRecord(h->ev0, h->stream)); }
-    return 0;
-}
-int timed_end(rtiow_handle_s* h, float* kernel_ms) {
-    if (!kernel_ms) return 0;
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(h->ev1));
-    HIP_TRY(h, hipEventElapsedTime(kernel_ms, h->ev0, h->ev1));
-    return 0;
-}
 int render_guides(rtiow_handle_s* h) {
-    return h->precision == 32 ? launch_guides<float>(h, h->cam32) : launch_guides<double>(h, h->cam64);
+    return by_precision(h, [&](auto t) { return launch_guides<decltype(t)>(h); });
 }
 // D2H copy of `bytes` from a device buffer on the handle's stream, then wait.
 int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
@@ -521,19 +522,18 @@ int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
 int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_linear: no chunk since the last reset");
-    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    const size_t need = image_bytes(h);
     if (bytes != need || (need && !host_rgb)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_linear: bytes must be local_rows x width x 3 x sizeof(T)");
     if (need == 0) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = h->precision == 32 ? launch_linear<float>(h) : launch_linear<double>(h);
-    if (rc) return rc;
+    if (int rc = by_precision(h, [&](auto t) { return launch_linear<decltype(t)>(h); })) return rc;
     return copy_out(h, host_rgb, h->linear, need);
 }
 
 int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_render_guides before rtiow_set_scene/rtiow_set_camera");
+    if (int rc = need_scene(h, "rtiow_render_guides")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->local_rows == 0) { h->guides_ok = true; return 0; }
     int rc = timed_begin(h, kernel_ms);
@@ -545,7 +545,7 @@ int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
 int rtiow_read_guides(rtiow_handle h, void* normal, void* albedo, void* depth, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera || !h->guides_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_guides: no guides for the current scene, camera and shard (rtiow_render_guides)");
-    const size_t want = (size_t)img_w(h) * (size_t)h->local_rows;
+    const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_guides: npix must be local_rows x width");
     if (want == 0 || (!normal && !albedo && !depth)) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -576,15 +576,14 @@ int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_n
     int rc = timed_begin(h, kernel_ms);
     if (rc) return rc;
     if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    rc = h->precision == 32 ? launch_denoise<float>(h, levels, inv2) : launch_denoise<double>(h, levels, inv2);
-    if (rc) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2); }))) return rc;
     return timed_end(h, kernel_ms);
 }
 
 int rtiow_read_denoised(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h) return RTIOW_E_BADARG;
     if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_denoised before rtiow_denoise");
-    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    const size_t need = image_bytes(h);
     if (bytes != need || !host_rgb) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_denoised: bytes must be local_rows x width x 3 x sizeof(T)");
     HIP_TRY(h, hipSetDevice(h->device));
     return copy_out(h, host_rgb, h->denoised, need);
@@ -594,7 +593,7 @@ int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) 
     if (!h || !device_ptr || !bytes) return RTIOW_E_BADARG;
     if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoised_device_ptr before rtiow_denoise");
     *device_ptr = h->denoised;
-    *bytes = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    *bytes = image_bytes(h);
     return 0;
 }
 
@@ -612,8 +611,8 @@ int rtiow_device(rtiow_handle h, int* device) {
 
 int rtiow_count_segments(rtiow_handle h, int threads_per_block_row, uint64_t* segments) {
     if (!h || !segments) return RTIOW_E_BADARG;
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_count_segments before rtiow_set_scene/rtiow_set_camera");
-    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_count_segments before rtiow_init_rng");
+    if (int rc = need_scene(h, "rtiow_count_segments")) return rc;
+    if (int rc = need_rng(h, "rtiow_count_segments")) return rc;
     const int T = threads_per_block_row;
     if (T < 0 || T > 32) return fail_arg(h, RTIOW_E_BADARG, "rtiow_count_segments: threads_per_block_row must be 0..32");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -621,16 +620,14 @@ int rtiow_count_segments(rtiow_handle h, int threads_per_block_row, uint64_t* se
     if (rc) return rc;
     *segments = 0;
     if (h->local_rows == 0) return 0;
-    DeviceScratch d;                                     // segments of [0] the prepass launch, [1] the main (or only) launch; [2], [3] their longest per-pixel chains; freed on every return path
-    HIP_TRY(h, d.alloc(4 * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemsetAsync(d.ptr, 0, 4 * sizeof(unsigned long long), h->stream));
+    DeviceBuffer<unsigned long long> d;                  // segments of [0] the prepass launch, [1] the main (or only) launch; [2], [3] their longest per-pixel chains; freed on every return path
+    HIP_TRY(h, d.ensure(4 * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), h->stream));
     int bx, by, wave_tiles;
     block_shape(T, h->schedule == RTIOW_SCHED_STATIC, bx, by, wave_tiles);
-    if (h->precision == 32) rc = launch_render<float>(h, h->cam32, bx, by, wave_tiles, (unsigned long long*)d.ptr);
-    else rc = launch_render<double>(h, h->cam64, bx, by, wave_tiles, (unsigned long long*)d.ptr);
-    if (rc) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_render<decltype(t)>(h, bx, by, wave_tiles, d); }))) return rc;
     unsigned long long host[4] = {0, 0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(host, d.ptr, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(host, d, sizeof host, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *segments = host[0] + host[1];
     h->stats.segments_prepass = host[0]; h->stats.segments_main = host[1];
@@ -653,14 +650,14 @@ int rtiow_framebuffer_device_ptr(rtiow_handle h, void** device_ptr, size_t* byte
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     *device_ptr = h->fb;
-    if (bytes) *bytes = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    if (bytes) *bytes = image_bytes(h);
     return 0;
 }
 
 int rtiow_read_framebuffer(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h || !host_rgb) return RTIOW_E_BADARG;
     if (!h->have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_framebuffer before rtiow_render");
-    const size_t need = (size_t)h->local_rows * img_w(h) * 3 * elem_size(h);
+    const size_t need = image_bytes(h);
     if (bytes < need) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_framebuffer: host buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -671,19 +668,20 @@ int rtiow_read_framebuffer(rtiow_handle h, void* host_rgb, size_t bytes) {
 int rtiow_read_levels(rtiow_handle h, unsigned char* host_levels, size_t bytes, uint64_t* nan_channels) {
     if (!h || !host_levels || !nan_channels) return RTIOW_E_BADARG;
     if (!h->have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_levels before rtiow_render");
-    const size_t n = (size_t)h->local_rows * img_w(h) * 3;
+    const size_t n = local_pixels(h) * 3;
     if (bytes < n) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_levels: host buffer too small");
     *nan_channels = 0;
     if (n == 0) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t padded = (n + 255) / 256 * 256;
-    int rc = ensure_buffer(h, &h->levels, &h->levels_bytes, padded + 256);
-    if (rc) return rc;
+    HIP_TRY(h, h->levels.ensure(padded + 256));
     unsigned long long* counter = reinterpret_cast<unsigned long long*>(h->levels + padded);
     HIP_TRY(h, hipMemsetAsync(counter, 0, sizeof(unsigned long long), h->stream));
     const unsigned blocks = (unsigned)(((n + 3) / 4 + 255) / 256);
-    if (h->precision == 32) hipLaunchKernelGGL(quantise_kernel<float>, dim3(blocks), dim3(256), 0, h->stream, (const float*)h->fb, h->levels, n, counter);
-    else hipLaunchKernelGGL(quantise_kernel<double>, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->fb, h->levels, n, counter);
+    by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(quantise_kernel<T>, dim3(blocks), dim3(256), 0, h->stream, (const T*)h->fb, h->levels, n, counter);
+    });
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     // one blocking copy of levels + counter (pageable destination, like rtiow_read_framebuffer)
@@ -736,7 +734,7 @@ int rtiow_synchronize(rtiow_handle h) {
 int rtiow_debug_read_rng(rtiow_handle h, uint32_t* host_states, size_t count_words) {
     if (!h || !host_states) return RTIOW_E_BADARG;
     if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_rng before rtiow_init_rng");
-    const size_t npix = (size_t)img_w(h) * h->local_rows;
+    const size_t npix = local_pixels(h);
     if (count_words < npix * 6) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_rng: buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
     std::vector<uint32_t> soa(npix * 6);
@@ -748,7 +746,7 @@ int rtiow_debug_read_rng(rtiow_handle h, uint32_t* host_states, size_t count_wor
 
 int rtiow_debug_read_costs(rtiow_handle h, uint32_t* own, uint32_t* smoothed, size_t count) {
     if (!h || !own || !smoothed) return RTIOW_E_BADARG;
-    const size_t npix = (size_t)img_w(h) * h->local_rows;
+    const size_t npix = local_pixels(h);
     if (h->stats.phases != 2 || !h->cost || !h->cost_rank) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_costs: the last render did not sort");
     if (count < npix) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_costs: buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -765,10 +763,10 @@ int rtiow_debug_timeline(rtiow_handle h, int threads_per_block_row, uint64_t* ou
     // a persistent launch never has more waves than the device holds (32 per CU); launch_render
     // hands the buffer to the kernel only when it holds every wave of the launch
     const size_t max_waves = (size_t)h->num_cus * 32;
-    DeviceScratch buf;
-    HIP_TRY(h, buf.alloc(max_waves * 8 * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemset(buf.ptr, 0, max_waves * 8 * sizeof(unsigned long long)));
-    h->timeline = (unsigned long long*)buf.ptr;
+    DeviceBuffer<unsigned long long> buf;
+    HIP_TRY(h, buf.ensure(max_waves * 8 * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemset(buf, 0, max_waves * 8 * sizeof(unsigned long long)));
+    h->timeline = buf;
     h->timeline_cap_waves = max_waves;
     uint64_t seg = 0;
     int rc = rtiow_count_segments(h, threads_per_block_row, &seg);
@@ -780,7 +778,7 @@ int rtiow_debug_timeline(rtiow_handle h, int threads_per_block_row, uint64_t* ou
     if (nw > max_waves) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_timeline: launch larger than the timeline buffer");
     *waves = (int)nw;
     const size_t words = nw * 8 < cap_words ? nw * 8 : cap_words;
-    HIP_TRY(h, hipMemcpy(out_words, buf.ptr, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out_words, buf, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -792,38 +790,33 @@ int rtiow_debug_pixel_times(rtiow_handle h, int threads_per_block_row, uint32_t*
     if (h->schedule == RTIOW_SCHED_STATIC) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times needs a persistent schedule");
     if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t words = (size_t)h->local_rows * img_w(h) * 4;
+    const size_t words = local_pixels(h) * 4;
     if (cap_words < words) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_pixel_times: buffer too small");
-    DeviceScratch buf;
-    HIP_TRY(h, buf.alloc(words * sizeof(uint32_t)));
-    HIP_TRY(h, hipMemset(buf.ptr, 0, words * sizeof(uint32_t)));
-    h->pixel_times = (uint32_t*)buf.ptr;
+    DeviceBuffer<uint32_t> buf;
+    HIP_TRY(h, buf.ensure(words * sizeof(uint32_t)));
+    HIP_TRY(h, hipMemset(buf, 0, words * sizeof(uint32_t)));
+    h->pixel_times = buf;
     uint64_t seg = 0;
     const int rc = rtiow_count_segments(h, threads_per_block_row, &seg);
     h->pixel_times = nullptr;
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(out_words, buf.ptr, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out_words, buf, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int rtiow_debug_hit_world(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out) {
     if (!h || n <= 0 || !rays || !t_out || !index_out) return RTIOW_E_BADARG;
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_hit_world before rtiow_set_scene/rtiow_set_camera");
+    if (int rc = need_scene(h, "rtiow_debug_hit_world")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h);
-    DeviceScratch dr, dt, di;
-    HIP_TRY(h, dr.alloc((size_t)n * 6 * es)); HIP_TRY(h, dt.alloc((size_t)n * es)); HIP_TRY(h, di.alloc((size_t)n * sizeof(int)));
-    HIP_TRY(h, hipMemcpy(dr.ptr, rays, (size_t)n * 6 * es, hipMemcpyHostToDevice));
-    h->probe_n = n; h->probe_rays = dr.ptr; h->probe_t = dt.ptr; h->probe_idx = (int*)di.ptr;
-    const int saved_schedule = h->schedule;
-    h->schedule = RTIOW_SCHED_PERSISTENT;                    // table layout of the dynamic schedules (four-wave workgroups)
-    int rc = h->precision == 32 ? launch_render<float>(h, h->cam32, 16, 16, 1) : launch_render<double>(h, h->cam64, 16, 16, 1);
-    h->schedule = saved_schedule;
-    h->probe_n = 0; h->probe_rays = nullptr; h->probe_t = nullptr; h->probe_idx = nullptr;
-    if (rc) return rc;
+    DeviceBuffer<> dr, dt;
+    DeviceBuffer<int> di;
+    HIP_TRY(h, dr.ensure((size_t)n * 6 * es)); HIP_TRY(h, dt.ensure((size_t)n * es)); HIP_TRY(h, di.ensure((size_t)n * sizeof(int)));
+    HIP_TRY(h, hipMemcpy(dr, rays, (size_t)n * 6 * es, hipMemcpyHostToDevice));
+    if (int rc = by_precision(h, [&](auto t) { using T = decltype(t); return launch_probe<T>(h, n, dr.as<const T>(), dt.as<T>(), di); })) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(t_out, dt.ptr, (size_t)n * es, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(index_out, di.ptr, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(t_out, dt, (size_t)n * es, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(index_out, di, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -851,15 +844,16 @@ int rtiow_debug_ops(rtiow_handle h, int op, size_t n, const void* a, const void*
     if (!h || !a || !out || n == 0) return RTIOW_E_BADARG;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h), bytes = n * es;
-    DeviceScratch sa, sb, sc, sout;
-    HIP_TRY(h, sa.alloc(bytes)); HIP_TRY(h, sb.alloc(bytes)); HIP_TRY(h, sc.alloc(bytes)); HIP_TRY(h, sout.alloc(bytes));
-    void *da = sa.ptr, *db = sb.ptr, *dc = sc.ptr, *dout = sout.ptr;
+    DeviceBuffer<> da, db, dc, dout;
+    HIP_TRY(h, da.ensure(bytes)); HIP_TRY(h, db.ensure(bytes)); HIP_TRY(h, dc.ensure(bytes)); HIP_TRY(h, dout.ensure(bytes));
     HIP_TRY(h, hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(db, b ? b : a, bytes, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(dc, c ? c : a, bytes, hipMemcpyHostToDevice));
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (h->precision == 32) hipLaunchKernelGGL(debug_ops_kernel<float>, dim3(blocks), dim3(256), 0, h->stream, op, n, (const float*)da, (const float*)db, (const float*)dc, (float*)dout);
-    else hipLaunchKernelGGL(debug_ops_kernel<double>, dim3(blocks), dim3(256), 0, h->stream, op, n, (const double*)da, (const double*)db, (const double*)dc, (double*)dout);
+    by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(debug_ops_kernel<T>, dim3(blocks), dim3(256), 0, h->stream, op, n, da.as<const T>(), db.as<const T>(), dc.as<const T>(), dout.as<T>());
+    });
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));

@@ -1,12 +1,13 @@
-"""Compare the device code of the existing render kernels between two builds.
+"""Compare the device code of every kernel between two builds.
 
     python scripts/isa_diff_render_kernels.py --ref HEAD~1        # the tree at a git ref (exported with git archive) against the working tree
     python scripts/isa_diff_render_kernels.py BEFORE.s AFTER.s    # two `hipcc -S --cuda-device-only` listings
 
-Every instantiation of render_kernel, render_persistent_kernel, render_prepass_kernel, render_solo_kernel, render_accumulate_kernel,
-render_adaptive_kernel, adaptive_select_kernel and adaptive_finish_kernel
-is cut from its label to its .Lfunc_end and compared text for text.  This shows that a change confined to new kernels (e.g. the ACCUM
-or ADAPT flag of persistent_body) leaves the existing ones as they were.  A kernel the older build lacks is listed as new.  Exit status 1 if any of them differ or is missing.
+Every function of the older listing is cut from its label to its .Lfunc_end and compared text for text with the newer one's, after the
+function-local labels (.LBB<n>_<k>, .Lfunc_end<n>: n follows the order in which the module instantiates the functions) are renumbered
+in order of appearance and the comments dropped, so that host code naming the kernels in another order does not count as a change.  This shows that a change
+confined to host code or to new kernels (e.g. the ACCUM or ADAPT flag of persistent_body) leaves the existing device code as it was.  A
+kernel the older build lacks is listed as new.  Exit status 1 if any of them differ or is missing.
 """
 import argparse
 import os
@@ -18,8 +19,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-EXISTING = ("render_kernel<", "render_persistent_kernel<", "render_prepass_kernel<", "render_solo_kernel<", "render_accumulate_kernel<",
-            "render_adaptive_kernel<", "adaptive_select_kernel<", "adaptive_finish_kernel<")
+LABEL = re.compile(r"\.L[A-Za-z_]+\d+(?:_\d+)*")
 
 
 def listing(src_root, out):
@@ -30,11 +30,18 @@ def listing(src_root, out):
     return out
 
 
+def normalised(body):
+    seen = {}
+    body = re.sub(r"[ \t]*;.*$", "", body, flags=re.M)        # assembler comments (they name blocks by their numbers too)
+    return LABEL.sub(lambda m: seen.setdefault(m.group(0), ".L#%d" % len(seen)), body)
+
+
 def bodies(path):
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_Z\S+):", text, re.M):
-        out[m.group(1)] = text[m.start():text.index(".Lfunc_end", m.end())]
+    for name in re.findall(r"^\s*\.type\s+([^,\s]+),@function", text, re.M):
+        m = re.search(r"^%s:" % re.escape(name), text, re.M)
+        out[name] = normalised(text[m.start():text.index(".Lfunc_end", m.end())])
     return out
 
 
@@ -58,15 +65,14 @@ def main():
         old, new = bodies(before), bodies(after)
     names = sorted(old)
     dem = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()))
-    kept = [n for n in names if any(k in dem[n] for k in EXISTING)]
-    diff = [dem[n] for n in kept if old[n] != new.get(n)]
-    print("existing render kernels compared: %d, differing or missing: %d" % (len(kept), len(diff)))
+    diff = [dem[n] for n in names if old[n] != new.get(n)]
+    print("kernels compared: %d, differing or missing: %d" % (len(names), len(diff)))
     for d in diff:
         print("  DIFF", d)
     added = [n for n in new if n not in old]
     for d in subprocess.run(["c++filt"], input="\n".join(added), capture_output=True, text=True, check=True).stdout.splitlines():
         print("  new", d)
-    return 1 if diff or not kept else 0
+    return 1 if diff or not names else 0
 
 
 if __name__ == "__main__":

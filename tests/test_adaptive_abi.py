@@ -49,19 +49,9 @@ def test_bad_arguments_need_no_gpu(native):
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory, native):
-    from raytracingincuda_amd import build as b
-    out = str(tmp_path_factory.mktemp("isa_adapt") / "rtiow_hip.s")
-    flags = [f for f in b.HIP_FLAGS if f not in ("-shared",)]
-    subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(b.CSRC, "rtiow_hip.hip")],
-                   check=True, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    pat = re.compile(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+(\d+)\n\s+\.sgpr_spill_count:\s+(\d+)\n"
-                     r"(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)")
-    found = list(pat.finditer(text))
-    names = subprocess.run(["c++filt"], input="\n".join(m.group(1) for m in found), capture_output=True, text=True, check=True).stdout.splitlines()
-    return {name: {"scratch": int(m.group(2)), "sgpr": int(m.group(3)), "sgpr_spill": int(m.group(4)), "vgpr": int(m.group(5)), "vgpr_spill": int(m.group(6))}
-            for m, name in zip(found, names)}
+def metadata(native):
+    from raytracingincuda_amd.kernel_metadata import device_metadata
+    return device_metadata()[0]
 
 
 def _one(meta, part):
