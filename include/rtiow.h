@@ -278,6 +278,34 @@ int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_n
 int rtiow_read_denoised(rtiow_handle h, void* host_rgb, size_t bytes);
 int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
 
+/* ---- Variance-guided denoising: the colour edge-stop of the filter follows the noise each pixel measured.
+ * Both calls need the second moment s2 that only adaptive chunks keep: after plain chunks, and with no chunk since the last reset, they
+ * return RTIOW_E_STATE.  (rtiow_accumulate_adaptive(h, k, INT32_MAX, 0.0, INT32_MAX, ...) samples uniformly and keeps s2; its preview
+ * is rtiow_accumulate's bit for bit.)
+ *
+ * rtiow_read_variance copies V_p, the estimated variance of the pixel's MEAN luminance, one T per local pixel (npix = local_rows x
+ * width, else RTIOW_E_BADARG).  With n = n_p, the colour sum acc and s2 as stored, in double and in this order -- the expressions of
+ * err_p above --: m = Y(acc) / n, var = max(0, (s2 - n m^2) / (n - 1)), V_p = (T)(var / n); V_p = 0 for n_p < 2 (no estimate).
+ * sqrt(var / n) / (m + 1e-3) is err_p.  Works on shards.
+ *
+ * rtiow_denoise_variance filters the linear colour C^0 = c of the accumulation (rtiow_read_linear) together with V^0 = V.  Frame,
+ * taps, tap order, kern, the guide terms en, ea, ez with i_n, i_a, i_z, the skipping of taps outside the frame, the gamma of the last
+ * level, `levels`, stale guides, kernel_ms and the refusal of shards are rtiow_denoise's; everything in T, left to right as written,
+ * plain * + - /.  Level k, step s = 1 << k, gives every pixel p:
+ *   g_p = (sum b V^k_q) / (sum b) over q = p + (dx, dy), dy then dx in -1..1 (step 1 at every level), b = B[dx+1] B[dy+1],
+ *         B = {1/4, 1/2, 1/4}, those outside the frame skipped, sums from 0;
+ *   i_p = f_k / (sv2 g_p + eps), sv2 = (T)(sigma_variance^2) (the square in double), f_k = (T)(4^k), eps = (T)1e-8;
+ *   per tap q = p + (dx s, dy s), dy then dx in -2..2:  ec = (d.x d.x + d.y d.y) + d.z d.z with d = C^k_q - C^k_p,
+ *         e = ((ec i_p + en i_n) + ea i_a) + ez i_z,  w = kern / (1 + e),  S = S + w C^k_q,  W = W + w,  U = U + (w w) V^k_q;
+ *   C^(k+1)_p = S / W per channel,  V^(k+1)_p = U / (W W).
+ * sigma_variance = +inf turns the colour term off: i_p = 0 by definition (decided on the host, also when sv2 is not finite in T); the
+ * colour output is then rtiow_denoise's with sigma_color = +inf.  The output goes to the buffer rtiow_denoise writes:
+ * rtiow_read_denoised and rtiow_denoised_device_ptr return the image of whichever of the two calls ran last.
+ * RTIOW_E_BADARG: levels outside 1..8, a sigma <= 0 or NaN.  RTIOW_E_STATE: as said above, or a sharded handle.  The framebuffer,
+ * the accumulation, its counts and errors and the next chunk's bits are untouched.  Not available on groups. */
+int rtiow_read_variance(rtiow_handle h, void* host_var /* npix T */, size_t npix);
+int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -92,6 +92,7 @@ HIP_SYMBOLS = [
     "rtiow_render_async", "rtiow_render_wait", "rtiow_stream", "rtiow_device",
     "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples", "rtiow_accumulate_adaptive", "rtiow_read_adaptive_state",
     "rtiow_read_linear", "rtiow_render_guides", "rtiow_read_guides", "rtiow_denoise", "rtiow_read_denoised", "rtiow_denoised_device_ptr",
+    "rtiow_read_variance", "rtiow_denoise_variance",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -199,6 +200,8 @@ def load_hip_library(debug=False):
         lib.rtiow_denoise.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_read_denoised.argtypes = [H, vp, ctypes.c_size_t]
         lib.rtiow_denoised_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        lib.rtiow_read_variance.argtypes = [H, vp, ctypes.c_size_t]
+        lib.rtiow_denoise_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -373,6 +376,10 @@ DENOISE_SIGMA_COLOR = 0.1
 DENOISE_SIGMA_NORMAL = 0.1
 DENOISE_SIGMA_ALBEDO = 0.2
 DENOISE_SIGMA_DEPTH = 0.05
+# Renderer.denoise_variance default: the best of scripts/denoise_variance_probe.py --sweep, i.e. the smallest worst case over 4, 16 and
+# 64 uniform samples of the worse-of-two-scenes ratio q_var / q_fixed, q = MSE ratio as above, q_fixed from denoise() at its defaults
+# (profiles/denoise_variance/denoise_variance_probe.json).  Dimensionless: a tolerance in standard deviations.
+DENOISE_SIGMA_VARIANCE = 4.5
 
 
 class Renderer:
@@ -525,6 +532,13 @@ class Renderer:
                                                         None, ctypes.byref(active)))
         return None, active.value
 
+    def accumulate_with_variance(self, samples, sync=True):
+        """Uniform sampling that keeps the second moment variance() and denoise_variance() need: an adaptive chunk in which every pixel
+        is active (min_samples and max_samples at their largest, rel_error 0).  The preview is accumulate()'s bit for bit; the chunk costs
+        a few per cent more than a plain one plus the select and finish passes and, like every adaptive
+        chunk, is not ranked by cost.  Returns the kernel ms (None when sync=False)."""
+        return self.accumulate_adaptive(samples, 0.0, min_samples=2 ** 31 - 1, max_samples=2 ** 31 - 1, sync=sync)[0]
+
     def adaptive_state(self):
         """(counts, rel_err): each pixel's sample count (int32) and relative standard error of its mean luminance (float32, +inf below
         two samples), local_rows x width."""
@@ -577,6 +591,23 @@ class Renderer:
         self._check(self._lib.rtiow_denoise(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
                                             float(sigma_depth), ctypes.byref(ms)))
         return self.read_denoised()
+
+    def variance(self):
+        """The estimated variance of each pixel's mean luminance, [local_rows, W] (0 below two samples), from the second moment an
+        adaptive accumulation keeps: adaptive_state()'s rel_err is sqrt(variance) / (mean luminance + 1e-3)."""
+        out = np.empty((self.local_rows, self.width), self.dtype)
+        self._check(self._lib.rtiow_read_variance(self._h, out.ctypes.data if out.size else None, out.shape[0] * out.shape[1]))
+        return out
+
+    def denoise_variance(self, levels=DENOISE_LEVELS, sigma_variance=DENOISE_SIGMA_VARIANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
+                         sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, sync=True):
+        """Variance-guided a-trous filter of an adaptive accumulation: denoise() with the colour edge-stop
+        of every pixel set by its measured variance(), sigma_variance standard deviations wide, so it follows the noise as samples
+        accumulate.  Needs accumulate_adaptive() or accumulate_with_variance() chunks.  Returns and stores its image like denoise()."""
+        ms = None if not sync else ctypes.c_float(0)
+        self._check(self._lib.rtiow_denoise_variance(self._h, int(levels), float(sigma_variance), float(sigma_normal), float(sigma_albedo),
+                                                     float(sigma_depth), ctypes.byref(ms) if sync else None))
+        return self.read_denoised() if sync else None
 
     def read_denoised(self):
         out = np.empty((self.local_rows, self.width, 3), self.dtype)

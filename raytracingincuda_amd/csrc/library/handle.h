@@ -106,6 +106,10 @@ struct rtiow_handle_s {
     DeviceBuffer<> dn_tmp[2];
     DeviceBuffer<> denoised;
     bool denoised_ok = false;
+    // variance-guided denoising (rtiow_read_variance / rtiow_denoise_variance), allocated at first use: the variance plane of the adaptive
+    // accumulation (1 T per pixel, rewritten by every call) and the filter's two ping-pong variance planes
+    DeviceBuffer<> variance;
+    DeviceBuffer<> dn_var[2];
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

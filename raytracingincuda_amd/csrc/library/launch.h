@@ -1,6 +1,7 @@
 // launch.h -- the render-family launches on one shared setup (layout_lds, persistent_setup, size_persistent, record_launch): launch_render
 // (static / persistent / sorted with prepass + cost sort + solo waves), launch_accumulate (one chunk of progressive rendering),
-// launch_adaptive (one adaptive chunk); launch_guides / launch_linear / launch_denoise: the denoised previews
+// launch_adaptive (one adaptive chunk); launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
+// launch_denoise_variance: the variance-guided filter
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -8,6 +9,7 @@
 #include "../device/adaptive.h"
 #include "../device/cost_sort.h"
 #include "../device/denoise.h"
+#include "../device/denoise_variance.h"
 
 namespace {
 
@@ -580,6 +582,67 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
         T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
         hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
                            counts, n_uniform, cin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, last ? 1 : 0);
+        HIP_TRY(h, hipGetLastError());
+    }
+    h->denoised_ok = true;
+    return 0;
+}
+
+// The variance plane of an adaptive accumulation into h->variance (rtiow_read_variance, level 0 of rtiow_denoise_variance).  The caller
+// has checked that the accumulation is adaptive.
+template <class T>
+int launch_variance_plane(rtiow_handle_s* h) {
+    const size_t npix = local_pixels(h);
+    HIP_TRY(h, h->variance.ensure(npix * sizeof(T)));
+    hipLaunchKernelGGL(variance_plane_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, npix,
+                       (const unsigned char*)h->acc_mid[h->acc_cur], (const int32_t*)h->adapt_counts, h->variance.as<T>());
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// The levels of rtiow_denoise_variance that stage their taps in LDS (bit k = level k), by measurement at 1920 x 1080 (DESIGN.md section 4.9,
+// profiles/denoise_variance/denoise_variance_probe.json): fp32 steps 1, 2 and 4 (5 levels about 1.8 -> 0.9 ms); fp64 steps 1 and 2 (about 2.1 -> 1.25 ms;
+// step 4, 96 KB of LDS and one workgroup per CU, gains under 1 %).
+constexpr int VARIANCE_TILE_LEVELS_F32 = 7, VARIANCE_TILE_LEVELS_F64 = 3;
+
+// variance_plane_kernel, then `levels` launches of variance_tile_kernel (the levels above) or variance_filter_kernel over the adaptive accumulation (rtiow_denoise_variance): the
+// colour ping-pongs through h->dn_tmp[0/1] into h->denoised as in launch_denoise, the variance from h->variance through h->dn_var[0/1]
+// (the last level stores none).  sigma_variance in double, its square rounded to T here; +inf -- or a square that is not finite in T --
+// turns the colour term off on the host.  inv2g[3] = 1 / sigma^2 of normal, albedo, depth.  The caller has checked state and arguments
+// and made the guides current.
+template <class T>
+int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance, const double inv2g[3]) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    if (int rc = launch_variance_plane<T>(h)) return rc;
+    HIP_TRY(h, h->denoised.ensure(npix * 3 * sizeof(T)));
+    for (int b = 0; b < 2 && b < levels - 1; ++b) {
+        HIP_TRY(h, h->dn_tmp[b].ensure(npix * 3 * sizeof(T)));
+        HIP_TRY(h, h->dn_var[b].ensure(npix * sizeof(T)));
+    }
+    VarianceWeights<T> fw;
+    fw.sv2 = (T)(sigma_variance * sigma_variance);
+    fw.colour_on = std::isfinite(fw.sv2) ? 1 : 0;
+    if (!fw.colour_on) fw.sv2 = (T)0;
+    fw.eps = (T)1e-8;
+    fw.in = (T)inv2g[0]; fw.ia = (T)inv2g[1]; fw.iz = (T)inv2g[2];
+    const unsigned char* mid = h->acc_mid[h->acc_cur];
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    // bit k: level k (step 1 << k, k < 3) stages its taps in LDS (variance_tile_kernel)
+    const int tile_levels = tuned("RTIOW_TUNE_VARIANCE_TILE", sizeof(T) == 4 ? VARIANCE_TILE_LEVELS_F32 : VARIANCE_TILE_LEVELS_F64);
+    for (int k = 0; k < levels; ++k) {
+        fw.fk = (T)std::ldexp(1.0, 2 * k);
+        const bool last = k == levels - 1;
+        const T* cin = k == 0 ? nullptr : h->dn_tmp[(k - 1) & 1].as<const T>();
+        const T* vin = k == 0 ? h->variance.as<const T>() : h->dn_var[(k - 1) & 1].as<const T>();
+        T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
+        T* vout = last ? nullptr : h->dn_var[k & 1].as<T>();
+        const bool tiled = k < 3 && ((tile_levels >> k) & 1);
+        const size_t lds = tiled ? variance_tile_bytes<T>(1 << k) : 0;
+        const auto kernel = tiled ? variance_tile_kernel<T> : variance_filter_kernel<T>;
+        HIP_TRY(h, allow_lds(kernel, lds));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
+                           (const int32_t*)h->adapt_counts, cin, vin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, vout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
     h->denoised_ok = true;

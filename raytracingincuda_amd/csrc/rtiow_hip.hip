@@ -62,6 +62,7 @@
 #include "device/render_kernels.h"
 #include "device/cost_sort.h"
 #include "device/denoise.h"
+#include "device/denoise_variance.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -595,6 +596,37 @@ int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) 
     *device_ptr = h->denoised;
     *bytes = image_bytes(h);
     return 0;
+}
+
+// ---- Variance-guided denoising
+int rtiow_read_variance(rtiow_handle h, void* host_var, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->have_camera || h->acc_mode != ACC_MODE_ADAPTIVE) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_variance: no adaptive chunk since the last reset (plain chunks keep no second moment)");
+    const size_t want = local_pixels(h);
+    if (npix != want || (want && !host_var)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_variance: npix must be local_rows x width");
+    if (want == 0) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = by_precision(h, [&](auto t) { return launch_variance_plane<decltype(t)>(h); })) return rc;
+    return copy_out(h, host_var, h->variance, want * elem_size(h));
+}
+
+int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    const double sig[4] = {sigma_variance, sigma_normal, sigma_albedo, sigma_depth};
+    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_variance: levels must be 1..8");
+    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_variance: every sigma must be > 0 (+inf turns its term off)");
+    if (!h->have_camera || h->n == 0 || h->acc_mode != ACC_MODE_ADAPTIVE)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_variance: no adaptive chunk since the last reset (plain chunks keep no second moment)");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_variance: not on a sharded handle (the strips of a shard are not image neighbours)");
+    double inv2g[3];
+    for (int k = 0; k < 3; ++k) inv2g[k] = 1.0 / (sig[k + 1] * sig[k + 1]);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2g); }))) return rc;
+    return timed_end(h, kernel_ms);
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {
