@@ -306,6 +306,51 @@ int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
 int rtiow_read_variance(rtiow_handle h, void* host_var /* npix T */, size_t npix);
 int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms);
 
+/* ---- Temporal history for progressive previews: samples survive a camera move.  The handle keeps a BASE
+ * -- per pixel {H.rgb, M} (history colour, history length in samples) and {normal', depth'} of an earlier camera, with that camera
+ * (primed below) -- and a TEMPORAL IMAGE {C.rgb, M} of the current camera.  rtiow_history_update reprojects every pixel of the current
+ * camera into the base, gathers the matching history bilinearly and blends it with the current accumulation by sample count;
+ * rtiow_history_commit makes the result the new base.  Everything in T, left to right as written, plain * + - / (no fused
+ * multiply-add), so a restatement in numpy gives the same bits.
+ *
+ * Host constants of the base camera, in double from its stored fields, each rounded once to T: a = pixel00' - O', w = du' x dv',
+ * f = (a.x w.x + a.y w.y) + a.z w.z (f < 0: w and f negated), iu = 1 / ((du'.x du'.x + du'.y du'.y) + du'.z du'.z), iv likewise.
+ * Pixel p = (x, y) has the colour c and count n_p of rtiow_read_linear and the guides N_p, t_p:
+ *   D = ((pixel00 + x du) + y dv) - O;  hit (t_p > 0): d = (O + t_p D) - O';  miss: d = D;
+ *   den = (d.x w.x + d.y w.y) + d.z w.z;  s = f / den;  e = s d - a;  u = ((e.x du'.x + e.y du'.y) + e.z du'.z) iu, v with dv', iv;
+ *   te = den / f;  x0 = floor(u), y0 = floor(v), fx = u - x0, fy = v - y0.
+ * Taps (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) with b = (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy, those outside the frame skipped.
+ * A tap q counts when M_q > 0 and -- hit: depth'_q > 0, |depth'_q - te| <= (T)depth_tol te, (N_p.x N'_q.x + N_p.y N'_q.y) + N_p.z
+ * N'_q.z >= (T)normal_cos -- miss: depth'_q == 0.  From 0 over the taps that count: S = S + b H_q, L = L + b M_q, Bs = Bs + b;
+ * Bs > 0: h = S / Bs, m = L / Bs, else h = 0, m = 0;  m = min(m, (T)max_history).  There are no taps (m = 0) unless den > 0,
+ * -1 < u < W and -1 < v < H, nor when the base is empty, was committed at another frame size, or f is 0 or not finite.
+ *   nT = (T)n_p, Mout = m + nT;  Mout > 0: alpha = nT / Mout, Cout = h + alpha (c - h), else Cout = 0.
+ * Without history Cout is c bit for bit and Mout is n_p.  *reprojected_pixels (may be NULL) = the pixels with m > 0.
+ *
+ * rtiow_history_update writes the temporal image.  It always combines the base with the WHOLE current accumulation, so it may be
+ * called after every chunk.  Stale guides are rendered first, inside kernel_ms (NULL: not timed; with reprojected_pixels NULL too
+ * the call is asynchronous).  RTIOW_E_BADARG: depth_tol < 0 or NaN, normal_cos outside [-1, 1] or NaN, max_history <= 0 or NaN
+ * (+inf: no cap).  RTIOW_E_STATE: no chunk since the last accumulation reset.
+ * rtiow_history_commit makes the temporal image, the current guides and the current camera the base: the buffers change owners,
+ * nothing is copied.  The temporal image and the guides are stale afterwards.  Commit, then move the camera (or reset the
+ * accumulation): an update over the accumulation that was committed would count its samples twice.  RTIOW_E_STATE when the temporal
+ * image is stale.
+ * rtiow_history_reset empties the base.  So do rtiow_set_scene and rtiow_set_shard; the base survives rtiow_set_camera, rtiow_init_rng
+ * and rtiow_accumulate_reset.  The temporal image goes stale on rtiow_set_camera, rtiow_set_scene, rtiow_set_shard, rtiow_history_reset
+ * and rtiow_history_commit: rtiow_read_history (planes: rgb npix x 3 T linear, length npix T; either may be NULL; npix = height x width),
+ * rtiow_history_device_ptr (npix x 4 T {C.rgb, M}; valid until the next commit or an update on a larger frame) and
+ * rtiow_denoise_history then return RTIOW_E_STATE.
+ * rtiow_denoise_history is rtiow_denoise with level 0 reading Cout instead of the accumulation: arguments, errors, stale guides and
+ * the output buffer (rtiow_read_denoised, rtiow_denoised_device_ptr) are rtiow_denoise's.
+ * None of these touches the framebuffer, the accumulation, its counts or the bits of the next chunk.  All return RTIOW_E_STATE on a
+ * sharded handle (nranks > 1).  Buffers are allocated at first use.  Not available on groups. */
+int rtiow_history_reset(rtiow_handle h);
+int rtiow_history_update(rtiow_handle h, double depth_tol, double normal_cos, double max_history, float* kernel_ms, uint64_t* reprojected_pixels);
+int rtiow_history_commit(rtiow_handle h);
+int rtiow_read_history(rtiow_handle h, void* rgb /* npix*3 T, linear */, void* length /* npix T */, size_t npix);
+int rtiow_history_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);   /* npix x 4 T: {C.rgb, M} */
+int rtiow_denoise_history(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -33,6 +33,11 @@ int rtiow_host_build_scene(int scene_id, int precision, void* center_radius, voi
 /* camera configuration + camera::initialize (main.cu:100-124, camera.h:33-68).
  * out points to rtiow_camera_f32 or rtiow_camera_f64. */
 int rtiow_host_camera(int precision, int width, int height, int samples, int bounces, void* out);
+/* The same camera::initialize for a placement of the caller's: lookfrom, lookat, vup (3 doubles each), the vertical field of view
+ * and the defocus angle in degrees, the focus distance.  Each is rounded to T on entry and the operations run in T in the order
+ * of rtiow_host_camera, which is this call with the reference's constants (13,2,3), (0,0,0), (0,1,0), 20, 0.6, 10. */
+int rtiow_host_camera_look(int precision, int width, int height, int samples, int bounces, const double* lookfrom, const double* lookat,
+                           const double* vup, double vfov_deg, double defocus_angle_deg, double focus_dist, void* out);
 
 /* Output file name (main.cu:349-358): "<variant>_scene{id}_{W}x{H}_{S}samples_{B}bounces_
  * {T}threadsPerBlockRow.ppm", variant = "global_float" | "global_double". */

@@ -93,6 +93,7 @@ HIP_SYMBOLS = [
     "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples", "rtiow_accumulate_adaptive", "rtiow_read_adaptive_state",
     "rtiow_read_linear", "rtiow_render_guides", "rtiow_read_guides", "rtiow_denoise", "rtiow_read_denoised", "rtiow_denoised_device_ptr",
     "rtiow_read_variance", "rtiow_denoise_variance",
+    "rtiow_history_reset", "rtiow_history_update", "rtiow_history_commit", "rtiow_read_history", "rtiow_history_device_ptr", "rtiow_denoise_history",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -104,7 +105,7 @@ DEBUG_SYMBOLS = [
     "rtiow_debug_gather_schedule",
 ]
 HOST_SYMBOLS = [
-    "rtiow_host_scene_slots", "rtiow_host_build_scene", "rtiow_host_camera", "rtiow_host_ppm_filename",
+    "rtiow_host_scene_slots", "rtiow_host_build_scene", "rtiow_host_camera", "rtiow_host_camera_look", "rtiow_host_ppm_filename",
     "rtiow_host_write_ppm", "rtiow_host_format_ppm", "rtiow_host_write_ppm_binary", "rtiow_host_write_ppm_levels", "rtiow_host_levels", "rtiow_host_shard_rows", "rtiow_host_place_rows",
 ]
 
@@ -132,6 +133,8 @@ def load_host_library():
         lib.rtiow_host_scene_slots.argtypes = [ctypes.c_int]
         lib.rtiow_host_build_scene.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, i32p, i32p]
         lib.rtiow_host_camera.argtypes = [ctypes.c_int] * 5 + [vp]
+        d3 = ctypes.POINTER(ctypes.c_double)
+        lib.rtiow_host_camera_look.argtypes = [ctypes.c_int] * 5 + [d3, d3, d3] + [ctypes.c_double] * 3 + [vp]
         lib.rtiow_host_ppm_filename.argtypes = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_size_t]
         lib.rtiow_host_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
         lib.rtiow_host_write_ppm_binary.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
@@ -202,6 +205,12 @@ def load_hip_library(debug=False):
         lib.rtiow_denoised_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_read_variance.argtypes = [H, vp, ctypes.c_size_t]
         lib.rtiow_denoise_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_history_reset.argtypes = [H]
+        lib.rtiow_history_update.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
+        lib.rtiow_history_commit.argtypes = [H]
+        lib.rtiow_read_history.argtypes = [H, vp, vp, ctypes.c_size_t]
+        lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -281,6 +290,21 @@ def camera(precision, width, height, samples, bounces):
     rc = lib.rtiow_host_camera(precision, int(width), int(height), int(samples), int(bounces), ctypes.addressof(cam))
     if rc:
         raise RtiowError(rc, "rtiow_host_camera: bad arguments")
+    return cam
+
+
+def camera_look(precision, width, height, samples, bounces, lookfrom=(13.0, 2.0, 3.0), lookat=(0.0, 0.0, 0.0), vup=(0.0, 1.0, 0.0),
+                vfov=20.0, defocus_angle=0.6, focus_dist=10.0):
+    """camera::initialize (camera.h:33-68) for a placement of the caller's; the defaults are the reference's (main.cu:114-121), with
+    which this is camera() byte for byte.  Every argument is rounded to the precision on entry."""
+    lib = load_host_library()
+    cam = CameraF64() if precision == 64 else CameraF32()
+    _dtype(precision)
+    v3 = lambda v: (ctypes.c_double * 3)(*[float(x) for x in v])
+    rc = lib.rtiow_host_camera_look(precision, int(width), int(height), int(samples), int(bounces), v3(lookfrom), v3(lookat), v3(vup),
+                                    float(vfov), float(defocus_angle), float(focus_dist), ctypes.addressof(cam))
+    if rc:
+        raise RtiowError(rc, "rtiow_host_camera_look: bad arguments")
     return cam
 
 
@@ -380,6 +404,14 @@ DENOISE_SIGMA_DEPTH = 0.05
 # 64 uniform samples of the worse-of-two-scenes ratio q_var / q_fixed, q = MSE ratio as above, q_fixed from denoise() at its defaults
 # (profiles/denoise_variance/denoise_variance_probe.json).  Dimensionless: a tolerance in standard deviations.
 DENOISE_SIGMA_VARIANCE = 4.5
+
+
+# Renderer.history_update defaults: the best of scripts/history_probe.py --sweep, i.e. the smallest worse-of-two-scenes MSE ratio of
+# the temporal image against the noisy one at the end of an 8-frame orbit, 320 x 180, 4 samples a frame, against 1024 samples
+# (profiles/history/history_probe.json).
+HISTORY_DEPTH_TOL = 0.1
+HISTORY_NORMAL_COS = 0.9
+HISTORY_MAX = 16.0
 
 
 class Renderer:
@@ -607,6 +639,51 @@ class Renderer:
         ms = None if not sync else ctypes.c_float(0)
         self._check(self._lib.rtiow_denoise_variance(self._h, int(levels), float(sigma_variance), float(sigma_normal), float(sigma_albedo),
                                                      float(sigma_depth), ctypes.byref(ms) if sync else None))
+        return self.read_denoised() if sync else None
+
+    def history_reset(self):
+        """Forget the temporal history: the next history_update() finds no base."""
+        self._check(self._lib.rtiow_history_reset(self._h))
+
+    def history_update(self, depth_tol=HISTORY_DEPTH_TOL, normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
+        """Temporal reprojection: combine the history committed from an earlier camera with the whole
+        current accumulation into the temporal image history() reads.  A base sample is carried where it reprojects into the frame
+        onto the same surface: relative depth within depth_tol, normals at least normal_cos apart in cosine; a pixel's history
+        length is capped at max_history samples (float("inf"): no cap).  Call it after any chunk: nothing is counted twice.
+        Returns the number of pixels that carried history (None when sync=False)."""
+        if not sync:
+            self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), None, None))
+            return None
+        ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
+        self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
+        return int(n.value)
+
+    def history_commit(self):
+        """Make the temporal image, the current guides and the current camera the base of later updates (buffers change owners, nothing
+        is copied).  Then move the camera: the temporal image and the guides are stale after the call."""
+        self._check(self._lib.rtiow_history_commit(self._h))
+
+    def history(self):
+        """(rgb [H, W, 3] linear, length [H, W]) of the temporal image: the blended colour and its history length in samples."""
+        rgb = np.empty((self.local_rows, self.width, 3), self.dtype)
+        length = np.empty((self.local_rows, self.width), self.dtype)
+        self._check(self._lib.rtiow_read_history(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
+        return rgb, length
+
+    def history_device_ptr(self):
+        """(device address, bytes) of the temporal image, H x W x 4 T: {C.rgb, M}."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.rtiow_history_device_ptr(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def denoise_history(self, levels=DENOISE_LEVELS, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                        sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, sync=True):
+        """denoise() of the temporal image instead of the accumulation: the same filter, level 0 reading history()'s colour.  Returns
+        and stores its image like denoise()."""
+        ms = None if not sync else ctypes.c_float(0)
+        self._check(self._lib.rtiow_denoise_history(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
+                                                    float(sigma_depth), ctypes.byref(ms) if sync else None))
         return self.read_denoised() if sync else None
 
     def read_denoised(self):

@@ -129,11 +129,13 @@ template <class T> P3<T> normalize(P3<T> a) {                                   
     return over(a, len);
 }
 
+// camera::initialize for a placement given in double: every argument is rounded to T on entry, the rest runs in T.
 template <class T, class CAM>
-void camera_t(int width, int height, int samples, int bounces, CAM* cam) {
+void camera_t(int width, int height, int samples, int bounces, const double* from, const double* at, const double* up,
+              double vfov_deg, double defocus_angle_deg, double focus, CAM* cam) {
     const T pi = (T)3.1415926535897932385L;                     // rtweekend.h:14
-    const T vfov = 20, focus_dist = (T)10.0, defocus_angle = (T)0.6;   // main.cu:114-121
-    const P3<T> lookfrom = {{13, 2, 3}}, lookat = {{0, 0, 0}}, vup = {{0, 1, 0}};
+    const T vfov = (T)vfov_deg, focus_dist = (T)focus, defocus_angle = (T)defocus_angle_deg;   // main.cu:114-121
+    const P3<T> lookfrom = {{(T)from[0], (T)from[1], (T)from[2]}}, lookat = {{(T)at[0], (T)at[1], (T)at[2]}}, vup = {{(T)up[0], (T)up[1], (T)up[2]}};
     cam->img_width = width; cam->img_height = height;
     cam->samples_per_pixel = samples; cam->max_depth = bounces;
     cam->pixel_samples_scale = (T)1 / samples;                  // camera.h:34
@@ -279,11 +281,17 @@ int rtiow_host_build_scene(int scene_id, int precision, void* center_radius, voi
     return RTIOW_E_BADARG;
 }
 
-int rtiow_host_camera(int precision, int width, int height, int samples, int bounces, void* out) {
-    if (!out || width <= 0 || height <= 0) return RTIOW_E_BADARG;
-    if (precision == 32) { camera_t<float>(width, height, samples, bounces, (rtiow_camera_f32*)out); return 0; }
-    if (precision == 64) { camera_t<double>(width, height, samples, bounces, (rtiow_camera_f64*)out); return 0; }
+int rtiow_host_camera_look(int precision, int width, int height, int samples, int bounces, const double* lookfrom, const double* lookat,
+                           const double* vup, double vfov_deg, double defocus_angle_deg, double focus_dist, void* out) {
+    if (!out || !lookfrom || !lookat || !vup || width <= 0 || height <= 0) return RTIOW_E_BADARG;
+    if (precision == 32) { camera_t<float>(width, height, samples, bounces, lookfrom, lookat, vup, vfov_deg, defocus_angle_deg, focus_dist, (rtiow_camera_f32*)out); return 0; }
+    if (precision == 64) { camera_t<double>(width, height, samples, bounces, lookfrom, lookat, vup, vfov_deg, defocus_angle_deg, focus_dist, (rtiow_camera_f64*)out); return 0; }
     return RTIOW_E_BADARG;
+}
+
+int rtiow_host_camera(int precision, int width, int height, int samples, int bounces, void* out) {
+    const double lookfrom[3] = {13, 2, 3}, lookat[3] = {0, 0, 0}, vup[3] = {0, 1, 0};       // main.cu:114-121
+    return rtiow_host_camera_look(precision, width, height, samples, bounces, lookfrom, lookat, vup, 20, 0.6, 10.0, out);
 }
 
 int rtiow_host_ppm_filename(int precision, int scene_id, int width, int height, int samples,

@@ -110,6 +110,18 @@ struct rtiow_handle_s {
     // accumulation (1 T per pixel, rewritten by every call) and the filter's two ping-pong variance planes
     DeviceBuffer<> variance;
     DeviceBuffer<> dn_var[2];
+    // temporal history (rtiow_history_*), allocated at first use.  The base: what rtiow_history_commit kept of an earlier camera --
+    // {H.rgb, M} and {normal', depth'}, 4 T per pixel each, and that camera (hist_base_ok: there is one; it survives rtiow_set_camera,
+    // rtiow_accumulate_reset and rtiow_init_rng, and is emptied by rtiow_history_reset, rtiow_set_scene and rtiow_set_shard).  The
+    // temporal image of the current camera: {C.rgb, M}, 4 T per pixel, and its colour alone as the 3-T plane the filter reads
+    // (hist_ok: rtiow_history_update has written them since the last set_* / reset / commit).  hist_ctr: the reprojected-pixel count.
+    DeviceBuffer<> hist_base_hm, hist_base_nd;
+    bool hist_base_ok = false;
+    rtiow_camera_f32 hist_cam32{};
+    rtiow_camera_f64 hist_cam64{};
+    DeviceBuffer<> hist_cm, hist_rgb;
+    bool hist_ok = false;
+    DeviceBuffer<unsigned> hist_ctr;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

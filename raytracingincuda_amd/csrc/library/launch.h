@@ -1,7 +1,7 @@
 // launch.h -- the render-family launches on one shared setup (layout_lds, persistent_setup, size_persistent, record_launch): launch_render
 // (static / persistent / sorted with prepass + cost sort + solo waves), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk); launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter
+// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -10,6 +10,7 @@
 #include "../device/cost_sort.h"
 #include "../device/denoise.h"
 #include "../device/denoise_variance.h"
+#include "../device/history.h"
 
 namespace {
 
@@ -564,8 +565,9 @@ int launch_linear(rtiow_handle_s* h) {
 // h->dn_tmp[0/1], the last writes the gamma-encoded image to h->denoised.  inv2[4] = 1 / sigma^2 of colour, normal, albedo, depth (double);
 // the colour term of level k is scaled by 4^k and every weight is rounded to T here.  The caller has checked state and arguments and
 // made the guides current.
+// from_history: level 0 reads the temporal colour plane h->hist_rgb instead (rtiow_denoise_history).
 template <class T>
-int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
+int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool from_history = false) {
     const int W = img_w(h), rows = h->local_rows;
     const size_t npix = (size_t)W * rows;
     HIP_TRY(h, h->denoised.ensure(npix * 3 * sizeof(T)));
@@ -578,13 +580,66 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4]) {
         fw.ic = (T)(inv2[0] * std::ldexp(1.0, 2 * k));
         fw.in = (T)inv2[1]; fw.ia = (T)inv2[2]; fw.iz = (T)inv2[3];
         const bool last = k == levels - 1;
-        const T* cin = k == 0 ? nullptr : h->dn_tmp[(k - 1) & 1].as<const T>();
+        const bool records = k == 0 && !from_history;
+        const T* cin = k == 0 ? (from_history ? h->hist_rgb.as<const T>() : nullptr) : h->dn_tmp[(k - 1) & 1].as<const T>();
         T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
-        hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
+        hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, records ? mid : nullptr,
                            counts, n_uniform, cin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
     h->denoised_ok = true;
+    return 0;
+}
+
+// The base camera's constants of history_reproject_kernel, in double from the stored camera fields and
+// rounded once to T: a = pixel00' - O', w = du' x dv' turned so that f = a.w > 0, iu = 1 / |du'|^2, iv = 1 / |dv'|^2.  Returns whether
+// the base can be reprojected into: f finite and not 0.
+template <class T, class CAM>
+bool history_constants(const CAM& b, HistoryParams<T>& hp) {
+    const double O[3] = {(double)b.center[0], (double)b.center[1], (double)b.center[2]};
+    const double du[3] = {(double)b.pixel_delta_u[0], (double)b.pixel_delta_u[1], (double)b.pixel_delta_u[2]};
+    const double dv[3] = {(double)b.pixel_delta_v[0], (double)b.pixel_delta_v[1], (double)b.pixel_delta_v[2]};
+    const double a[3] = {(double)b.pixel00_loc[0] - O[0], (double)b.pixel00_loc[1] - O[1], (double)b.pixel00_loc[2] - O[2]};
+    double w[3] = {du[1] * dv[2] - du[2] * dv[1], du[2] * dv[0] - du[0] * dv[2], du[0] * dv[1] - du[1] * dv[0]};
+    double f = (a[0] * w[0] + a[1] * w[1]) + a[2] * w[2];
+    if (f < 0) { w[0] = -w[0]; w[1] = -w[1]; w[2] = -w[2]; f = -f; }
+    const double iu = 1.0 / ((du[0] * du[0] + du[1] * du[1]) + du[2] * du[2]), iv = 1.0 / ((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
+    hp.Ob = {(T)O[0], (T)O[1], (T)O[2]};
+    hp.a = {(T)a[0], (T)a[1], (T)a[2]};
+    hp.w = {(T)w[0], (T)w[1], (T)w[2]};
+    hp.dub = {(T)du[0], (T)du[1], (T)du[2]};
+    hp.dvb = {(T)dv[0], (T)dv[1], (T)dv[2]};
+    hp.f = (T)f; hp.iu = (T)iu; hp.iv = (T)iv;
+    return std::isfinite(hp.f) && hp.f != (T)0;
+}
+
+// history_reproject_kernel over the current accumulation and the base into h->hist_cm / h->hist_rgb (rtiow_history_update); the count of
+// pixels that carried history goes to h->hist_ctr.  The caller has checked state and arguments and made the guides current.
+template <class T>
+int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
+    HIP_TRY(h, h->hist_rgb.ensure(npix * 3 * sizeof(T)));
+    HIP_TRY(h, h->hist_ctr.ensure(sizeof(unsigned)));
+    const auto& c = camera<T>(h);
+    HistoryParams<T> hp{};
+    hp.O = {c.center[0], c.center[1], c.center[2]};
+    hp.pixel00 = {c.pixel00_loc[0], c.pixel00_loc[1], c.pixel00_loc[2]};
+    hp.du = {c.pixel_delta_u[0], c.pixel_delta_u[1], c.pixel_delta_u[2]};
+    hp.dv = {c.pixel_delta_v[0], c.pixel_delta_v[1], c.pixel_delta_v[2]};
+    hp.depth_tol = (T)depth_tol; hp.normal_cos = (T)normal_cos; hp.max_history = (T)max_history;
+    const auto& b = [&]() -> const auto& { if constexpr (sizeof(T) == 4) return h->hist_cam32; else return h->hist_cam64; }();
+    hp.have_base = h->hist_base_ok && b.img_width == W && b.img_height == rows && history_constants<T>(b, hp) ? 1 : 0;
+    const unsigned char* mid; const int32_t* counts; int n_uniform;
+    accumulation_source(h, mid, counts, n_uniform);
+    HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, sizeof(unsigned), h->stream));
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    hipLaunchKernelGGL(history_reproject_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, mid, counts, n_uniform,
+                       h->guide_nd.as<const Vec4<T>>(), h->hist_base_hm.as<const Vec4<T>>(), h->hist_base_nd.as<const Vec4<T>>(),
+                       h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    HIP_TRY(h, hipGetLastError());
+    h->hist_ok = true;
     return 0;
 }
 

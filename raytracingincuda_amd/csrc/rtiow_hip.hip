@@ -63,6 +63,7 @@
 #include "device/cost_sort.h"
 #include "device/denoise.h"
 #include "device/denoise_variance.h"
+#include "device/history.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -127,12 +128,13 @@ int need_rng(rtiow_handle_s* h, const char* call) {
 }
 
 // What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
-// and (clear_rng: camera, shard) the RNG states.
+// the temporal image and (clear_rng: camera, shard) the RNG states; (clear_base: scene, shard) the history base, which a new camera keeps.
 void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
-void invalidate_frame(rtiow_handle_s* h, bool clear_rng) {
+void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
     reset_accumulation(h);
-    h->guides_ok = false; h->denoised_ok = false;
+    h->guides_ok = false; h->denoised_ok = false; h->hist_ok = false;
     if (clear_rng) h->rng_ready = false;
+    if (clear_base) h->hist_base_ok = false;
 }
 
 // The times a render call on a shard without rows reports.
@@ -245,7 +247,7 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (!h) return RTIOW_E_BADARG;
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
-    invalidate_frame(h, false);
+    invalidate_frame(h, false, true);
     return by_precision(h, [&](auto t) {
         using T = decltype(t);
         return upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid);
@@ -261,7 +263,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->have_camera = true;
     h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
-    invalidate_frame(h, true);
+    invalidate_frame(h, true, false);
     return 0;
 }
 
@@ -270,7 +272,7 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
     h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
     if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
-    invalidate_frame(h, true);
+    invalidate_frame(h, true, true);
     return 0;
 }
 
@@ -626,6 +628,95 @@ int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, do
     if (rc) return rc;
     if (!h->guides_ok && (rc = render_guides(h))) return rc;
     if ((rc = by_precision(h, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2g); }))) return rc;
+    return timed_end(h, kernel_ms);
+}
+
+// ---- Temporal history
+int rtiow_history_reset(rtiow_handle h) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_reset: not on a sharded handle");
+    h->hist_base_ok = false; h->hist_ok = false;
+    return 0;
+}
+
+int rtiow_history_update(rtiow_handle h, double depth_tol, double normal_cos, double max_history, float* kernel_ms, uint64_t* reprojected_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    if (reprojected_pixels) *reprojected_pixels = 0;
+    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
+    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update: no chunk since the last reset");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update: not on a sharded handle (the strips of a shard are not image neighbours)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_history<decltype(t)>(h, depth_tol, normal_cos, max_history); }))) return rc;
+    if ((rc = timed_end(h, kernel_ms))) return rc;
+    if (reprojected_pixels) {
+        unsigned count = 0;
+        if ((rc = copy_out(h, &count, h->hist_ctr, sizeof count))) return rc;
+        *reprojected_pixels = count;
+    }
+    return 0;
+}
+
+int rtiow_history_commit(rtiow_handle h) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit: not on a sharded handle");
+    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit: no temporal image for the current camera (rtiow_history_update)");
+    // the temporal image and the guides become the base by changing owners (the work that wrote them is ordered on the stream before
+    // whatever reads them next); the buffers they leave behind hold the old base, so both go stale
+    std::swap(h->hist_base_hm, h->hist_cm);
+    std::swap(h->hist_base_nd, h->guide_nd);
+    h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
+    h->hist_base_ok = true;
+    h->hist_ok = false; h->guides_ok = false;
+    return 0;
+}
+
+int rtiow_read_history(rtiow_handle h, void* rgb, void* length, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history: not on a sharded handle");
+    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history: no temporal image for the current camera (rtiow_history_update)");
+    const size_t want = local_pixels(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history: npix must be height x width");
+    if (!rgb && !length) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h);
+    std::vector<unsigned char> cm(want * 4 * es);
+    if (int rc = copy_out(h, cm.data(), h->hist_cm, cm.size())) return rc;
+    for (size_t k = 0; k < want; ++k) {                  // {C.rgb, M} -> planes
+        if (rgb) std::memcpy((unsigned char*)rgb + 3 * k * es, cm.data() + 4 * k * es, 3 * es);
+        if (length) std::memcpy((unsigned char*)length + k * es, cm.data() + (4 * k + 3) * es, es);
+    }
+    return 0;
+}
+
+int rtiow_history_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
+    if (!h || !device_ptr || !bytes) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_device_ptr: not on a sharded handle");
+    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_device_ptr: no temporal image for the current camera (rtiow_history_update)");
+    *device_ptr = h->hist_cm;
+    *bytes = local_pixels(h) * 4 * elem_size(h);
+    return 0;
+}
+
+int rtiow_denoise_history(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
+    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history: levels must be 1..8");
+    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history: every sigma must be > 0 (+inf turns its term off)");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history: not on a sharded handle (the strips of a shard are not image neighbours)");
+    if (!h->have_camera || h->n == 0 || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history: no temporal image for the current camera (rtiow_history_update)");
+    double inv2[4];
+    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2, true); }))) return rc;
     return timed_end(h, kernel_ms);
 }
 
