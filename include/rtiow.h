@@ -64,7 +64,14 @@ extern "C" {
  * state and colour sum carried exactly, so the image is unchanged).  Removes the drain tail of
  * late heavy pixels.  Default.  The hand-out order packs a pixel as (local row << 16 | column): a frame wider than 65535
  * columns or a shard taller than 32767 rows (or smaller than 4096 pixels) is rendered like RTIOW_SCHED_PERSISTENT, in one
- * launch in tile order (same image; rtiow_stats.phases then reads 1). */
+ * launch in tile order (same image; rtiow_stats.phases then reads 1).
+ * The order is carried across renders: it depends on scene, camera, shard, bounce limit and sample count, not on the seed, so after
+ * a handle's first two-phase render every further rtiow_render of the same frame skips prepass and ranking and launches once, from
+ * sample 0, in that order (rtiow_stats.phases 1, order_reused 1; the same image bit for bit -- the order is a scheduling hint).
+ * rtiow_set_scene, rtiow_set_shard and rtiow_set_camera with another camera drop the order (the identical camera keeps it), as do
+ * rtiow_count_segments, rtiow_accumulate and rtiow_accumulate_adaptive, which write the same buffers; rtiow_init_rng keeps it.  Any
+ * change of the launch geometry (schedule, scene source, waves_per_simd) is caught by a key compared on every render.  The
+ * environment variable RTIOW_ORDER_REUSE=0, read by rtiow_create, makes every render rank again. */
 #define RTIOW_SCHED_SORTED     2
 
 typedef struct rtiow_handle_s* rtiow_handle;
@@ -130,7 +137,9 @@ typedef struct {
     int32_t  num_cus;            /* compute units of the handle's device (hipDeviceProp_t::multiProcessorCount)              */
     double   place_ms;
     int32_t  clock_mhz;          /* its nominal shader clock (hipDeviceProp_t::clockRate): what an issue-slot figure is rated against */
-    int32_t  reserved0;
+    int32_t  order_reused;       /* RTIOW_SCHED_SORTED: 1 when the last render skipped prepass and ranking and launched once, from sample 0, in the
+                                  * order an earlier render of the same frame left (phases 1, prepass_ms 0, staged_stores 1; main_ms and place_ms
+                                  * still split render_ms).  Was reserved0: same offset and size, no ABI change. */
     /* ABI 6.  EFFECTIVE shader clock of the last timed render's launches (persistent schedules; 0: none taken): one wave of each launch --
      * the first dispatched, resident until the hand-out runs dry -- stamps s_memtime and s_memrealtime when it starts and ends, the clock is
      * d(s_memtime) / d(s_memrealtime) x 100 MHz over that wave's life.  A cold process whose render takes 16 ms instead of 11.6 shows here

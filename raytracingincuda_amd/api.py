@@ -72,7 +72,7 @@ class Stats(ctypes.Structure):
                 ("grid_direct", ctypes.c_int32), ("grid_cell", ctypes.c_double),
                 ("solo_waves", ctypes.c_int32), ("solo_lanes", ctypes.c_int32), ("scene_prepare_ms", ctypes.c_double),
                 ("staged_stores", ctypes.c_int32), ("num_cus", ctypes.c_int32), ("place_ms", ctypes.c_double),
-                ("clock_mhz", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("clock_mhz", ctypes.c_int32), ("order_reused", ctypes.c_int32),
                 ("main_clock_mhz", ctypes.c_double), ("prepass_clock_mhz", ctypes.c_double), ("main_wave0_ms", ctypes.c_double)]
 
 
@@ -747,7 +747,7 @@ class Renderer:
         return out
 
     def debug_read_costs(self):
-        """(own, smoothed) prepass cost maps of the last sorted render, each local_rows x width."""
+        """(own, smoothed) prepass cost maps of the last ranking (the last sorted render's own, or the one whose order it reused), each local_rows x width."""
         self._need_debug()
         own = np.zeros((self.local_rows, self.width), np.uint32)
         smoothed = np.zeros_like(own)

@@ -3,6 +3,7 @@
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "../device/params.h"
+#include "order_key.h"
 
 // A device allocation owned by the handle or by one call: freed when it goes out of scope.  ensure() grows it to at least `bytes`
 // and never shrinks it; the old allocation is freed before the new one is made, so its contents are lost.
@@ -85,6 +86,11 @@ struct rtiow_handle_s {
     DeviceBuffer<int> slot_of;                    // SCHED_SORTED: pixel -> slot (the inverse of `order`)
     DeviceBuffer<> staged;                        // SCHED_SORTED: finished pixels in slot order (place_pixels_kernel writes the image)
     DeviceBuffer<unsigned> sort_scratch;
+    // SCHED_SORTED: the order a two-phase render left in `order` / `slot_of` is carried to the next renders of the same frame, which then
+    // launch once from sample 0 (order_key.h).  Cleared by whatever changes the cost map (scene, camera, shard: invalidate_frame) or
+    // overwrites the two buffers (counting runs, rtiow_accumulate, rtiow_accumulate_adaptive); launch_render compares the key itself.
+    CarriedOrder carried;
+    bool order_reuse = true;                      // RTIOW_ORDER_REUSE=0 at rtiow_create: every sorted render ranks again (A/B runs, studies)
     // progressive rendering (rtiow_accumulate): samples accumulated since the last reset, the per-pixel MidState records of the last chunk
     // (two buffers, ping-pong: acc_mid[acc_cur] holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)
     int acc_samples = 0;

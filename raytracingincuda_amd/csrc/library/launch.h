@@ -1,5 +1,5 @@
 // launch.h -- the render-family launches on one shared setup (layout_lds, persistent_setup, size_persistent, record_launch): launch_render
-// (static / persistent / sorted with prepass + cost sort + solo waves), launch_accumulate (one chunk of progressive rendering),
+// (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk); launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
 // launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
@@ -262,6 +262,7 @@ void record_launch(rtiow_handle_s* h, const Launch<T>& L, int phases = 1, int so
     h->stats.solo_waves = solo_waves;
     h->stats.solo_lanes = solo_lanes;
     h->stats.staged_stores = staged_stores;
+    h->stats.order_reused = 0;
 }
 
 template <class T>
@@ -273,6 +274,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
     p.cold.seg_counter = seg_counter ? seg_counter + 1 : nullptr;     // [0] prepass launch, [1] main (or only) launch
     p.cold.pixel_times = seg_counter ? h->pixel_times : nullptr;
     int phases = 1;
+    bool reused = false;                        // sorted schedule: the launch below runs in the order an earlier render ranked
     dim3 grid;
     if (h->schedule == RTIOW_SCHED_STATIC) {
         p.cold.bx = bx; p.cold.by = by; p.cold.wave_tiles = wave_tiles;
@@ -301,11 +303,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
         int SA = S >= 64 ? 3 : (S >= 24 ? 2 : 0);
         SA = tuned("RTIOW_TUNE_SA", SA);       // measured on the headline config: 1 -> 25.5 ms, 2 -> 22.5, 3 -> 22.1, 4 -> 22.4, 8 -> 23.1
         if (SA > 0 && sorted_handout(h)) {
-            phases = 2;
             const int total_pools = (npix + POOL - 1) / POOL;
-            HIP_TRY(h, h->mid.ensure((size_t)npix * sizeof(MidState<T>)));
-            HIP_TRY(h, h->cost.ensure((size_t)npix * sizeof(uint32_t)));
-            HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
             // Solo waves (ColdParams::solo_*, render_solo_kernel).  A shard or small frame ends with its longest sample
             // chains (one pixel = one sequential chain), and a chain advances at the pace of its wave: 2452 segments at
             // ~3 us per trip among 63 other pixels.  Two heavy pixels alone in a wave share every sphere loop with the
@@ -333,41 +331,58 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
             if (solo_waves > (int)blocks) solo_waves = (int)blocks;
             if ((long long)solo_waves * solo_lanes > npix / 2) solo_waves = npix / 2 / solo_lanes;
             const int solo_slots = solo_waves * solo_lanes;
-            HIP_TRY(h, h->order.ensure(((size_t)total_pools * POOL + (size_t)solo_slots) * sizeof(int)));
-            HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
             // finished pixels go to their slot in a staging buffer and place_pixels_kernel writes the image (ColdParams::stage_by_slot)
 #ifdef RTIOW_DIRECT_STORES
             const bool staged_stores = false;           // A/B build: every lane stores its pixel at its place in the image when it finishes
 #else
             const bool staged_stores = true;
 #endif
+            // The carried order (order_key.h): the last two-phase render of this handle ranked this very frame for this very launch and
+            // nothing has touched h->order / h->slot_of since.  Then the prepass and the ranking are skipped: one launch renders samples
+            // [0, S) from the states of rtiow_init_rng in that order.  The order is a scheduling hint -- every pixel is its own
+            // sequential chain -- so the image is the same bit for bit.  Counting runs always rank again.
+            const OrderKey key = {p.cold.W, h->local_rows, h->rank, h->nranks, h->strip_rows, S, p.B, h->precision, h->schedule, h->scene_source,
+                                  lane_cap, (int)blocks, total_pools, solo_waves, solo_lanes, L.bounded_f32 ? 1 : 0, staged_stores ? 1 : 0};
+            reused = !count && staged_stores && h->order_reuse && h->carried.usable(key);
+            if (!reused) {
+                h->carried.clear();                      // the buffers below are about to be overwritten, perhaps reallocated
+                phases = 2;
+                HIP_TRY(h, h->mid.ensure((size_t)npix * sizeof(MidState<T>)));
+                HIP_TRY(h, h->cost.ensure((size_t)npix * sizeof(uint32_t)));
+                HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
+            }
             const size_t total_slots = (size_t)total_pools * POOL + (size_t)solo_slots;
+            HIP_TRY(h, h->order.ensure(total_slots * sizeof(int)));
+            HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
             if (staged_stores) {
                 HIP_TRY(h, h->slot_of.ensure((size_t)npix * sizeof(int)));
                 HIP_TRY(h, h->staged.ensure(total_slots * 3 * sizeof(T)));
             }
             if (prepare_only) return 0;                  // every table and buffer of this configuration now exists
-            // ---- prepass: samples [0, SA) in tile order through the same persistent body (the static
-            // kernel keeps only ~40 % of its lanes busy over a few samples: 2.6 ms vs 1.4 ms measured
-            // for 4 samples); RNG state, colour sum and segment count are parked per pixel.
-            RenderParams<T> pa = p;
-            pa.s_end = SA; pa.cold.mid_out = h->mid; pa.cold.cost_out = h->cost;
-            pa.cold.seg_counter = seg_counter;
-            if (pa.cold.clock_stamps) pa.cold.clock_stamps = h->clock_stamps_dev;          // the prepass's four words
-            const RenderFn<T> kp = by_source(L.lds_source, [&](auto src) -> RenderFn<T> {
-                if constexpr (sizeof(T) == 4)
-                    if (L.bounded_f32) return count ? render_prepass_kernel<T, src, true, true> : render_prepass_kernel<T, src, false, true>;
-                return count ? render_prepass_kernel<T, src, true> : render_prepass_kernel<T, src, false>;
-            });
-            HIP_TRY(h, allow_lds(kp, L.lds));
-            hipLaunchKernelGGL(kp, grid, block, L.lds, h->stream, pa);
-            if (h->time_phases) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
-            h->stats.prepass_samples = SA;
-            HIP_TRY(h, hipGetLastError());
-            // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools
-            if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of.as<int>() : nullptr))) return rc;
-            // ---- main launch: samples [SA, S) in that order
-            p.cold.s_begin = SA; p.cold.mid_in = h->mid;
+            if (!reused) {
+                // ---- prepass: samples [0, SA) in tile order through the same persistent body (the static
+                // kernel keeps only ~40 % of its lanes busy over a few samples: 2.6 ms vs 1.4 ms measured
+                // for 4 samples); RNG state, colour sum and segment count are parked per pixel.
+                RenderParams<T> pa = p;
+                pa.s_end = SA; pa.cold.mid_out = h->mid; pa.cold.cost_out = h->cost;
+                pa.cold.seg_counter = seg_counter;
+                if (pa.cold.clock_stamps) pa.cold.clock_stamps = h->clock_stamps_dev;          // the prepass's four words
+                const RenderFn<T> kp = by_source(L.lds_source, [&](auto src) -> RenderFn<T> {
+                    if constexpr (sizeof(T) == 4)
+                        if (L.bounded_f32) return count ? render_prepass_kernel<T, src, true, true> : render_prepass_kernel<T, src, false, true>;
+                    return count ? render_prepass_kernel<T, src, true> : render_prepass_kernel<T, src, false>;
+                });
+                HIP_TRY(h, allow_lds(kp, L.lds));
+                hipLaunchKernelGGL(kp, grid, block, L.lds, h->stream, pa);
+                if (h->time_phases) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
+                h->stats.prepass_samples = SA;
+                HIP_TRY(h, hipGetLastError());
+                // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools
+                if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of.as<int>() : nullptr))) return rc;
+                if (!count && staged_stores) h->carried.store(key);
+                // ---- main launch: samples [SA, S) in that order
+                p.cold.s_begin = SA; p.cold.mid_in = h->mid;
+            }
             p.cold.solo_waves = solo_waves; p.cold.solo_lanes = solo_lanes;
             if (staged_stores) { p.cold.stage_by_slot = 1; p.cold.fb = h->staged.as<T>(); }
             if (solo_waves > 0) {
@@ -396,6 +411,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
     if (!count) {
         record_launch(h, L, phases, p.cold.solo_waves, p.cold.solo_waves > 0 ? p.cold.solo_lanes : 0, p.cold.stage_by_slot);
         h->stats.primary_rays = (uint64_t)h->local_rows * p.cold.W * (uint64_t)p.cold.S;
+        h->stats.order_reused = reused ? 1 : 0;
     }
     return 0;
 }
@@ -437,6 +453,7 @@ int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
     const bool ranked = n > 0 && sorted_handout(h);
     const int total_pools = (npix + POOL - 1) / POOL;
     if (ranked) {
+        h->carried.clear();                              // this chunk's ranking overwrites h->order: launch_render ranks again
         HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
         HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
         HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
@@ -482,6 +499,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
     HIP_TRY(h, h->adapt_counts.ensure((size_t)npix * sizeof(int32_t)));
     HIP_TRY(h, h->adapt_err.ensure((size_t)npix * sizeof(float)));
     HIP_TRY(h, h->adapt_ctr.ensure(2 * sizeof(unsigned)));
+    h->carried.clear();                                  // the active list overwrites h->order: launch_render ranks again
     HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
     const bool first = h->acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
     const int in = h->acc_cur, out = first ? 0 : 1 - in;

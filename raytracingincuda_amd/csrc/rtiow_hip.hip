@@ -128,11 +128,13 @@ int need_rng(rtiow_handle_s* h, const char* call) {
 }
 
 // What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
-// the temporal image and (clear_rng: camera, shard) the RNG states; (clear_base: scene, shard) the history base, which a new camera keeps.
+// the temporal image, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
+// (clear_base: scene, shard) the history base, which a new camera keeps.
 void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
 void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
     reset_accumulation(h);
     h->guides_ok = false; h->denoised_ok = false; h->hist_ok = false;
+    h->carried.clear();
     if (clear_rng) h->rng_ready = false;
     if (clear_base) h->hist_base_ok = false;
 }
@@ -201,6 +203,7 @@ int rtiow_create(int device, int precision, rtiow_handle* out) {
     }
     h->stats.num_cus = h->num_cus;
     if (const char* w = getenv("RTIOW_CLOCK_WARMUP_US")) { const int v = atoi(w); h->warmup_us = v > 0 && v <= 50000 ? v : 0; }
+    if (const char* w = getenv("RTIOW_ORDER_REUSE")) h->order_reuse = atoi(w) != 0;      // 0: every sorted render runs its prepass and ranks again
     // the clock stamps of the render launches (ColdParams::clock_stamps): 64 bytes of pinned host memory the device writes to; without them
     // (allocation refused) the stats fields stay 0
     {
@@ -256,6 +259,10 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
 
 int rtiow_set_camera(rtiow_handle h, const void* camera) {
     if (!h || !camera) return RTIOW_E_BADARG;
+    // the very camera the handle already has: the same frame, the carried order stays (everything else is reset as for any camera)
+    const bool same_camera = h->have_camera && std::memcmp(h->precision == 32 ? (const void*)&h->cam32 : (const void*)&h->cam64, camera,
+                                                           h->precision == 32 ? sizeof h->cam32 : sizeof h->cam64) == 0;
+    const CarriedOrder carried = h->carried;
     int W, H, S;
     if (h->precision == 32) { h->cam32 = *(const rtiow_camera_f32*)camera; W = h->cam32.img_width; H = h->cam32.img_height; S = h->cam32.samples_per_pixel; }
     else { h->cam64 = *(const rtiow_camera_f64*)camera; W = h->cam64.img_width; H = h->cam64.img_height; S = h->cam64.samples_per_pixel; }
@@ -264,6 +271,7 @@ int rtiow_set_camera(rtiow_handle h, const void* camera) {
     h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
     invalidate_frame(h, true, false);
+    if (same_camera) h->carried = carried;
     return 0;
 }
 
@@ -378,6 +386,12 @@ static int render_wait(rtiow_handle_s* h, float* kernel_ms) {
     if (kernel_ms) *kernel_ms = ms;
     h->stats.render_ms = ms;
     h->stats.prepass_ms = 0; h->stats.main_ms = ms; h->stats.place_ms = 0;
+    if (h->stats.phases == 1 && h->stats.staged_stores) {     // one launch in a carried order: the main launch, then place_pixels_kernel
+        float b = 0, c = 0;
+        HIP_TRY(h, hipEventElapsedTime(&b, h->ev0, h->ev_c));
+        HIP_TRY(h, hipEventElapsedTime(&c, h->ev_c, h->ev1));
+        h->stats.main_ms = b; h->stats.place_ms = c;
+    }
     if (h->stats.phases == 2) {
         float a = 0, b = 0, c = 0;
         HIP_TRY(h, hipEventElapsedTime(&a, h->ev0, h->ev_a));
@@ -870,7 +884,8 @@ int rtiow_debug_read_rng(rtiow_handle h, uint32_t* host_states, size_t count_wor
 int rtiow_debug_read_costs(rtiow_handle h, uint32_t* own, uint32_t* smoothed, size_t count) {
     if (!h || !own || !smoothed) return RTIOW_E_BADARG;
     const size_t npix = local_pixels(h);
-    if (h->stats.phases != 2 || !h->cost || !h->cost_rank) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_costs: the last render did not sort");
+    // the costs of the last ranking: the last render's own, or the ranking whose order it reused
+    if ((h->stats.phases != 2 && !h->stats.order_reused) || !h->cost || !h->cost_rank) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_costs: the last render did not sort");
     if (count < npix) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_costs: buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
