@@ -17,6 +17,31 @@ int rtiow_debug_read_rng(rtiow_handle h, uint32_t* host_states, size_t count_wor
  * the costs of the last ranking -- per local pixel the prepass cost (path segments of its prepass samples) and the key the sort
  * ranked it by (the mean of that cost over the pixel's neighbourhood inside its row strip, in quarter segments).  count = local pixels. */
 int rtiow_debug_read_costs(rtiow_handle h, uint32_t* own, uint32_t* smoothed, size_t count);
+/* The hand-out order itself: what h->order holds now, whoever wrote it last -- the ranking of a two-phase RTIOW_SCHED_SORTED render (also
+ * read after the renders that reused it, and after a counting run), the ranking of an rtiow_accumulate chunk, or the active list of an
+ * rtiow_accumulate_adaptive chunk.  The render kernels take their pixels from these very slots, so the tests can hold the order to its
+ * invariants (tests/test_handout_order.py): a permutation with padding only where the deal leaves holes, heavy first, neighbours adjacent.
+ *   info12  {kind (RTIOW_ORDER_*), total_slots, solo_slots, total_pools, pools_per_block, deal_group, lane_cap, blocks (workgroups of the
+ *           launch the order was dealt for), n_active (adaptive list), W, local_rows (the frame the order indexes), 0}: always written.
+ *   order   total_slots entries, slot -> (local row << 16 | column) or -1 (padding); an adaptive list: n_active pixels, then -1 up to the
+ *           next multiple of 64 (total_slots; 0 when nothing was active).  NULL: not wanted.
+ *   slot_of W x local_rows entries, pixel -> slot (RTIOW_ORDER_RENDER only; anything else: pass NULL).
+ *   keys    W x local_rows entries, what the ranking sorted by (the rankings only; an adaptive list: pass NULL).
+ * A first call with NULL buffers gives the sizes.  Waits for the stream.  RTIOW_E_STATE: nothing has written an order on this handle, or
+ * the order's buffers were reallocated since; RTIOW_E_BADARG: a buffer is too small or asks for what this kind of order does not have. */
+#define RTIOW_ORDER_NONE 0
+#define RTIOW_ORDER_RENDER 1
+#define RTIOW_ORDER_ACCUMULATE 2
+#define RTIOW_ORDER_ADAPTIVE 3
+int rtiow_debug_read_order(rtiow_handle h, int32_t* info12, int32_t* order, size_t order_cap, int32_t* slot_of, uint32_t* keys, size_t pixel_cap);
+/* The path segments every local pixel ran in the last rtiow_accumulate chunk: what the NEXT chunk's ranking smooths into its keys
+ * (rtiow_debug_read_order after that chunk).  A call of its own rather than a field of rtiow_debug_read_order: the first chunk after a
+ * reset is not ranked, so there is no order to read when its costs are wanted.  RTIOW_E_STATE without such a chunk since the last reset. */
+int rtiow_debug_read_chunk_costs(rtiow_handle h, uint32_t* costs, size_t count);
+/* Fill the staging buffer of the staged stores (finished pixels in slot order, gathered by place_pixels_kernel) with 0xff bytes -- NaN in
+ * both precisions -- on the handle's stream.  A slot the next render never hands out then shows in the image instead of keeping the bytes
+ * of the render before.  RTIOW_E_STATE when the handle has no staging buffer. */
+int rtiow_debug_poison_staged(rtiow_handle h);
 /* Per-wave timeline of one (untimed, counting) persistent render: 8 words per wave
  * {t_start, t_pool_exhausted, t_end (100 MHz ticks), iterations alone, iterations cooperative,
  * pixels taken, 0, 0}. */

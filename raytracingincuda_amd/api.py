@@ -102,8 +102,10 @@ HIP_SYMBOLS = [
 # include/rtiow_debug.h: exported by lib/librtiow_hip_debug.so (the test build) only
 DEBUG_SYMBOLS = [
     "rtiow_debug_read_rng", "rtiow_debug_read_costs", "rtiow_debug_timeline", "rtiow_debug_pixel_times", "rtiow_debug_ops", "rtiow_debug_jump_matrices", "rtiow_debug_grid_plan", "rtiow_debug_hit_world",
-    "rtiow_debug_gather_schedule",
+    "rtiow_debug_gather_schedule", "rtiow_debug_read_order", "rtiow_debug_read_chunk_costs", "rtiow_debug_poison_staged",
 ]
+ORDER_NONE, ORDER_RENDER, ORDER_ACCUMULATE, ORDER_ADAPTIVE = 0, 1, 2, 3     # rtiow_debug_read_order: info["kind"]
+ORDER_INFO_FIELDS = ("kind", "total_slots", "solo_slots", "total_pools", "pools_per_block", "deal_group", "lane_cap", "blocks", "n_active", "W", "local_rows")
 HOST_SYMBOLS = [
     "rtiow_host_scene_slots", "rtiow_host_build_scene", "rtiow_host_camera", "rtiow_host_camera_look", "rtiow_host_ppm_filename",
     "rtiow_host_write_ppm", "rtiow_host_format_ppm", "rtiow_host_write_ppm_binary", "rtiow_host_write_ppm_levels", "rtiow_host_levels", "rtiow_host_shard_rows", "rtiow_host_place_rows",
@@ -183,6 +185,10 @@ def load_hip_library(debug=False):
         if debug:
             lib.rtiow_debug_read_rng.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
             lib.rtiow_debug_read_costs.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
+            lib.rtiow_debug_read_order.argtypes = [H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
+            lib.rtiow_debug_read_chunk_costs.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
+            lib.rtiow_debug_poison_staged.argtypes = [H]
             lib.rtiow_debug_timeline.argtypes = [H, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
             lib.rtiow_debug_ops.argtypes = [H, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp]
             lib.rtiow_debug_gather_schedule.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -754,6 +760,37 @@ class Renderer:
         u32p = ctypes.POINTER(ctypes.c_uint32)
         self._check(self._lib.rtiow_debug_read_costs(self._h, own.ctypes.data_as(u32p), smoothed.ctypes.data_as(u32p), own.size))
         return own, smoothed
+
+    def debug_read_order(self):
+        """What the hand-out order buffer holds now (rtiow_debug_read_order): (info, order, slot_of, keys).  info: a dict of
+        ORDER_INFO_FIELDS; order: int32 [total_slots], slot -> (local row << 16 | column) or -1; slot_of: int32 [local_rows, W] for the
+        ranking of a render, else None; keys: uint32 [local_rows, W] for a ranking, None for an adaptive list.  Raises RtiowError
+        (RTIOW_E_STATE) when nothing has written an order."""
+        self._need_debug()
+        i32p, u32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
+        raw = np.zeros(12, np.int32)
+        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(i32p), None, 0, None, None, 0))
+        info = dict(zip(ORDER_INFO_FIELDS, (int(v) for v in raw)))
+        shape = (info["local_rows"], info["W"])
+        order = np.zeros(max(info["total_slots"], 1), np.int32)
+        slot_of = np.zeros(shape, np.int32) if info["kind"] == ORDER_RENDER else None
+        keys = np.zeros(shape, np.uint32) if info["kind"] in (ORDER_RENDER, ORDER_ACCUMULATE) else None
+        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(i32p), order.ctypes.data_as(i32p), order.size,
+                                                     slot_of.ctypes.data_as(i32p) if slot_of is not None else None,
+                                                     keys.ctypes.data_as(u32p) if keys is not None else None, shape[0] * shape[1]))
+        return info, order[:info["total_slots"]], slot_of, keys
+
+    def debug_read_chunk_costs(self):
+        """uint32 [local_rows, W]: the path segments each pixel ran in the last accumulate() chunk (the next chunk's ranking smooths them)."""
+        self._need_debug()
+        out = np.zeros((self.local_rows, self.width), np.uint32)
+        self._check(self._lib.rtiow_debug_read_chunk_costs(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), out.size))
+        return out
+
+    def debug_poison_staged(self):
+        """Fill the staging buffer of the sorted schedule's staged stores with 0xff bytes (NaN in both precisions), on the handle's stream."""
+        self._need_debug()
+        self._check(self._lib.rtiow_debug_poison_staged(self._h))
 
     def debug_timeline(self, threads=0):
         self._need_debug()

@@ -185,7 +185,7 @@ int size_persistent(rtiow_handle_s* h, Launch<T>& L, long long slots) {
 // and dealt into balanced pools, written to h->order (slot -> row << 16 | column, -1 for padding; the first solo_slots slots are the top
 // ranks) and, when slot_of is given, its inverse.  Blocks of the order are one "age class" of resident waves wide (see first_pools).
 // Needs h->order, h->cost_rank and h->sort_scratch sized for the frame.
-inline int rank_pixels(rtiow_handle_s* h, const uint32_t* cost, long long blocks, int waves_per_block, int total_pools, int solo_slots, int* slot_of) {
+inline int rank_pixels(rtiow_handle_s* h, const uint32_t* cost, long long blocks, int waves_per_block, int lane_cap, int total_pools, int solo_slots, int* slot_of) {
     const int W = img_w(h), npix = W * h->local_rows;
     unsigned* hist = h->sort_scratch; unsigned* start = hist + COST_BINS; unsigned* fill = start + COST_BINS;
     HIP_TRY(h, hipMemsetAsync(hist, 0, COST_BINS * sizeof(unsigned), h->stream));
@@ -229,6 +229,7 @@ inline int rank_pixels(rtiow_handle_s* h, const uint32_t* cost, long long blocks
     hipLaunchKernelGGL(cost_scatter_kernel, dim3(scatter_blocks), dim3(1024), 0, h->stream, rank_by, W, h->local_rows, start, fill, h->order,
                        pools_per_block, total_pools, deal_group, solo_slots, slot_of);
     HIP_TRY(h, hipGetLastError());
+    h->order_rec = OrderRecord{slot_of ? 1 : 2, total_pools * POOL + solo_slots, solo_slots, total_pools, pools_per_block, deal_group, lane_cap, (int)blocks, 0, W, h->local_rows};
     return 0;
 }
 
@@ -346,6 +347,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
             reused = !count && staged_stores && h->order_reuse && h->carried.usable(key);
             if (!reused) {
                 h->carried.clear();                      // the buffers below are about to be overwritten, perhaps reallocated
+                h->order_rec = OrderRecord{};
                 phases = 2;
                 HIP_TRY(h, h->mid.ensure((size_t)npix * sizeof(MidState<T>)));
                 HIP_TRY(h, h->cost.ensure((size_t)npix * sizeof(uint32_t)));
@@ -378,7 +380,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
                 h->stats.prepass_samples = SA;
                 HIP_TRY(h, hipGetLastError());
                 // ---- rank the pixels by measured cost, heavy first, dealt into balanced pools
-                if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, total_pools, solo_slots, staged_stores ? h->slot_of.as<int>() : nullptr))) return rc;
+                if ((rc = rank_pixels(h, h->cost, blocks, waves_per_block, lane_cap, total_pools, solo_slots, staged_stores ? h->slot_of.as<int>() : nullptr))) return rc;
                 if (!count && staged_stores) h->carried.store(key);
                 // ---- main launch: samples [SA, S) in that order
                 p.cold.s_begin = SA; p.cold.mid_in = h->mid;
@@ -454,6 +456,7 @@ int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
     const int total_pools = (npix + POOL - 1) / POOL;
     if (ranked) {
         h->carried.clear();                              // this chunk's ranking overwrites h->order: launch_render ranks again
+        h->order_rec = OrderRecord{};
         HIP_TRY(h, h->cost_rank.ensure((size_t)npix * sizeof(uint32_t)));
         HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
         HIP_TRY(h, h->sort_scratch.ensure((size_t)3 * COST_BINS * sizeof(unsigned)));
@@ -469,7 +472,7 @@ int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
     HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
     if (ranked) {
         // the previous chunk's segment counts rank this one (the launch below overwrites them: stream order)
-        if ((rc = rank_pixels(h, h->acc_cost, L.blocks, 4, total_pools, 0, nullptr))) return rc;
+        if ((rc = rank_pixels(h, h->acc_cost, L.blocks, 4, L.p.lane_cap, total_pools, 0, nullptr))) return rc;
         if ((rc = hand_out_ranked(h, L, total_pools, 0, 0))) return rc;
     }
     hipLaunchKernelGGL(L.k, dim3((unsigned)L.blocks), dim3(256), L.lds, h->stream, p);
@@ -500,6 +503,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
     HIP_TRY(h, h->adapt_err.ensure((size_t)npix * sizeof(float)));
     HIP_TRY(h, h->adapt_ctr.ensure(2 * sizeof(unsigned)));
     h->carried.clear();                                  // the active list overwrites h->order: launch_render ranks again
+    h->order_rec = OrderRecord{};
     HIP_TRY(h, h->order.ensure((size_t)total_pools * POOL * sizeof(int)));
     const bool first = h->acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
     const int in = h->acc_cur, out = first ? 0 : 1 - in;
@@ -517,6 +521,8 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
     HIP_TRY(h, hipMemcpyAsync(&n_active, h->adapt_ctr, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     active = (int)n_active;
+    h->order_rec.kind = 3; h->order_rec.n_active = active; h->order_rec.total_slots = (int)(((long long)n_active + POOL - 1) / POOL * POOL);
+    h->order_rec.total_pools = h->order_rec.total_slots / POOL; h->order_rec.W = W; h->order_rec.local_rows = h->local_rows;
     if (timed) HIP_TRY(h, hipEventRecord(h->ev_b, h->stream));
 
     if (n_active > 0) {
@@ -530,6 +536,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
         HIP_TRY(h, hipMemsetAsync(h->work_counter, 0, 2 * sizeof(unsigned int), h->stream));
         hipLaunchKernelGGL(L.k, dim3((unsigned)L.blocks), dim3(256), L.lds, h->stream, p);
         HIP_TRY(h, hipGetLastError());
+        h->order_rec.lane_cap = p.lane_cap; h->order_rec.blocks = (int)L.blocks;
     }
     hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (size_t)npix, (const unsigned char*)p.cold.mid_out,
                        p.cold.fb, h->adapt_counts, h->adapt_err, h->adapt_ctr + 1);

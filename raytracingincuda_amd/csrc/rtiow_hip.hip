@@ -894,6 +894,46 @@ int rtiow_debug_read_costs(rtiow_handle h, uint32_t* own, uint32_t* smoothed, si
     return 0;
 }
 
+int rtiow_debug_read_order(rtiow_handle h, int32_t* info12, int32_t* order, size_t order_cap, int32_t* slot_of, uint32_t* keys, size_t pixel_cap) {
+    if (!h || !info12) return RTIOW_E_BADARG;
+    const OrderRecord& rec = h->order_rec;
+    const bool ranking = rec.kind == RTIOW_ORDER_RENDER || rec.kind == RTIOW_ORDER_ACCUMULATE;
+    if (rec.kind == RTIOW_ORDER_NONE || !h->order || (ranking && !h->cost_rank) || (rec.kind == RTIOW_ORDER_RENDER && !h->slot_of))
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_order: no hand-out order has been written, or its buffers were dropped");
+    const int32_t info[12] = {rec.kind, rec.total_slots, rec.solo_slots, rec.total_pools, rec.pools_per_block, rec.deal_group,
+                              rec.lane_cap, rec.blocks, rec.n_active, rec.W, rec.local_rows, 0};
+    std::memcpy(info12, info, sizeof info);
+    const size_t slots = (size_t)rec.total_slots, npix = (size_t)rec.W * (size_t)rec.local_rows;
+    if ((order && order_cap < slots) || ((slot_of || keys) && pixel_cap < npix)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_order: buffer too small");
+    if ((slot_of && rec.kind != RTIOW_ORDER_RENDER) || (keys && !ranking)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_order: this order has no slot_of / no keys");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (order && slots) HIP_TRY(h, hipMemcpy(order, h->order, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (slot_of && npix) HIP_TRY(h, hipMemcpy(slot_of, h->slot_of, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (keys && npix) HIP_TRY(h, hipMemcpy(keys, h->cost_rank, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rtiow_debug_read_chunk_costs(rtiow_handle h, uint32_t* costs, size_t count) {
+    if (!h || !costs) return RTIOW_E_BADARG;
+    const size_t npix = local_pixels(h);
+    if (h->acc_mode != ACC_MODE_PLAIN || h->acc_samples <= 0 || !h->acc_cost || npix == 0)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_chunk_costs: no rtiow_accumulate chunk since the last reset");
+    if (count < npix) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_chunk_costs: buffer too small");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(costs, h->acc_cost, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rtiow_debug_poison_staged(rtiow_handle h) {
+    if (!h) return RTIOW_E_BADARG;
+    if (!h->staged || h->staged.bytes() == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_poison_staged: no staging buffer (no sorted render with staged stores yet)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemsetAsync(h->staged, 0xff, h->staged.bytes(), h->stream));
+    return 0;
+}
+
 int rtiow_debug_timeline(rtiow_handle h, int threads_per_block_row, uint64_t* out_words, size_t cap_words, int* waves) {
     if (!h || !out_words || !waves) return RTIOW_E_BADARG;
     if (h->schedule == RTIOW_SCHED_STATIC) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_timeline needs a persistent schedule");
