@@ -97,7 +97,7 @@ template <class T> struct ScreenParams {
 
 template <class T> struct RenderParams {
     int B, s_end;                     // bounce limit; this launch renders samples [cold.s_begin, s_end)
-    int lane_cap;                     // lanes of a wave that take pixels (64; fewer when the launch is underfilled, see launch_render)
+    int lane_cap;                     // lanes of a wave that take pixels (64; fewer when the launch is underfilled, see plan_size in library/launch_plan.h)
     int range_flags;                  // host-checked operand ranges.  bit 0 (primary_rays_in_range): |D|^2 of every primary ray lies well
                                       // inside [2^-80, 2^80]; bit 1 (scene_in_range): every coordinate of spheres and lens is below 2^18
     CameraParams<T> cam;              // read through cam_of

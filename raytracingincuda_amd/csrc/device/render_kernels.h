@@ -72,8 +72,8 @@ constexpr int POOL = 64;
 // chain's latency does: round 3 measured -5.6 % vector instructions and no time on the 1080p frame, -2...4 % on small frames and shards; with
 // round 4's shorter trips 1080p gains 1.8 %, 2560 x 1440 4.3 %, 3840 x 2160 2.2 %, 1280 x 720 loses 1-3 % (profiles/r04/ab_bounded_rounds_f32.jsonl,
 // ruv_rounds_sweep.jsonl).  The bound has to be a compile-time constant (the three rounds unroll; as a launch parameter the loop and its two extra
-// registers cost what the bound saves), so the fp32 main launch and prepass exist in both forms (template argument BOUND_F32) and launch_render
-// takes the bounded one when the launch has at least four 64-pixel pools per resident wave.
+// registers cost what the bound saves), so the fp32 main launch and prepass exist in both forms (template argument BOUND_F32) and the launch plan
+// (plan_size, library/launch_plan.h) takes the bounded one when the launch has at least four 64-pixel pools per resident wave.
 #ifndef RTIOW_RUV_ROUNDS_PER_ITERATION
 #define RTIOW_RUV_ROUNDS_PER_ITERATION 3
 #endif
@@ -171,7 +171,7 @@ __device__ __forceinline__ void persistent_body(const RenderParams<T>& p) {
                 if (m == 0) break;
                 if (pool_next >= pool_end) {     // refill the wave's pool: one atomic per 64 pixels
                     int base = 0, this_take = take;
-                    if (first_pool >= 0) {       // the first pool follows dispatch order (= wave age), see launch_render
+                    if (first_pool >= 0) {       // the first pool follows dispatch order (= wave age), see plan_deal in library/launch_plan.h
                         base = first_pool; this_take = first_take;
                         first_pool = -1;
                     } else {

@@ -4,6 +4,7 @@
 #pragma once
 #include "../device/params.h"
 #include "order_key.h"
+#include "launch_plan.h"
 
 // A device allocation owned by the handle or by one call: freed when it goes out of scope.  ensure() grows it to at least `bytes`
 // and never shrinks it; the old allocation is freed before the new one is made, so its contents are lost.
@@ -35,15 +36,6 @@ class DeviceBuffer {
     size_t bytes_ = 0;
 };
 
-// What wrote h->order last, for the test hook rtiow_debug_read_order (include/rtiow_debug.h): a few ints on the host, in every build.
-// kind: 0 nothing (or the buffers were reallocated since), 1 the ranking of a render (with slot_of), 2 the ranking of an rtiow_accumulate
-// chunk, 3 the active list of an adaptive chunk.  The rest: the parameters rank_pixels dealt by and the launch it dealt for; n_active and
-// total_slots of an adaptive list.
-struct OrderRecord {
-    int kind = 0, total_slots = 0, solo_slots = 0, total_pools = 0, pools_per_block = 0, deal_group = 0, lane_cap = 0, blocks = 0, n_active = 0;
-    int W = 0, local_rows = 0;                    // the local frame the order indexes
-};
-
 enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive
 
 struct rtiow_handle_s {
@@ -65,7 +57,7 @@ struct rtiow_handle_s {
     double ctr[3] = {0, 0, 0}, omax2 = 0;
     // uniform grid over the small spheres (RTIOW_SCENE_GRID; built with the screening table)
     DeviceBuffer<> grid_blob;
-    GridParams grid{};                            // offsets are relative to the blob until launch_render places it in LDS
+    GridParams grid{};                            // offsets are relative to the blob until layout_lds places it in LDS
     int grid_cells_bytes = 0, grid_aos_bytes = 0, grid_direct_bytes = 0, grid_ids_bytes = 0;
     int grid_direct = 0, grid_registered = 0;
     // camera
@@ -100,7 +92,7 @@ struct rtiow_handle_s {
     // launch once from sample 0 (order_key.h).  Cleared by whatever changes the cost map (scene, camera, shard: invalidate_frame) or
     // overwrites the two buffers (counting runs, rtiow_accumulate, rtiow_accumulate_adaptive); launch_render compares the key itself.
     CarriedOrder carried;
-    OrderRecord order_rec;                        // what `order` holds now (rank_pixels, launch_adaptive)
+    OrderRecord order_rec;                        // what `order` holds now (launch_plan.h: plan_ranking_record, plan_adaptive_record)
     bool order_reuse = true;                      // RTIOW_ORDER_REUSE=0 at rtiow_create: every sorted render ranks again (A/B runs, studies)
     // progressive rendering (rtiow_accumulate): samples accumulated since the last reset, the per-pixel MidState records of the last chunk
     // (two buffers, ping-pong: acc_mid[acc_cur] holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)

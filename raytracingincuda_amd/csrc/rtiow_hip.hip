@@ -479,7 +479,7 @@ int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, doub
     if (int rc = need_rng(h, "rtiow_accumulate_adaptive")) return rc;
     if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
         return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
-    if (!order_fits(h)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
+    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
     if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);

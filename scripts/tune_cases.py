@@ -1,4 +1,4 @@
-"""Interleaved timing of schedule knobs with the tuning build (lib/ab/tuning.so, -DRTIOW_TUNING: launch.h reads RTIOW_TUNE_<KNOB> from the
+"""Interleaved timing of schedule knobs with the tuning build (lib/ab/tuning.so, -DRTIOW_TUNING: launch_plan.h reads RTIOW_TUNE_<KNOB> from the
 environment).  Every case must render the same image.  Usage:
     tune_cases.py "PRE_STRIDE=1,SA=3;PRE_STRIDE=2,SA=3;..." [--rounds 3] [-- one_render args]"""
 import json, os, re, subprocess, sys

@@ -122,7 +122,7 @@ def rt(native):
 
 
 def _strip(rows, shard):
-    return shard[2] if shard else rows       # one rank: the window crosses its strips (rank_pixels)
+    return shard[2] if shard else rows       # one rank: the window crosses its strips (plan_deal)
 
 
 # ---- 3. the reference itself, on the CPU
@@ -173,16 +173,22 @@ def test_ranking_of_a_render(rt, prec, scene_id, W, H, S, B, shard, solo):
         r.render(0)
         assert r.stats()["phases"] == 2
         rows = r.local_rows
-        check_render_ranking(r, W, rows, _strip(rows, shard), solo)
+        info, _, _, _ = check_render_ranking(r, W, rows, _strip(rows, shard), solo)
+        if (prec, W, H, S, B, shard) == (32, 64, 64, 24, 40, None):
+            # the plan tests/native/launch_plan_main.cpp pins on the CPU is the plan the library made: these values hold on any device
+            # with more than 64 resident workgroups, whatever its occupancy
+            want = {"lane_cap": 16, "blocks": 64, "solo_slots": 128, "pools_per_block": 64, "deal_group": 1, "total_slots": 4224}
+            assert {k: info[k] for k in want} == want, info
+            assert r.stats()["prepass_samples"] == 2
 
 
 # ---- (b) the coarse deal
 
-# How the size was found: rank_pixels deals whole pools (deal_group 64) from 2.5 pools per resident wave on.  A full fp32 launch on the
-# MI355X is 1280 workgroups (the hook's `blocks`: 256 CUs x 5, five dispatch-age classes of 1024 waves), 5120 resident waves, so the
-# order needs 12800 pools = 819200 pixels; 1280 x 720 has 14400.  Scanning 16:9 frames in steps of 16 columns with the hook (960 x 540 ...
-# 1408 x 792 at S 24, B 4), 1200 x 675 (12657 pools) and everything below report deal_group 1, the frame below (12996 pools) and everything
-# above report 64; the render takes 1.4 ms.
+# The size: plan_deal (csrc/library/launch_plan.h) deals whole pools (deal_group 64) from 2.5 pools per resident wave on.  A full fp32
+# launch on the MI355X is 1280 workgroups (the hook's `blocks`: 256 CUs x 5, five dispatch-age classes of 1024 waves), 5120 resident waves,
+# so the order needs 12800 pools = 819200 pixels; 1280 x 720 has 14400.  Of the 16:9 frames in steps of 16 columns, 1200 x 675 (12657 pools,
+# 2.47 per wave) is the last with deal_group 1 and the frame below (12996 pools, 2.54 per wave) the first with 64: tests/native/launch_plan_main.cpp
+# pins both plans on the CPU, and a scan with the hook on the device (960 x 540 ... 1408 x 792 at S 24, B 4) agreed; the render takes 1.4 ms.
 COARSE_W, COARSE_H = 1216, 684
 
 
@@ -357,7 +363,7 @@ def test_adaptive_active_list(rt, prec, W, H, shard):
 
 # ---- (g) exactly once, counted
 
-# Counting runs use no solo waves (launch_render), so the solo kernel's hand-out is not counted here: that every one of ITS slots is
+# Counting runs use no solo waves (plan_sorted), so the solo kernel's hand-out is not counted here: that every one of ITS slots is
 # written exactly where slot_of looks stays with test_a_reused_order_writes_every_slot above.
 @gpu
 @pytest.mark.parametrize("sched", [1, 2])          # RTIOW_SCHED_PERSISTENT, RTIOW_SCHED_SORTED

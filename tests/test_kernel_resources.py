@@ -41,7 +41,7 @@ def test_main_launch_register_budget(kernel_metadata):
     # the kernels bench.py times: LDS scene source (template argument 0), no counting
     f32 = _find(meta, "render_persistent_kernel<float, 0, false, false>")
     assert f32["sgpr_spill"] <= 6 and f32["vgpr"] <= 96, f32        # five waves per SIMD
-    # the same kernel with the bounded rejection loop (full frames: launch_render takes it at >= 4 pools per resident wave)
+    # the same kernel with the bounded rejection loop (full frames: plan_size, launch_plan.h, takes it at >= 4 pools per resident wave)
     f32b = _find(meta, "render_persistent_kernel<float, 0, false, true>")
     assert f32b["sgpr_spill"] <= 6 and f32b["vgpr"] <= 96, f32b
     pre = _find(meta, "render_prepass_kernel<float, 0, false, false>")
