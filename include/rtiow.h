@@ -360,6 +360,43 @@ int rtiow_read_history(rtiow_handle h, void* rgb /* npix*3 T, linear */, void* l
 int rtiow_history_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);   /* npix x 4 T: {C.rgb, M} */
 int rtiow_denoise_history(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms);
 
+/* ---- Filter guides that follow mirrors and glass to the first diffuse surface.  The handle has two sets
+ * of guides.  The FIRST-HIT guides are those of rtiow_render_guides / rtiow_read_guides above, in either mode; rtiow_history_update and
+ * rtiow_history_commit use them alone (reprojection needs the real first surface).  The FILTER guides are what rtiow_denoise,
+ * rtiow_denoise_variance and rtiow_denoise_history steer by.  RTIOW_GUIDES_FIRST_HIT (default): they are the first-hit buffers
+ * themselves -- no extra memory, no extra launch, every output as without this call.  RTIOW_GUIDES_SPECULAR: a second pair of buffers,
+ * allocated at first use and written wherever the first-hit guides are rendered (rtiow_render_guides, and the stale guides a filter
+ * or rtiow_history_update renders first), by following each pixel's centre ray through the specular surfaces it meets:
+ *
+ * Everything in T, left to right as written, plain * + - / and a correctly rounded sqrt, no fused multiply-add.  O_0, D_0 = the ray of
+ * rtiow_render_guides; A = {1,1,1}, Z = 0, b = 0.  Repeat (t, k) = hit_world(O_b, D_b) (D for D_b below):
+ *   miss, b == 0: normal' = albedo' = 0, depth' = 0.   miss, b > 0: normal' = 0, albedo' = A, depth' = Z.
+ *   hit: P = O_b + t D, outward = (P - C_k) * ((T)1 / r_k), dn = (D.x o.x + D.y o.y) + D.z o.z, front = dn < 0, N = front ? outward :
+ *   -outward; a_k = the material's {r,g,b}, {1,1,1} for a dielectric.  The surface is specular when it is a dielectric, or a metal with
+ *   (double)fuzz_k <= max_fuzz.  Not specular, or b == max_bounces: normal' = N, albedo' = A a_k per channel (A for a dielectric),
+ *   depth' = Z + t, and the chain ends.  Otherwise A = A a_k (A kept for a dielectric), Z = Z + t, O_(b+1) = P, b = b + 1 and
+ *     metal:      dN = (D.x N.x + D.y N.y) + D.z N.z, c2 = 2 dN, D' = D - c2 N per component;
+ *     dielectric: dd = (D.x D.x + D.y D.y) + D.z D.z, len = sqrt(dd), il = 1 / len, u = D il, m = -((u.x N.x + u.y N.y) + u.z N.z),
+ *                 ct = m < 1 ? m : 1, st = sqrt(1 - ct ct), ri = front ? (T)1 / eta_k (as the shade table holds it) : eta_k;
+ *                 ri st > 1 (total internal reflection): c2 = 2 (-ct), r = u - c2 N;  else perp = ri (u + ct N) per component,
+ *                 kk = -sqrt(|1 - ((perp.x perp.x + perp.y perp.y) + perp.z perp.z)|), r = perp + kk N;  D' = r len.
+ * Schlick's reflectance is not consulted: the refracted branch is taken whenever there is one.  Through `len` every t of a chain is in
+ * the units of the primary ray, so depth' compares with the first-hit depth.  bounces = b at the end.  A sky seen in a mirror has the
+ * colour A x (the primary ray's sky), hence albedo' = A on a miss.
+ *
+ * rtiow_set_guide_mode is a knob like rtiow_set_scene_source: it survives rtiow_set_scene, rtiow_set_camera and rtiow_set_shard.  A call
+ * that changes nothing does nothing; one that changes mode, max_bounces or max_fuzz makes the guides (both sets: rtiow_read_guides too
+ * returns RTIOW_E_STATE until they are rendered again) and the denoised image stale and leaves the accumulation, the history base and
+ * the temporal image alone.  RTIOW_E_BADARG: a mode other than 0 or 1; in mode 1 max_bounces outside 1..16, max_fuzz < 0 or NaN (+inf:
+ * every metal is a mirror).  In mode 0 the other arguments are ignored.
+ * rtiow_read_filter_guides copies the filter guides as planes: arguments, RTIOW_E_STATE when stale, layout and shards as
+ * rtiow_read_guides, plus bounces (npix int32); any pointer may be NULL.  In mode 0 it gives the first-hit planes and bounces = 0. */
+#define RTIOW_GUIDES_FIRST_HIT 0   /* default: the filters steer by the first-hit guides */
+#define RTIOW_GUIDES_SPECULAR  1
+int rtiow_set_guide_mode(rtiow_handle h, int mode /* RTIOW_GUIDES_* */, int max_bounces, double max_fuzz);
+int rtiow_read_filter_guides(rtiow_handle h, void* normal /* npix*3 T */, void* albedo /* npix*3 T */, void* depth /* npix T */,
+                             int32_t* bounces /* npix */, size_t npix);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

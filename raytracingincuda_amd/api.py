@@ -25,6 +25,7 @@ LAMBERTIAN, METAL, DIELECTRIC = 0, 1, 2
 SCENE_LDS, SCENE_SCALAR, SCENE_LDS_EXACT, SCENE_GRID = 0, 1, 2, 3
 SCHED_STATIC, SCHED_PERSISTENT, SCHED_SORTED = 0, 1, 2
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER, GATHER_HOST = 0, 1, 2, 3
+GUIDES_FIRST_HIT, GUIDES_SPECULAR = 0, 1  # rtiow_set_guide_mode
 GROUP_MAX_STATS = 16
 ABI_VERSION = 6          # include/rtiow.h RTIOW_ABI_VERSION
 
@@ -94,6 +95,7 @@ HIP_SYMBOLS = [
     "rtiow_read_linear", "rtiow_render_guides", "rtiow_read_guides", "rtiow_denoise", "rtiow_read_denoised", "rtiow_denoised_device_ptr",
     "rtiow_read_variance", "rtiow_denoise_variance",
     "rtiow_history_reset", "rtiow_history_update", "rtiow_history_commit", "rtiow_read_history", "rtiow_history_device_ptr", "rtiow_denoise_history",
+    "rtiow_set_guide_mode", "rtiow_read_filter_guides",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -217,6 +219,8 @@ def load_hip_library(debug=False):
         lib.rtiow_read_history.argtypes = [H, vp, vp, ctypes.c_size_t]
         lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+        lib.rtiow_read_filter_guides.argtypes = [H, vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t]
         G = ctypes.c_void_p
         lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
         lib.rtiow_group_create_error.argtypes = []
@@ -418,6 +422,12 @@ DENOISE_SIGMA_VARIANCE = 4.5
 HISTORY_DEPTH_TOL = 0.1
 HISTORY_NORMAL_COS = 0.9
 HISTORY_MAX = 16.0
+# The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
+# to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
+# section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
+# first-hit guides on both scenes, which is why GUIDES_FIRST_HIT stays the mode a handle starts in.
+GUIDE_MAX_BOUNCES = 1
+GUIDE_MAX_FUZZ = 0.0
 
 
 class Renderer:
@@ -615,6 +625,29 @@ class Renderer:
             rc = self._lib.rtiow_read_guides(self._h, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, rows * w)
         self._check(rc)
         return normal, albedo, depth
+
+    def set_guide_mode(self, mode, max_bounces=GUIDE_MAX_BOUNCES, max_fuzz=GUIDE_MAX_FUZZ):
+        """What denoise(), denoise_variance() and denoise_history() steer by.  GUIDES_FIRST_HIT (default): the
+        first-hit guides.  GUIDES_SPECULAR: guides that follow each centre ray through glass and through metals with fuzz <= max_fuzz
+        (float("inf"): every metal) to the first other surface, at most max_bounces (1..16) times.  The history calls keep the first-hit
+        guides.  A change makes the guides and the denoised image stale; the knob survives set_scene, set_camera and set_shard."""
+        self._check(self._lib.rtiow_set_guide_mode(self._h, int(mode), int(max_bounces), float(max_fuzz)))
+
+    def filter_guides(self):
+        """(normal [rows, W, 3], albedo [rows, W, 3], depth [rows, W], bounces [rows, W] int32) of the guides the filters read: guides()
+        and zeros in GUIDES_FIRST_HIT mode, the end of each pixel's specular chain in GUIDES_SPECULAR mode.  Renders stale guides first."""
+        rows, w = self.local_rows, self.width
+        normal = np.empty((rows, w, 3), self.dtype)
+        albedo = np.empty((rows, w, 3), self.dtype)
+        depth = np.empty((rows, w), self.dtype)
+        bounces = np.empty((rows, w), np.int32)
+        args = (normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, bounces.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), rows * w)
+        rc = self._lib.rtiow_read_filter_guides(self._h, *args)
+        if rc == -2:                                     # RTIOW_E_STATE: stale or never rendered
+            self.render_guides()
+            rc = self._lib.rtiow_read_filter_guides(self._h, *args)
+        self._check(rc)
+        return normal, albedo, depth, bounces
 
     def denoise(self, levels=DENOISE_LEVELS, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
                 sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, sync=True):

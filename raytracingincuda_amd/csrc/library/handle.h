@@ -115,6 +115,13 @@ struct rtiow_handle_s {
     DeviceBuffer<> dn_tmp[2];
     DeviceBuffer<> denoised;
     bool denoised_ok = false;
+    // filter guides (rtiow_set_guide_mode): what the three filters steer by.  RTIOW_GUIDES_FIRST_HIT: guide_nd / guide_alb themselves.
+    // RTIOW_GUIDES_SPECULAR: the specular chain's {normal', depth'} and {albedo', (T)bounces}, 4 T per pixel each, allocated at first use
+    // and written wherever the first-hit guides are (guides_ok covers both sets).  The knob survives set_scene / _camera / _shard.
+    int guide_mode = RTIOW_GUIDES_FIRST_HIT;
+    int guide_max_bounces = 0;
+    double guide_max_fuzz = 0;
+    DeviceBuffer<> chain_nd, chain_alb;
     // variance-guided denoising (rtiow_read_variance / rtiow_denoise_variance), allocated at first use: the variance plane of the adaptive
     // accumulation (1 T per pixel, rewritten by every call) and the filter's two ping-pong variance planes
     DeviceBuffer<> variance;
@@ -182,6 +189,10 @@ template <class F>
 auto by_precision(const rtiow_handle_s* h, F f) { return h->precision == 32 ? f(float()) : f(double()); }
 
 size_t local_pixels(const rtiow_handle_s* h) { return (size_t)img_w(h) * h->local_rows; }
+// The guides the filters read (rtiow_denoise, rtiow_denoise_variance, rtiow_denoise_history): the first-hit buffers themselves, or the
+// specular chain's.  The history launch and the commit's swap use guide_nd whatever the mode.
+const DeviceBuffer<>& filter_nd(const rtiow_handle_s* h) { return h->guide_mode == RTIOW_GUIDES_SPECULAR ? h->chain_nd : h->guide_nd; }
+const DeviceBuffer<>& filter_alb(const rtiow_handle_s* h) { return h->guide_mode == RTIOW_GUIDES_SPECULAR ? h->chain_alb : h->guide_alb; }
 size_t image_bytes(const rtiow_handle_s* h) { return local_pixels(h) * 3 * elem_size(h); }          // the local image, 3 T per pixel
 
 int ensure_framebuffer(rtiow_handle_s* h) {

@@ -10,6 +10,7 @@
 #include "../device/adaptive.h"
 #include "../device/cost_sort.h"
 #include "../device/denoise.h"
+#include "../device/guide_chain.h"
 #include "../device/denoise_variance.h"
 #include "../device/history.h"
 
@@ -454,6 +455,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
 
 // First-hit guides of every local pixel (rtiow_render_guides) into h->guide_nd / h->guide_alb: guide_kernel with the scene staged as
 // the render launches stage it (layout_lds of a non-persistent launch: no drain scratch), one 8x8 tile per wave, four waves a workgroup.
+// RTIOW_GUIDES_SPECULAR: guide_chain_kernel follows on the same layout and grid and writes the filter guides to h->chain_nd / h->chain_alb.
 template <class T>
 int launch_guides(rtiow_handle_s* h) {
     Launch<T> L{make_params<T>(h)};
@@ -468,6 +470,15 @@ int launch_guides(rtiow_handle_s* h) {
     const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_nd.as<T>(), h->guide_alb.as<T>());
     HIP_TRY(h, hipGetLastError());
+    if (h->guide_mode == RTIOW_GUIDES_SPECULAR) {
+        HIP_TRY(h, h->chain_nd.ensure(npix * 4 * sizeof(T)));
+        HIP_TRY(h, h->chain_alb.ensure(npix * 4 * sizeof(T)));
+        const auto kc = by_source(L.lds_source, [](auto src) { return guide_chain_kernel<T, src>; });
+        HIP_TRY(h, allow_lds(kc, L.lds));
+        hipLaunchKernelGGL(kc, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_max_bounces, h->guide_max_fuzz,
+                           h->chain_nd.as<T>(), h->chain_alb.as<T>());
+        HIP_TRY(h, hipGetLastError());
+    }
     h->guides_ok = true;
     return 0;
 }
@@ -494,7 +505,7 @@ int launch_linear(rtiow_handle_s* h) {
 // `levels` launches of denoise_level_kernel over the accumulation (rtiow_denoise): level 0 reads the records, the levels ping-pong through
 // h->dn_tmp[0/1], the last writes the gamma-encoded image to h->denoised.  inv2[4] = 1 / sigma^2 of colour, normal, albedo, depth (double);
 // the colour term of level k is scaled by 4^k and every weight is rounded to T here.  The caller has checked state and arguments and
-// made the guides current.
+// made the guides current.  The guides are the handle's filter guides (filter_nd / filter_alb), here and in launch_denoise_variance.
 // from_history: level 0 reads the temporal colour plane h->hist_rgb instead (rtiow_denoise_history).
 template <class T>
 int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool from_history = false) {
@@ -514,7 +525,7 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool fro
         const T* cin = k == 0 ? (from_history ? h->hist_rgb.as<const T>() : nullptr) : h->dn_tmp[(k - 1) & 1].as<const T>();
         T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
         hipLaunchKernelGGL(denoise_level_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, 1 << k, fw, records ? mid : nullptr,
-                           counts, n_uniform, cin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, last ? 1 : 0);
+                           counts, n_uniform, cin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
     h->denoised_ok = true;
@@ -627,7 +638,7 @@ int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance
         const auto kernel = tiled ? variance_tile_kernel<T> : variance_filter_kernel<T>;
         HIP_TRY(h, allow_lds(kernel, lds));
         hipLaunchKernelGGL(kernel, grid, dim3(256), lds, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
-                           (const int32_t*)h->adapt_counts, cin, vin, h->guide_nd.as<const T>(), h->guide_alb.as<const T>(), cout, vout, last ? 1 : 0);
+                           (const int32_t*)h->adapt_counts, cin, vin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, vout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
     h->denoised_ok = true;

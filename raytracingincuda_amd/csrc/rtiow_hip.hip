@@ -64,6 +64,7 @@
 #include "device/denoise.h"
 #include "device/denoise_variance.h"
 #include "device/history.h"
+#include "device/guide_chain.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -131,9 +132,12 @@ int need_rng(rtiow_handle_s* h, const char* call) {
 // the temporal image, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
 // (clear_base: scene, shard) the history base, which a new camera keeps.
 void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
+// A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
+void invalidate_guides(rtiow_handle_s* h) { h->guides_ok = false; h->denoised_ok = false; }
 void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
     reset_accumulation(h);
-    h->guides_ok = false; h->denoised_ok = false; h->hist_ok = false;
+    invalidate_guides(h);
+    h->hist_ok = false;
     h->carried.clear();
     if (clear_rng) h->rng_ready = false;
     if (clear_base) h->hist_base_ok = false;
@@ -559,24 +563,68 @@ int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
     return timed_end(h, kernel_ms);
 }
 
-int rtiow_read_guides(rtiow_handle h, void* normal, void* albedo, void* depth, size_t npix) {
-    if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera || !h->guides_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_guides: no guides for the current scene, camera and shard (rtiow_render_guides)");
+namespace {
+// The planes of a pair of guide buffers, {n.xyz, depth} and {albedo.rgb, x} per pixel, for rtiow_read_guides and
+// rtiow_read_filter_guides (`call`); bounces: (int)x of the filter guides, 0 when they are the first-hit buffers (from_chain false).
+int read_guide_planes(rtiow_handle_s* h, const char* call, const void* dev_nd, const void* dev_alb, bool from_chain, void* normal, void* albedo,
+                      void* depth, int32_t* bounces, size_t npix) {
+    if (!h->have_camera || !h->guides_ok)
+        return fail_arg(h, RTIOW_E_STATE, (std::string(call) + ": no guides for the current scene, camera and shard (rtiow_render_guides)").c_str());
     const size_t want = local_pixels(h);
-    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_guides: npix must be local_rows x width");
-    if (want == 0 || (!normal && !albedo && !depth)) return 0;
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": npix must be local_rows x width").c_str());
+    if (want == 0 || (!normal && !albedo && !depth && !bounces)) return 0;
+    if (bounces && !from_chain) std::memset(bounces, 0, want * sizeof(int32_t));
+    const bool need_alb = albedo || (bounces && from_chain);
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h);
-    std::vector<unsigned char> nd(normal || depth ? want * 4 * es : 0), alb(albedo ? want * 4 * es : 0);
-    if (normal || depth) HIP_TRY(h, hipMemcpyAsync(nd.data(), h->guide_nd, nd.size(), hipMemcpyDeviceToHost, h->stream));
-    if (albedo) HIP_TRY(h, hipMemcpyAsync(alb.data(), h->guide_alb, alb.size(), hipMemcpyDeviceToHost, h->stream));
+    std::vector<unsigned char> nd(normal || depth ? want * 4 * es : 0), alb(need_alb ? want * 4 * es : 0);
+    if (normal || depth) HIP_TRY(h, hipMemcpyAsync(nd.data(), dev_nd, nd.size(), hipMemcpyDeviceToHost, h->stream));
+    if (need_alb) HIP_TRY(h, hipMemcpyAsync(alb.data(), dev_alb, alb.size(), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (size_t k = 0; k < want; ++k) {                  // {n.xyz, depth} and {albedo.rgb, 0} -> planes
+    for (size_t k = 0; k < want; ++k) {                  // {n.xyz, depth} and {albedo.rgb, x} -> planes
         if (normal) std::memcpy((unsigned char*)normal + 3 * k * es, nd.data() + 4 * k * es, 3 * es);
         if (depth) std::memcpy((unsigned char*)depth + k * es, nd.data() + (4 * k + 3) * es, es);
         if (albedo) std::memcpy((unsigned char*)albedo + 3 * k * es, alb.data() + 4 * k * es, 3 * es);
+        if (bounces && from_chain) {
+            const unsigned char* x = alb.data() + (4 * k + 3) * es;
+            if (es == 4) { float v; std::memcpy(&v, x, 4); bounces[k] = (int32_t)v; }
+            else { double v; std::memcpy(&v, x, 8); bounces[k] = (int32_t)v; }
+        }
     }
     return 0;
+}
+}  // namespace
+
+int rtiow_read_guides(rtiow_handle h, void* normal, void* albedo, void* depth, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    return read_guide_planes(h, "rtiow_read_guides", h->guide_nd, h->guide_alb, false, normal, albedo, depth, nullptr, npix);
+}
+
+// ---- Filter guides
+int rtiow_set_guide_mode(rtiow_handle h, int mode, int max_bounces, double max_fuzz) {
+    if (!h) return RTIOW_E_BADARG;
+    if (mode != RTIOW_GUIDES_FIRST_HIT && mode != RTIOW_GUIDES_SPECULAR) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_guide_mode: unknown mode");
+    if (mode == RTIOW_GUIDES_FIRST_HIT) {                // the arguments are ignored
+        if (h->guide_mode == RTIOW_GUIDES_FIRST_HIT) return 0;
+        h->guide_mode = RTIOW_GUIDES_FIRST_HIT;
+        invalidate_guides(h);
+        HIP_TRY(h, hipSetDevice(h->device));             // the first-hit buffers are the filter guides again: no second pair is kept
+        HIP_TRY(h, h->chain_nd.reset());
+        HIP_TRY(h, h->chain_alb.reset());
+        return 0;
+    }
+    if (max_bounces < 1 || max_bounces > 16 || !(max_fuzz >= 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_guide_mode: need max_bounces in 1..16 and max_fuzz >= 0 (+inf: every metal is a mirror)");
+    if (h->guide_mode == mode && h->guide_max_bounces == max_bounces && h->guide_max_fuzz == max_fuzz) return 0;
+    h->guide_mode = mode; h->guide_max_bounces = max_bounces; h->guide_max_fuzz = max_fuzz;
+    invalidate_guides(h);
+    return 0;
+}
+
+int rtiow_read_filter_guides(rtiow_handle h, void* normal, void* albedo, void* depth, int32_t* bounces, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    return read_guide_planes(h, "rtiow_read_filter_guides", filter_nd(h), filter_alb(h), h->guide_mode == RTIOW_GUIDES_SPECULAR, normal, albedo, depth,
+                             bounces, npix);
 }
 
 int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
