@@ -397,6 +397,39 @@ int rtiow_set_guide_mode(rtiow_handle h, int mode /* RTIOW_GUIDES_* */, int max_
 int rtiow_read_filter_guides(rtiow_handle h, void* normal /* npix*3 T */, void* albedo /* npix*3 T */, void* depth /* npix T */,
                              int32_t* bounces /* npix */, size_t npix);
 
+/* ---- History-guided sample budgets: sample where the history is short.  After a camera move most pixels
+ * will carry up to max_history samples from the base; the few that were just disoccluded will carry none.  Which is which is known
+ * before the first sample of the new frame is traced, because the history length m of rtiow_history_update depends on the current
+ * camera, the first-hit guides and the base alone, not on the accumulation.
+ * rtiow_history_plan computes the PLAN: for every pixel p, m_p = the m of the block above, to the letter -- the ray, the reprojection,
+ * te, the four taps, the tests on M_q, depth'_q and the normals, L / Bs and min(m, (T)max_history), in T with plain * + - /, floor and
+ * fabs -- and 0 in every case listed there as "no taps".  An empty base or a base of another frame size gives m = 0 everywhere, not an
+ * error.  *reprojected_pixels (may be NULL) = the pixels with m_p > 0.  An rtiow_history_update with the same three arguments later
+ * gives Mout = m_p + (T)n_p bit for bit.  Arguments, their errors, the rendering of stale guides inside kernel_ms and the asynchronous
+ * form (both pointers NULL) are rtiow_history_update's.  It needs scene and camera (else RTIOW_E_STATE), no RNG and no chunk; RTIOW_E_STATE
+ * on a sharded handle.
+ * The plan goes stale exactly when the temporal image does -- rtiow_set_camera, rtiow_set_scene, rtiow_set_shard, rtiow_history_reset,
+ * rtiow_history_commit -- and survives rtiow_init_rng, rtiow_accumulate_reset, rtiow_set_guide_mode (it uses the first-hit guides) and
+ * every chunk.  rtiow_read_history_plan copies it (npix T, npix = height x width; NULL: only the checks): RTIOW_E_STATE when stale.
+ *
+ * rtiow_accumulate_budget is rtiow_accumulate_adaptive with another rule.  A local pixel is active iff
+ *     (n_p < min_samples  or  (T)n_p + m_p < (T)target)  and  n_p + samples <= max_samples
+ * with the sum and the comparison in T and n_p = 0 in the first chunk after a reset.  Everything else is that call's: inactive pixels
+ * are not traced, the whole preview is rewritten, every pixel holds the bits rtiow_render leaves at samples_per_pixel = n_p (never
+ * sampled: 0), the second moment and err_p are kept (rtiow_read_adaptive_state, rtiow_read_variance, rtiow_denoise_variance work
+ * afterwards), one blocking read-back of the active count, kernel_ms, and *active_pixels == 0 meaning that nothing but the finish was
+ * launched.  The chunk belongs to the adaptive mode: it alternates freely with rtiow_accumulate_adaptive between two resets and returns
+ * RTIOW_E_STATE after plain chunks.  RTIOW_E_STATE also when the plan is stale or scene, camera and RNG are not set up.  RTIOW_E_BADARG:
+ * samples <= 0, min_samples < 0, max_samples < min_samples, target <= 0 or NaN (+inf: everybody, up to max_samples), or a frame beyond
+ * rtiow_accumulate_adaptive's limits.  A failing call leaves the handle as it was.
+ * The loop of a moving camera: rtiow_set_camera, rtiow_init_rng, rtiow_history_plan, rtiow_accumulate_budget until *active_pixels == 0,
+ * rtiow_history_update with the plan's three arguments, rtiow_history_commit.  With max_history < target no pixel ever reaches the
+ * target and every frame adds target - max_history samples to a fully covered pixel; with min_samples = 0 a pixel whose m_p reaches
+ * the target is not sampled at all and Cout there is the gathered history h.  Not available on groups. */
+int rtiow_history_plan(rtiow_handle h, double depth_tol, double normal_cos, double max_history, float* kernel_ms, uint64_t* reprojected_pixels);
+int rtiow_read_history_plan(rtiow_handle h, void* length /* npix T */, size_t npix);
+int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -96,6 +96,7 @@ HIP_SYMBOLS = [
     "rtiow_read_variance", "rtiow_denoise_variance",
     "rtiow_history_reset", "rtiow_history_update", "rtiow_history_commit", "rtiow_read_history", "rtiow_history_device_ptr", "rtiow_denoise_history",
     "rtiow_set_guide_mode", "rtiow_read_filter_guides",
+    "rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -217,6 +218,10 @@ def load_hip_library(debug=False):
         lib.rtiow_history_update.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
         lib.rtiow_history_commit.argtypes = [H]
         lib.rtiow_read_history.argtypes = [H, vp, vp, ctypes.c_size_t]
+        lib.rtiow_history_plan.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
+        lib.rtiow_read_history_plan.argtypes = [H, vp, ctypes.c_size_t]
+        lib.rtiow_accumulate_budget.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
         lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
@@ -422,6 +427,14 @@ DENOISE_SIGMA_VARIANCE = 4.5
 HISTORY_DEPTH_TOL = 0.1
 HISTORY_NORMAL_COS = 0.9
 HISTORY_MAX = 16.0
+# Renderer.accumulate_budget defaults (with history_plan at the history defaults above): the eligible setting of
+# scripts/history_budget_probe.py's sweep with the smallest worse-of-two-scenes ratio of whole-frame MSE to the uniform walk's, on the
+# walk above; eligible: no more primary rays than that walk.  At these the disoccluded pixels' MSE is a quarter of the uniform walk's
+# and the whole frame's is 1.14 to 1.21 times it: no eligible setting lowers the whole frame's
+# (profiles/history_budget/history_budget_probe.json).
+BUDGET_TARGET = 16.0
+BUDGET_MIN_SAMPLES = 1
+BUDGET_CHUNK = 2
 # The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
 # to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
 # section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
@@ -696,6 +709,35 @@ class Renderer:
         ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
         self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
         return int(n.value)
+
+    def history_plan(self, depth_tol=HISTORY_DEPTH_TOL, normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
+        """The history length every pixel of the current camera will carry: history_update()'s m for the
+        same three arguments, before any sample of the frame is traced.  It needs scene and camera only, is what accumulate_budget()
+        samples by, and goes stale with the temporal image.  Returns the number of pixels with m > 0 (None when sync=False)."""
+        if not sync:
+            self._check(self._lib.rtiow_history_plan(self._h, float(depth_tol), float(normal_cos), float(max_history), None, None))
+            return None
+        ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
+        self._check(self._lib.rtiow_history_plan(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
+        return int(n.value)
+
+    def history_plan_lengths(self):
+        """The plan of history_plan(), [H, W]: each pixel's history length m in samples."""
+        length = np.empty((self.local_rows, self.width), self.dtype)
+        self._check(self._lib.rtiow_read_history_plan(self._h, length.ctypes.data, length.size))
+        return length
+
+    def accumulate_budget(self, samples=BUDGET_CHUNK, target=BUDGET_TARGET, min_samples=BUDGET_MIN_SAMPLES, max_samples=2 ** 31 - 1, sync=True):
+        """accumulate_adaptive() with the rule of INTEGRATION.md section 13: `samples` more samples for every pixel whose count is below
+        min_samples or whose count plus planned history length (history_plan) is below target, and count + samples <= max_samples.
+        The loop of a moving camera: set_camera, init_rng, history_plan, accumulate_budget until it returns 0 active pixels,
+        history_update with the plan's arguments, history_commit.  Alternates freely with accumulate_adaptive().  Returns (kernel ms or
+        None when sync=False, active pixels)."""
+        active = ctypes.c_int(0)
+        ms = ctypes.c_float(0)
+        self._check(self._lib.rtiow_accumulate_budget(self._h, int(samples), int(min_samples), float(target), int(max_samples),
+                                                      ctypes.byref(ms) if sync else None, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
 
     def history_commit(self):
         """Make the temporal image, the current guides and the current camera the base of later updates (buffers change owners, nothing

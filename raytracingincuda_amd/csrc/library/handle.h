@@ -36,7 +36,7 @@ class DeviceBuffer {
     size_t bytes_ = 0;
 };
 
-enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive
+enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive / _budget
 
 struct rtiow_handle_s {
     int device = 0;
@@ -138,6 +138,12 @@ struct rtiow_handle_s {
     DeviceBuffer<> hist_cm, hist_rgb;
     bool hist_ok = false;
     DeviceBuffer<unsigned> hist_ctr;
+    // history-guided sample budgets (rtiow_history_plan / rtiow_accumulate_budget), allocated at first use: the plan, i.e. the history
+    // length m every pixel of the current camera will carry, 1 T per pixel (plan_ok: rtiow_history_plan has written it since the last
+    // set_* / history reset / commit -- it goes stale with the temporal image), and its count of pixels with m > 0
+    DeviceBuffer<> plan_m;
+    bool plan_ok = false;
+    DeviceBuffer<unsigned> plan_ctr;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection
+// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection; launch_history_plan: its history length alone
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -13,6 +13,7 @@
 #include "../device/guide_chain.h"
 #include "../device/denoise_variance.h"
 #include "../device/history.h"
+#include "../device/history_budget.h"
 
 namespace {
 
@@ -391,14 +392,18 @@ int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
     return 0;
 }
 
-// One adaptive chunk (rtiow_accumulate_adaptive): adaptive_select_kernel lists the active pixels in h->order and copies the records of the
+// One adaptive chunk (rtiow_accumulate_adaptive, rtiow_accumulate_budget): the select kernel lists the active pixels in h->order and copies the records of the
 // others, the host reads the active count back (the call blocks here once), render_adaptive_kernel renders `samples` more samples of the
 // active pixels with a persistent grid sized from the active slots, and adaptive_finish_kernel writes every pixel's preview, count and
 // error.  The records ping-pong between h->acc_mid[0/1] like launch_accumulate's.  No ranking by previous cost and no solo waves.
 // timed: ev0 -> ev_a (select) plus ev_b -> ev1 (render and finish): the read-back between them is not counted.  The caller has checked
-// plan_order_fits.
+// plan_order_fits.  rule: which select decides (AdaptiveRule); the budget rule reads the plan h->plan_m, which the caller has found current.
+struct AdaptiveRule {
+    bool budget;                                         // false: adaptive_select_kernel by rel_error; true: budget_select_kernel by target
+    double rel_error, target;
+};
 template <class T>
-int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_error, int max_samples, bool timed, int& active) {
+int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule rule, int max_samples, bool timed, int& active) {
     Launch<T> L{make_params<T>(h)};
     RenderParams<T>& p = L.p;
     LaunchPlan P = new_plan(h, p);
@@ -420,8 +425,13 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, double rel_
 
     if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->adapt_ctr, 0, 2 * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(adaptive_select_kernel<T>, dim3((unsigned)((plan_tiles(W, h->local_rows) + 3) / 4)), dim3(256), 0, h->stream, FrameShape{W, h->local_rows},
-                       samples, min_samples, max_samples, rel_error, h->adapt_counts, h->adapt_err, h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
+    const dim3 select_grid((unsigned)((plan_tiles(W, h->local_rows) + 3) / 4));
+    if (rule.budget)
+        hipLaunchKernelGGL(budget_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
+                           (T)rule.target, h->adapt_counts, h->plan_m.as<const T>(), h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
+    else
+        hipLaunchKernelGGL(adaptive_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
+                           rule.rel_error, h->adapt_counts, h->adapt_err, h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
     HIP_TRY(h, hipGetLastError());
     if (timed) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
     unsigned n_active = 0;
@@ -554,15 +564,10 @@ bool history_constants(const CAM& b, HistoryParams<T>& hp) {
     return std::isfinite(hp.f) && hp.f != (T)0;
 }
 
-// history_reproject_kernel over the current accumulation and the base into h->hist_cm / h->hist_rgb (rtiow_history_update); the count of
-// pixels that carried history goes to h->hist_ctr.  The caller has checked state and arguments and made the guides current.
+// The constants of a reprojection from the current camera into the base (history_reproject_kernel, history_length_kernel).
 template <class T>
-int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
+HistoryParams<T> history_params(const rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
     const int W = img_w(h), rows = h->local_rows;
-    const size_t npix = (size_t)W * rows;
-    HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
-    HIP_TRY(h, h->hist_rgb.ensure(npix * 3 * sizeof(T)));
-    HIP_TRY(h, h->hist_ctr.ensure(sizeof(unsigned)));
     const auto& c = camera<T>(h);
     HistoryParams<T> hp{};
     hp.O = {c.center[0], c.center[1], c.center[2]};
@@ -572,6 +577,19 @@ int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, doubl
     hp.depth_tol = (T)depth_tol; hp.normal_cos = (T)normal_cos; hp.max_history = (T)max_history;
     const auto& b = [&]() -> const auto& { if constexpr (sizeof(T) == 4) return h->hist_cam32; else return h->hist_cam64; }();
     hp.have_base = h->hist_base_ok && b.img_width == W && b.img_height == rows && history_constants<T>(b, hp) ? 1 : 0;
+    return hp;
+}
+
+// history_reproject_kernel over the current accumulation and the base into h->hist_cm / h->hist_rgb (rtiow_history_update); the count of
+// pixels that carried history goes to h->hist_ctr.  The caller has checked state and arguments and made the guides current.
+template <class T>
+int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
+    HIP_TRY(h, h->hist_rgb.ensure(npix * 3 * sizeof(T)));
+    HIP_TRY(h, h->hist_ctr.ensure(sizeof(unsigned)));
+    const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
     const unsigned char* mid; const int32_t* counts; int n_uniform;
     accumulation_source(h, mid, counts, n_uniform);
     HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, sizeof(unsigned), h->stream));
@@ -581,6 +599,25 @@ int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, doubl
                        h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     HIP_TRY(h, hipGetLastError());
     h->hist_ok = true;
+    return 0;
+}
+
+// history_length_kernel over the current guides and the base into h->plan_m (rtiow_history_plan): the m of launch_history for the same
+// tolerances, before any sample of the frame; the count of pixels with m > 0 goes to h->plan_ctr.  The caller has checked state and
+// arguments and made the guides current.
+template <class T>
+int launch_history_plan(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    HIP_TRY(h, h->plan_m.ensure(npix * sizeof(T)));
+    HIP_TRY(h, h->plan_ctr.ensure(sizeof(unsigned)));
+    const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
+    HIP_TRY(h, hipMemsetAsync(h->plan_ctr, 0, sizeof(unsigned), h->stream));
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    hipLaunchKernelGGL(history_length_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
+                       h->hist_base_hm.as<const T>(), h->hist_base_nd.as<const Vec4<T>>(), h->plan_m.as<T>(), (unsigned*)h->plan_ctr);
+    HIP_TRY(h, hipGetLastError());
+    h->plan_ok = true;
     return 0;
 }
 

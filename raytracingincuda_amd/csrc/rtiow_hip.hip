@@ -64,6 +64,7 @@
 #include "device/denoise.h"
 #include "device/denoise_variance.h"
 #include "device/history.h"
+#include "device/history_budget.h"
 #include "device/guide_chain.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
@@ -129,7 +130,7 @@ int need_rng(rtiow_handle_s* h, const char* call) {
 }
 
 // What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
-// the temporal image, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
+// the temporal image and the history plan, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
 // (clear_base: scene, shard) the history base, which a new camera keeps.
 void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
 // A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
@@ -137,7 +138,7 @@ void invalidate_guides(rtiow_handle_s* h) { h->guides_ok = false; h->denoised_ok
 void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
     reset_accumulation(h);
     invalidate_guides(h);
-    h->hist_ok = false;
+    h->hist_ok = false; h->plan_ok = false;
     h->carried.clear();
     if (clear_rng) h->rng_ready = false;
     if (clear_base) h->hist_base_ok = false;
@@ -475,16 +476,9 @@ int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
     return 0;
 }
 
-int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels) {
-    if (!h) return RTIOW_E_BADARG;
-    if (active_pixels) *active_pixels = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    if (int rc = need_scene(h, "rtiow_accumulate_adaptive")) return rc;
-    if (int rc = need_rng(h, "rtiow_accumulate_adaptive")) return rc;
-    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
-    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
-    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
+namespace {
+// What rtiow_accumulate_adaptive and rtiow_accumulate_budget share once their arguments and states are checked: the chunk and its times.
+int adaptive_chunk(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule rule, int max_samples, float* kernel_ms, int* active_pixels) {
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
@@ -493,7 +487,7 @@ int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, doub
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
     int active = 0;
-    rc = by_precision(h, [&](auto t) { return launch_adaptive<decltype(t)>(h, samples, min_samples, rel_error, max_samples, timed, active); });
+    rc = by_precision(h, [&](auto t) { return launch_adaptive<decltype(t)>(h, samples, min_samples, rule, max_samples, timed, active); });
     if (rc) return rc;
     h->acc_mode = ACC_MODE_ADAPTIVE;
     if (active_pixels) *active_pixels = active;
@@ -508,6 +502,35 @@ int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, doub
         h->stats.render_ms = a + b; h->stats.main_ms = a + b;
     }
     return 0;
+}
+}  // namespace
+
+int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (active_pixels) *active_pixels = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (int rc = need_scene(h, "rtiow_accumulate_adaptive")) return rc;
+    if (int rc = need_rng(h, "rtiow_accumulate_adaptive")) return rc;
+    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
+    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
+    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
+    return adaptive_chunk(h, samples, min_samples, AdaptiveRule{false, rel_error, 0.0}, max_samples, kernel_ms, active_pixels);
+}
+
+// ---- History-guided sample budgets
+int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (active_pixels) *active_pixels = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    if (int rc = need_scene(h, "rtiow_accumulate_budget")) return rc;
+    if (int rc = need_rng(h, "rtiow_accumulate_budget")) return rc;
+    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(target > 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_budget: need samples > 0, 0 <= min_samples <= max_samples, target > 0 (+inf: everybody)");
+    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_budget: frames wider than 65535 or with more than 32767 local rows are not supported");
+    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_budget after rtiow_accumulate: reset the accumulation first");
+    if (!h->plan_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_budget: no history plan for the current camera (rtiow_history_plan)");
+    return adaptive_chunk(h, samples, min_samples, AdaptiveRule{true, 0.0, target}, max_samples, kernel_ms, active_pixels);
 }
 
 int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix) {
@@ -697,7 +720,7 @@ int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, do
 int rtiow_history_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
     if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_reset: not on a sharded handle");
-    h->hist_base_ok = false; h->hist_ok = false;
+    h->hist_base_ok = false; h->hist_ok = false; h->plan_ok = false;
     return 0;
 }
 
@@ -723,6 +746,39 @@ int rtiow_history_update(rtiow_handle h, double depth_tol, double normal_cos, do
     return 0;
 }
 
+int rtiow_history_plan(rtiow_handle h, double depth_tol, double normal_cos, double max_history, float* kernel_ms, uint64_t* reprojected_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    if (reprojected_pixels) *reprojected_pixels = 0;
+    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_plan: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
+    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_plan before rtiow_set_scene/rtiow_set_camera");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_plan: not on a sharded handle (the strips of a shard are not image neighbours)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_history_plan<decltype(t)>(h, depth_tol, normal_cos, max_history); }))) return rc;
+    if ((rc = timed_end(h, kernel_ms))) return rc;
+    if (reprojected_pixels) {
+        unsigned count = 0;
+        if ((rc = copy_out(h, &count, h->plan_ctr, sizeof count))) return rc;
+        *reprojected_pixels = count;
+    }
+    return 0;
+}
+
+int rtiow_read_history_plan(rtiow_handle h, void* length, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_plan: not on a sharded handle");
+    if (!h->have_camera || !h->plan_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_plan: no history plan for the current camera (rtiow_history_plan)");
+    const size_t want = local_pixels(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_plan: npix must be height x width");
+    if (!length) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return copy_out(h, length, h->plan_m, want * elem_size(h));
+}
+
 int rtiow_history_commit(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
     if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit: not on a sharded handle");
@@ -733,7 +789,7 @@ int rtiow_history_commit(rtiow_handle h) {
     std::swap(h->hist_base_nd, h->guide_nd);
     h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
     h->hist_base_ok = true;
-    h->hist_ok = false; h->guides_ok = false;
+    h->hist_ok = false; h->plan_ok = false; h->guides_ok = false;
     return 0;
 }
 
