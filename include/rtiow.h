@@ -430,6 +430,29 @@ int rtiow_history_plan(rtiow_handle h, double depth_tol, double normal_cos, doub
 int rtiow_read_history_plan(rtiow_handle h, void* length /* npix T */, size_t npix);
 int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels);
 
+/* ---- History clipped to the current frame's neighbourhood colours.  A reflection, a refraction or an
+ * out-of-focus edge moves with the camera but is reprojected as if painted on the first surface; max_history only bounds how long such
+ * a history lives.  rtiow_history_update_clipped is rtiow_history_update with one step inserted between "m = min(m, (T)max_history)"
+ * and "nT = (T)n_p": the gathered colour h is clamped to what the current accumulation shows around the pixel.  Everything in T, left
+ * to right as written, plain * + - / and a correctly rounded sqrt, no fused multiply-add.  For local pixel p = (x, y), r = clip_radius:
+ *   Window: q = (x + dx, y + dy), dy then dx in -r..r.  A tap counts when q is inside the frame and n_q > 0; n_q and c_q are those
+ *   of rtiow_read_linear.  From 0, per channel, over the taps that count: A = A + c_q, Q = Q + c_q c_q; the integer k = k + 1.
+ *   kT = (T)k, mu = A / kT, s = Q / kT - mu mu, s = s > 0 ? s : 0, sd = sqrt(s), e = (T)clip_gamma sd, lo = mu - e, hi = mu + e.
+ *   When m > 0 and k >= 2, per channel: h = h < lo ? lo : (h > hi ? hi : h); otherwise h stays.  Comparisons with NaN are false, so a
+ *   NaN bound leaves h alone.
+ * m is not changed: Mout, the length plane and *reprojected_pixels are rtiow_history_update's bit for bit for the same first three
+ * arguments, and rtiow_history_plan still predicts Mout.  *clipped_pixels (may be NULL) = the pixels with m > 0 in which at least one
+ * channel of h changed value; every other pixel has rtiow_history_update's Cout bit for bit.  clip_gamma = +inf clips nothing: the whole
+ * temporal image is rtiow_history_update's.  clip_gamma = 0 replaces the history by the neighbourhood mean.
+ * RTIOW_E_BADARG: the errors of rtiow_history_update, clip_radius outside 1..3, clip_gamma < 0 or NaN.  RTIOW_E_STATE, the rendering of
+ * stale guides inside kernel_ms, the asynchronous form (all three pointers NULL) and the refusal of sharded handles are
+ * rtiow_history_update's.  The call writes the same temporal image and colour plane, so rtiow_history_commit, rtiow_read_history,
+ * rtiow_history_device_ptr and rtiow_denoise_history work on its result unchanged, and it touches nothing else: framebuffer,
+ * accumulation, counts and errors, base, guides, plan, the bits of the next chunk.  A failing call leaves the handle as it was.
+ * Not available on groups. */
+int rtiow_history_update_clipped(rtiow_handle h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma,
+                                 float* kernel_ms, uint64_t* reprojected_pixels, uint64_t* clipped_pixels);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

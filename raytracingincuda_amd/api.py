@@ -97,6 +97,7 @@ HIP_SYMBOLS = [
     "rtiow_history_reset", "rtiow_history_update", "rtiow_history_commit", "rtiow_read_history", "rtiow_history_device_ptr", "rtiow_denoise_history",
     "rtiow_set_guide_mode", "rtiow_read_filter_guides",
     "rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget",
+    "rtiow_history_update_clipped",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -222,6 +223,8 @@ def load_hip_library(debug=False):
         lib.rtiow_read_history_plan.argtypes = [H, vp, ctypes.c_size_t]
         lib.rtiow_accumulate_budget.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
+        lib.rtiow_history_update_clipped.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
@@ -435,6 +438,11 @@ HISTORY_MAX = 16.0
 BUDGET_TARGET = 16.0
 BUDGET_MIN_SAMPLES = 1
 BUDGET_CHUNK = 2
+# Renderer.history_update_clipped defaults: the best of scripts/history_clip_probe.py's sweep by the rule above at 0.5 degrees a frame
+# and HISTORY_MAX, i.e. the smallest worse-of-two-scenes MSE ratio of the clipped walk's temporal image against the unclipped walk's
+# (profiles/history_clip/history_clip_probe.json).
+HISTORY_CLIP_RADIUS = 1
+HISTORY_CLIP_GAMMA = 0.5
 # The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
 # to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
 # section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
@@ -709,6 +717,21 @@ class Renderer:
         ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
         self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
         return int(n.value)
+
+    def history_update_clipped(self, clip_radius=HISTORY_CLIP_RADIUS, clip_gamma=HISTORY_CLIP_GAMMA, depth_tol=HISTORY_DEPTH_TOL,
+                               normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
+        """history_update() with the gathered history colour clamped, per channel, to mean +- clip_gamma standard deviations of the
+        current accumulation over the (2 clip_radius + 1)^2 pixels around each pixel: a history the
+        current frame contradicts -- a reflection reprojected as if painted on its mirror -- is pulled to what the frame sees.  History
+        lengths, and so history_plan(), are history_update()'s.  clip_radius 1..3; clip_gamma >= 0 (float("inf"): no clamp).
+        Returns (pixels that carried history, those of them the clamp changed), or None when sync=False."""
+        args = (float(depth_tol), float(normal_cos), float(max_history), int(clip_radius), float(clip_gamma))
+        if not sync:
+            self._check(self._lib.rtiow_history_update_clipped(self._h, *args, None, None, None))
+            return None
+        ms, n, k = ctypes.c_float(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.rtiow_history_update_clipped(self._h, *args, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(k)))
+        return int(n.value), int(k.value)
 
     def history_plan(self, depth_tol=HISTORY_DEPTH_TOL, normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
         """The history length every pixel of the current camera will carry: history_update()'s m for the

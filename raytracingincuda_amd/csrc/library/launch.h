@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection; launch_history_plan: its history length alone
+// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection; launch_history_clip: the same with the neighbourhood clamp; launch_history_plan: its history length alone
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -13,6 +13,7 @@
 #include "../device/guide_chain.h"
 #include "../device/denoise_variance.h"
 #include "../device/history.h"
+#include "../device/history_clip.h"
 #include "../device/history_budget.h"
 
 namespace {
@@ -595,6 +596,29 @@ int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, doubl
     HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, sizeof(unsigned), h->stream));
     const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
     hipLaunchKernelGGL(history_reproject_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, mid, counts, n_uniform,
+                       h->guide_nd.as<const Vec4<T>>(), h->hist_base_hm.as<const Vec4<T>>(), h->hist_base_nd.as<const Vec4<T>>(),
+                       h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    HIP_TRY(h, hipGetLastError());
+    h->hist_ok = true;
+    return 0;
+}
+
+// launch_history with the neighbourhood clamp (rtiow_history_update_clipped): history_clip_kernel writes the same two images; h->hist_ctr
+// holds two words, the pixels that carried history and those of them the clamp changed.  The caller has checked clip_radius in
+// 1..CLIP_MAX_RADIUS, which the kernel's LDS tile is sized for.
+template <class T>
+int launch_history_clip(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
+    HIP_TRY(h, h->hist_rgb.ensure(npix * 3 * sizeof(T)));
+    HIP_TRY(h, h->hist_ctr.ensure(2 * sizeof(unsigned)));
+    const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
+    const unsigned char* mid; const int32_t* counts; int n_uniform;
+    accumulation_source(h, mid, counts, n_uniform);
+    HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, 2 * sizeof(unsigned), h->stream));
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    hipLaunchKernelGGL(history_clip_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, clip_radius, (T)clip_gamma, mid, counts, n_uniform,
                        h->guide_nd.as<const Vec4<T>>(), h->hist_base_hm.as<const Vec4<T>>(), h->hist_base_nd.as<const Vec4<T>>(),
                        h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     HIP_TRY(h, hipGetLastError());

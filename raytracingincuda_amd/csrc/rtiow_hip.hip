@@ -64,6 +64,7 @@
 #include "device/denoise.h"
 #include "device/denoise_variance.h"
 #include "device/history.h"
+#include "device/history_clip.h"
 #include "device/history_budget.h"
 #include "device/guide_chain.h"
 #include "library/xorwow_jump.h"
@@ -742,6 +743,33 @@ int rtiow_history_update(rtiow_handle h, double depth_tol, double normal_cos, do
         unsigned count = 0;
         if ((rc = copy_out(h, &count, h->hist_ctr, sizeof count))) return rc;
         *reprojected_pixels = count;
+    }
+    return 0;
+}
+
+int rtiow_history_update_clipped(rtiow_handle h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma,
+                                 float* kernel_ms, uint64_t* reprojected_pixels, uint64_t* clipped_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    if (reprojected_pixels) *reprojected_pixels = 0;
+    if (clipped_pixels) *clipped_pixels = 0;
+    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update_clipped: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
+    if (clip_radius < 1 || clip_radius > CLIP_MAX_RADIUS || !(clip_gamma >= 0))
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update_clipped: need clip_radius in 1..3, clip_gamma >= 0 (+inf: no clamp)");
+    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update_clipped: no chunk since the last reset");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update_clipped: not on a sharded handle (the strips of a shard are not image neighbours)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_history_clip<decltype(t)>(h, depth_tol, normal_cos, max_history, clip_radius, clip_gamma); }))) return rc;
+    if ((rc = timed_end(h, kernel_ms))) return rc;
+    if (reprojected_pixels || clipped_pixels) {
+        unsigned count[2] = {0, 0};
+        if ((rc = copy_out(h, count, h->hist_ctr, sizeof count))) return rc;
+        if (reprojected_pixels) *reprojected_pixels = count[0];
+        if (clipped_pixels) *clipped_pixels = count[1];
     }
     return 0;
 }
