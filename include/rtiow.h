@@ -453,6 +453,35 @@ int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double
 int rtiow_history_update_clipped(rtiow_handle h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma,
                                  float* kernel_ms, uint64_t* reprojected_pixels, uint64_t* clipped_pixels);
 
+/* ---- Variance-guided filtering of the temporal image.  rtiow_denoise_variance steers its colour edge-stop
+ * by each pixel's measured noise but reads the current accumulation only; rtiow_denoise_history reads the temporal image but has one
+ * fixed sigma.  rtiow_denoise_history_variance is rtiow_denoise_variance with two changes at level 0: C^0 = Cout, the temporal colour
+ * plane rtiow_denoise_history reads, and V^0 = the plane below.  Nothing is carried from frame to frame: the blend is
+ * Cout = h + alpha (c - h), alpha = n / Mout, and if the history's samples have the per-sample variance the frame measured, the variance
+ * of Cout's mean luminance is alpha^2 V + (1 - alpha)^2 V n / m = alpha V.  Everything in T, left to right as written, plain * + - /,
+ * no fused multiply-add.  For local pixel p = (x, y), r = variance_radius:
+ *   Measured -- the accumulation is adaptive and n_p >= 2: V_p = rtiow_read_variance's value, alpha = (T)n_p / Mout_p (the update's own
+ *   expression and bits; Mout_p > 0 here), V^0_p = alpha V_p.
+ *   Spatial -- every other pixel (never sampled, n_p < 2, every pixel after plain chunks): Y_q = the luminance of adaptive chunks
+ *   ((0.2126 R + 0.7152 G) + 0.0722 B in T) of Cout_q.  Window: q = (x + dx, y + dy), dy then dx in -r..r; a tap counts when q is inside
+ *   the frame and Mout_q > 0.  From 0 over the taps that count: A = A + Y_q, Q = Q + Y_q Y_q; the integer k = k + 1.  kT = (T)k,
+ *   mu = A / kT, s = Q / kT - mu mu, s = s > 0 ? s : 0, V^0_p = k >= 2 ? s : 0.  s is the spread of per-pixel means already: it is not
+ *   divided by a count.
+ * levels, taps, tap order, kern, g_p, i_p, f_k, eps, the guide terms, the filter guides of the current guide mode, the skipping of taps
+ * outside the frame, the gamma of the last level, the output buffer (rtiow_read_denoised, rtiow_denoised_device_ptr), the rendering of
+ * stale guides inside kernel_ms, kernel_ms == NULL meaning asynchronous and sigma_variance = +inf decided on the host are
+ * rtiow_denoise_variance's to the letter.  V^0 lives in a buffer of its own, which the levels do not overwrite; rtiow_read_history_variance
+ * copies it out (npix = height x width, else RTIOW_E_BADARG; var == NULL runs only the checks).  It returns RTIOW_E_STATE until a
+ * rtiow_denoise_history_variance has run, wherever the temporal image goes stale, and after a later rtiow_history_update(_clipped).
+ * RTIOW_E_BADARG: rtiow_denoise_variance's errors, variance_radius outside 1..3.  RTIOW_E_STATE: the temporal image is stale; the handle
+ * is sharded; a chunk (rtiow_accumulate, _adaptive, _budget) or a reset of the accumulation (rtiow_accumulate_reset, rtiow_init_rng) ran
+ * after the update that wrote the temporal image -- alpha would no longer be the update's: update again.  A failing call leaves the
+ * handle as it was.  The call touches nothing else: framebuffer, accumulation, counts and errors, base, temporal image, guides, plan,
+ * the bits of the next chunk.  Not available on groups. */
+int rtiow_denoise_history_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth,
+                                   int variance_radius, float* kernel_ms);
+int rtiow_read_history_variance(rtiow_handle h, void* var /* npix T */, size_t npix);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -98,6 +98,7 @@ HIP_SYMBOLS = [
     "rtiow_set_guide_mode", "rtiow_read_filter_guides",
     "rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget",
     "rtiow_history_update_clipped",
+    "rtiow_denoise_history_variance", "rtiow_read_history_variance",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -225,6 +226,9 @@ def load_hip_library(debug=False):
                                                 ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
         lib.rtiow_history_update_clipped.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        lib.rtiow_denoise_history_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_read_history_variance.argtypes = [H, vp, ctypes.c_size_t]
         lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
@@ -443,6 +447,12 @@ BUDGET_CHUNK = 2
 # (profiles/history_clip/history_clip_probe.json).
 HISTORY_CLIP_RADIUS = 1
 HISTORY_CLIP_GAMMA = 0.5
+# Renderer.denoise_history_variance defaults: the best of scripts/history_variance_probe.py's sweep by the same rule at 0.5 degrees a
+# frame, i.e. the smallest worse-of-two-scenes ratio of its MSE to denoise_history()'s at the defaults above, first of equals in grid
+# order (profiles/history_variance/history_variance_probe.json).  At these the ratio is 0.86 on scene 1 and
+# 1.00 on scene 3: it does not pay on both yet, and denoise_history() stays the filter the documents recommend for the temporal image.
+HISTORY_VARIANCE_RADIUS = 1
+HISTORY_SIGMA_VARIANCE = 2.0
 # The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
 # to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
 # section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
@@ -789,6 +799,24 @@ class Renderer:
         self._check(self._lib.rtiow_denoise_history(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
                                                     float(sigma_depth), ctypes.byref(ms) if sync else None))
         return self.read_denoised() if sync else None
+
+    def denoise_history_variance(self, levels=DENOISE_LEVELS, sigma_variance=HISTORY_SIGMA_VARIANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
+                                 sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, variance_radius=HISTORY_VARIANCE_RADIUS, sync=True):
+        """denoise_variance() of the temporal image: level 0 reads history()'s colour and history_variance(),
+        i.e. the frame's measured variance() scaled by the update's blend weight n / length where the accumulation measured one, and
+        the spread of the temporal image's luminance over the (2 variance_radius + 1)^2 pixels around the pixel elsewhere (plain
+        chunks: everywhere).  Call it after history_update() or history_update_clipped() and before the next chunk.  variance_radius
+        1..3.  Returns and stores its image like denoise()."""
+        ms = None if not sync else ctypes.c_float(0)
+        self._check(self._lib.rtiow_denoise_history_variance(self._h, int(levels), float(sigma_variance), float(sigma_normal), float(sigma_albedo),
+                                                             float(sigma_depth), int(variance_radius), ctypes.byref(ms) if sync else None))
+        return self.read_denoised() if sync else None
+
+    def history_variance(self):
+        """The variance plane [H, W] the last denoise_history_variance() filtered the temporal image by."""
+        out = np.empty((self.local_rows, self.width), self.dtype)
+        self._check(self._lib.rtiow_read_history_variance(self._h, out.ctypes.data, out.size))
+        return out
 
     def read_denoised(self):
         out = np.empty((self.local_rows, self.width, 3), self.dtype)

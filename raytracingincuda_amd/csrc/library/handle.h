@@ -138,6 +138,13 @@ struct rtiow_handle_s {
     DeviceBuffer<> hist_cm, hist_rgb;
     bool hist_ok = false;
     DeviceBuffer<unsigned> hist_ctr;
+    // variance-guided filtering of the temporal image (rtiow_denoise_history_variance), allocated at first use: its level-0 variance
+    // plane V^0, 1 T per pixel, which the filter's ping-pong leaves alone (hist_var_ok: the call has written it for the temporal image
+    // the handle holds -- it goes stale with hist_ok and with every update).  acc_gen counts the chunks and resets of the accumulation;
+    // hist_gen is its value at the update that wrote the temporal image, whose alpha = n / Mout holds only while the two agree.
+    DeviceBuffer<> hist_var;
+    bool hist_var_ok = false;
+    uint64_t acc_gen = 0, hist_gen = 0;
     // history-guided sample budgets (rtiow_history_plan / rtiow_accumulate_budget), allocated at first use: the plan, i.e. the history
     // length m every pixel of the current camera will carry, 1 T per pixel (plan_ok: rtiow_history_plan has written it since the last
     // set_* / history reset / commit -- it goes stale with the temporal image), and its count of pixels with m > 0

@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter; launch_history: the temporal reprojection; launch_history_clip: the same with the neighbourhood clamp; launch_history_plan: its history length alone
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection; launch_history_clip: the same with the neighbourhood clamp; launch_history_plan: its history length alone
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -15,6 +15,7 @@
 #include "../device/history.h"
 #include "../device/history_clip.h"
 #include "../device/history_budget.h"
+#include "../device/temporal_noise.h"
 
 namespace {
 
@@ -600,6 +601,8 @@ int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, doubl
                        h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     HIP_TRY(h, hipGetLastError());
     h->hist_ok = true;
+    h->hist_var_ok = false;                              // V^0 was of the image this one replaces
+    h->hist_gen = h->acc_gen;
     return 0;
 }
 
@@ -623,6 +626,8 @@ int launch_history_clip(rtiow_handle_s* h, double depth_tol, double normal_cos, 
                        h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     HIP_TRY(h, hipGetLastError());
     h->hist_ok = true;
+    h->hist_var_ok = false;                              // V^0 was of the image this one replaces
+    h->hist_gen = h->acc_gen;
     return 0;
 }
 
@@ -657,6 +662,22 @@ int launch_variance_plane(rtiow_handle_s* h) {
     return 0;
 }
 
+// temporal_noise_kernel over the temporal image and the current accumulation into h->hist_var (level 0 of rtiow_denoise_history_variance,
+// rtiow_read_history_variance).  The caller has checked that the temporal image is current and the accumulation the one its update read,
+// and variance_radius in 1..NOISE_MAX_RADIUS, which the kernel's LDS tile is sized for.  Plain chunks keep no second moment: no counts.
+template <class T>
+int launch_temporal_noise(rtiow_handle_s* h, int variance_radius) {
+    const int W = img_w(h), rows = h->local_rows;
+    HIP_TRY(h, h->hist_var.ensure((size_t)W * rows * sizeof(T)));
+    const int32_t* counts = h->acc_mode == ACC_MODE_ADAPTIVE ? (const int32_t*)h->adapt_counts : nullptr;
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    hipLaunchKernelGGL(temporal_noise_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, variance_radius, h->hist_cm.as<const Vec4<T>>(),
+                       (const unsigned char*)h->acc_mid[h->acc_cur], counts, h->hist_var.as<T>());
+    HIP_TRY(h, hipGetLastError());
+    h->hist_var_ok = true;
+    return 0;
+}
+
 // The levels of rtiow_denoise_variance that stage their taps in LDS (bit k = level k), by measurement at 1920 x 1080 (DESIGN.md section 4.9,
 // profiles/denoise_variance/denoise_variance_probe.json): fp32 steps 1, 2 and 4 (5 levels about 1.8 -> 0.9 ms); fp64 steps 1 and 2 (about 2.1 -> 1.25 ms;
 // step 4, 96 KB of LDS and one workgroup per CU, gains under 1 %).
@@ -667,11 +688,13 @@ constexpr int VARIANCE_TILE_LEVELS_F32 = 7, VARIANCE_TILE_LEVELS_F64 = 3;
 // (the last level stores none).  sigma_variance in double, its square rounded to T here; +inf -- or a square that is not finite in T --
 // turns the colour term off on the host.  inv2g[3] = 1 / sigma^2 of normal, albedo, depth.  The caller has checked state and arguments
 // and made the guides current.
+// from_history (rtiow_denoise_history_variance): level 0 reads the temporal colour plane h->hist_rgb and the plane h->hist_var that
+// launch_temporal_noise writes first, at variance_radius; the later levels are the same launches.
 template <class T>
-int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance, const double inv2g[3]) {
+int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance, const double inv2g[3], bool from_history = false, int variance_radius = 0) {
     const int W = img_w(h), rows = h->local_rows;
     const size_t npix = (size_t)W * rows;
-    if (int rc = launch_variance_plane<T>(h)) return rc;
+    if (int rc = from_history ? launch_temporal_noise<T>(h, variance_radius) : launch_variance_plane<T>(h)) return rc;
     HIP_TRY(h, h->denoised.ensure(npix * 3 * sizeof(T)));
     for (int b = 0; b < 2 && b < levels - 1; ++b) {
         HIP_TRY(h, h->dn_tmp[b].ensure(npix * 3 * sizeof(T)));
@@ -690,15 +713,15 @@ int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance
     for (int k = 0; k < levels; ++k) {
         fw.fk = (T)std::ldexp(1.0, 2 * k);
         const bool last = k == levels - 1;
-        const T* cin = k == 0 ? nullptr : h->dn_tmp[(k - 1) & 1].as<const T>();
-        const T* vin = k == 0 ? h->variance.as<const T>() : h->dn_var[(k - 1) & 1].as<const T>();
+        const T* cin = k == 0 ? (from_history ? h->hist_rgb.as<const T>() : nullptr) : h->dn_tmp[(k - 1) & 1].as<const T>();
+        const T* vin = k == 0 ? (from_history ? h->hist_var : h->variance).as<const T>() : h->dn_var[(k - 1) & 1].as<const T>();
         T* cout = (last ? h->denoised : h->dn_tmp[k & 1]).as<T>();
         T* vout = last ? nullptr : h->dn_var[k & 1].as<T>();
         const bool tiled = k < 3 && ((tile_levels >> k) & 1);
         const size_t lds = tiled ? variance_tile_bytes<T>(1 << k) : 0;
         const auto kernel = tiled ? variance_tile_kernel<T> : variance_filter_kernel<T>;
         HIP_TRY(h, allow_lds(kernel, lds));
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 ? mid : nullptr,
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, h->stream, FrameShape{W, rows}, 1 << k, fw, k == 0 && !from_history ? mid : nullptr,
                            (const int32_t*)h->adapt_counts, cin, vin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, vout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }

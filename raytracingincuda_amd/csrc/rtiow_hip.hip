@@ -66,6 +66,7 @@
 #include "device/history.h"
 #include "device/history_clip.h"
 #include "device/history_budget.h"
+#include "device/temporal_noise.h"
 #include "device/guide_chain.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
@@ -133,7 +134,8 @@ int need_rng(rtiow_handle_s* h, const char* call) {
 // What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
 // the temporal image and the history plan, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
 // (clear_base: scene, shard) the history base, which a new camera keeps.
-void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; }
+// acc_gen: every chunk and every reset of the accumulation bumps it (rtiow_denoise_history_variance compares it with the update's).
+void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; ++h->acc_gen; }
 // A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
 void invalidate_guides(rtiow_handle_s* h) { h->guides_ok = false; h->denoised_ok = false; }
 void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
@@ -447,6 +449,7 @@ int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, flo
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
     if (kernel_ms) *kernel_ms = 0;
+    ++h->acc_gen;
     if (h->local_rows == 0) { zero_times(h); h->acc_samples += samples; h->acc_mode = ACC_MODE_PLAIN; return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
@@ -484,6 +487,7 @@ int adaptive_chunk(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the events of rtiow_render_async
+    ++h->acc_gen;
     if (h->local_rows == 0) { zero_times(h); h->stats.primary_rays = 0; h->acc_mode = ACC_MODE_ADAPTIVE; return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
@@ -864,6 +868,42 @@ int rtiow_denoise_history(rtiow_handle h, int levels, double sigma_color, double
     if (!h->guides_ok && (rc = render_guides(h))) return rc;
     if ((rc = by_precision(h, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2, true); }))) return rc;
     return timed_end(h, kernel_ms);
+}
+
+// ---- Variance-guided filtering of the temporal image
+int rtiow_denoise_history_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth,
+                                   int variance_radius, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    const double sig[4] = {sigma_variance, sigma_normal, sigma_albedo, sigma_depth};
+    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: levels must be 1..8");
+    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: every sigma must be > 0 (+inf turns its term off)");
+    if (variance_radius < 1 || variance_radius > NOISE_MAX_RADIUS) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: need variance_radius in 1..3");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: not on a sharded handle (the strips of a shard are not image neighbours)");
+    if (!h->have_camera || h->n == 0 || !h->hist_ok)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: no temporal image for the current camera (rtiow_history_update)");
+    if (h->hist_gen != h->acc_gen)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: a chunk or a reset since the update that wrote the temporal image (update again)");
+    double inv2g[3];
+    for (int k = 0; k < 3; ++k) inv2g[k] = 1.0 / (sig[k + 1] * sig[k + 1]);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2g, true, variance_radius); }))) return rc;
+    return timed_end(h, kernel_ms);
+}
+
+int rtiow_read_history_variance(rtiow_handle h, void* var, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_variance: not on a sharded handle");
+    if (!h->have_camera || !h->hist_ok || !h->hist_var_ok)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_variance: no variance plane for the temporal image (rtiow_denoise_history_variance)");
+    const size_t want = local_pixels(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_variance: npix must be height x width");
+    if (!var) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return copy_out(h, var, h->hist_var, want * elem_size(h));
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {
