@@ -505,7 +505,7 @@ int rtiow_synchronize(rtiow_handle h);
 int rtiow_stream(rtiow_handle h, void** hip_stream);   /* the hipStream_t the handle launches on */
 int rtiow_device(rtiow_handle h, int* device);
 
-/* Test hooks (device RNG states, per-pixel costs, per-wave timeline, hit_world on caller-supplied rays, ...) are NOT part of this
+/* Test hooks (device RNG states, per-pixel costs, per-wave timeline, hit_world on caller-supplied rays, the scatter step on caller-supplied hit records, ...) are NOT part of this
  * library's ABI: include/rtiow_debug.h declares them and only the test build (librtiow_hip_debug.so, -DRTIOW_DEBUG_API) exports them. */
 
 /* ======================================================================================

@@ -54,6 +54,18 @@ int rtiow_debug_ops(rtiow_handle h, int op, size_t n, const void* a, const void*
  * {ox,oy,oz,dx,dy,dz} in the handle's precision: nearest root (+inf: none) and sphere index (-1: none) per ray.
  * Lets the tests compare the scene sources on rays no render produces. */
 int rtiow_debug_hit_world(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out);
+/* The scatter step alone -- everything that follows hit_world in one trip of the path loop (camera.h:88-124: sky, hit record, lambertian,
+ * metal and dielectric scatter with their rejection loops) -- with the handle's scene, on n caller-supplied calls in the handle's precision,
+ * one per lane: calls 64 w ... 64 w + 63 are the lanes of wave w, so the caller decides who shares a wave.  (closest, hit) are taken as
+ * given, not recomputed.  form selects the statement of the step: 0 shade_step<T, false>; 1 the bounded shade_step<T, true>, called with the
+ * build's rounds per trip until it stops asking for a retry; 2 (fp64 only, RTIOW_E_BADARG in fp32) shade_front, merged_rounds bounded the
+ * same way and repeated while the lane is still looking, shade_back -- the rotated trip of the persistent kernels.
+ *   in_real11  {ox,oy,oz, dx,dy,dz, closest, atten r,g,b, sky_uy}          in_int2  {hit (-1: miss), depth}       in_state6  {v0..v4,d}
+ *   out_real12 {col r,g,b, ox,oy,oz, dx,dy,dz, atten r,g,b} afterwards     out_int4 {1: the path ended (col is its colour) / 0: it goes on,
+ *              depth, trips the call took, flags (bit 0: a retry did not leave O, D, atten and depth untouched)}   out_state6 afterwards
+ * rounds_per_trip (optional): the build's bound of the rejection loop per trip.  RTIOW_E_BADARG: a hit index beyond the scene. */
+int rtiow_debug_scatter(rtiow_handle h, int form, int n, const void* in_real11, const int32_t* in_int2, const uint32_t* in_state6,
+                        void* out_real12, int32_t* out_int4, uint32_t* out_state6, int* rounds_per_trip);
 /* The 32 XORWOW subsequence-jump matrices A^(2^(67+b)) (160 x 5 words each) as the library builds
  * them: from its committed constant A^(2^67), or from_scratch != 0 from the one-step matrix A.
  * Host arithmetic only (no GPU needed).  Returns the number of matrices. */

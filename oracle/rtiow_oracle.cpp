@@ -331,6 +331,17 @@ template <class T> void camera_init(Camera<T>& cam, int W, int H, int S, int B) 
 // =====================================================================================
 template <class T> struct Hit { V3<T> p, normal; T t; bool front; int idx; };
 
+// hittable.h:59-63 with set_face_normal (:21-26): the record of the root that was found.  On its own so that oracle_scatter
+// builds the record of a caller-supplied (root, sphere) with the very statements hit_sphere runs.
+template <bool F, class T>
+inline void hit_record(V3<T> center, T radius, V3<T> O, V3<T> D, T root, Hit<T>& rec) {
+    rec.t = root;                                                     // :59
+    rec.p = F ? madd<true>(root, D, O) : O + scale(root, D);          // :60 ray::at
+    V3<T> outward = vdiv(rec.p - center, radius);                     // :61
+    rec.front = dot<F>(D, outward) < 0;                               // :24
+    rec.normal = rec.front ? outward : -outward;                      // :25
+}
+
 template <bool F, class T>
 inline bool hit_sphere(V3<T> center, T radius, V3<T> O, V3<T> D, T tmin, T tmax, Hit<T>& rec) {
     V3<T> oc = center - O;                                            // hittable.h:42
@@ -345,11 +356,7 @@ inline bool hit_sphere(V3<T> center, T radius, V3<T> O, V3<T> D, T tmin, T tmax,
         root = (h + sqrtd) / a;
         if (!(tmin < root && root < tmax)) return false;
     }
-    rec.t = root;                                                     // :59
-    rec.p = F ? madd<true>(root, D, O) : O + scale(root, D);          // :60 ray::at
-    V3<T> outward = vdiv(rec.p - center, radius);                     // :61
-    rec.front = dot<F>(D, outward) < 0;                               // :24
-    rec.normal = rec.front ? outward : -outward;                      // :25
+    hit_record<F>(center, radius, O, D, root, rec);                   // :59-63
     return true;
 }
 
@@ -496,12 +503,15 @@ inline bool scatter(const World<typename P::real>& w, V3<typename P::real> D, co
 
 // camera.h:121-123 (CUDA; `a` is double even in the float build) / src/InOneWeekend/camera.h:153-155:
 //   (1-a)*white + a*(0.5,0.7,1.0),  a = 0.5*(unit(dir).y + 1)
-template <class P> inline V3<typename P::real> sky_colour(V3<typename P::real> dir) {
+// The blend for a given unit_direction.y() (oracle_scatter supplies it; a render takes it from the ray through sky_colour).
+template <class P> inline V3<typename P::real> sky_blend(typename P::real uy) {
     typedef typename P::real T;
-    V3<T> ud = unit<P::fused>(dir);
-    double a = 0.5 * ((double)ud.y + 1.0);
+    double a = 0.5 * ((double)uy + 1.0);
     T w1 = (T)(1.0 - a), w2 = (T)a;                                   // operator*(T, vec3): the weights are converted to T
     return {mad<P::fused>(w2, (T)0.5, w1), mad<P::fused>(w2, (T)0.7, w1), mad<P::fused>(w2, (T)1.0, w1)};
+}
+template <class P> inline V3<typename P::real> sky_colour(V3<typename P::real> dir) {
+    return sky_blend<P>(unit<P::fused>(dir).y);
 }
 
 struct RenderStats { uint64_t primary_rays, segments, sphere_tests, rng_draws; };
@@ -563,6 +573,21 @@ template <class T> inline V3<T> dev_random_in_unit_disk(Xorwow& s) {  // vec3.h:
     }
 }
 
+// camera.h:145-155: the primary ray of pixel (i, j) from the pixel's stream (render_cuda_rows; oracle_primary_rays).
+template <class T>
+inline void primary_ray(const Camera<T>& cam, int i, int j, Xorwow& s, V3<T>& org, V3<T>& dir) {
+    T ox = device_uniform<T>(s) - (T)0.5;                             // :145 (first argument drawn first)
+    T oy = device_uniform<T>(s) - (T)0.5;                             // :146
+    T fi = (T)i + ox, fj = (T)j + oy;                                 // :149-150
+    V3<T> ps = madd<true>(fj, cam.pixel_delta_v, madd<true>(fi, cam.pixel_delta_u, cam.pixel00_loc));
+    org = cam.center;
+    if (!(cam.defocus_angle <= 0)) {                                  // :152-153, :73-76
+        V3<T> p = dev_random_in_unit_disk<T>(s);
+        org = madd<true>(p.y, cam.defocus_disk_v, madd<true>(p.x, cam.defocus_disk_u, cam.center));
+    }
+    dir = ps - org;                                                   // :154
+}
+
 template <class T>
 void render_cuda_rows(const World<T>& w, const Camera<T>& cam, uint64_t seed, int row0, int row1, int out_row0,
                       T* out_rgb, RenderStats& st, uint32_t* seg_per_pixel, LoopForm form, SkyMode sky) {
@@ -574,16 +599,8 @@ void render_cuda_rows(const World<T>& w, const Camera<T>& cam, uint64_t seed, in
             V3<T> pc = {0, 0, 0};
             const uint64_t seg0 = st.segments;
             for (int sample = 0; sample < cam.S; ++sample) {          // camera.h:141
-                T ox = device_uniform<T>(s) - (T)0.5;                 // :145 (first argument drawn first)
-                T oy = device_uniform<T>(s) - (T)0.5;                 // :146
-                T fi = (T)i + ox, fj = (T)j + oy;                     // :149-150
-                V3<T> ps = madd<true>(fj, cam.pixel_delta_v, madd<true>(fi, cam.pixel_delta_u, cam.pixel00_loc));
-                V3<T> org = cam.center;
-                if (!(cam.defocus_angle <= 0)) {                      // :152-153, :73-76
-                    V3<T> p = dev_random_in_unit_disk<T>(s);
-                    org = madd<true>(p.y, cam.defocus_disk_v, madd<true>(p.x, cam.defocus_disk_u, cam.center));
-                }
-                V3<T> dir = ps - org;                                 // :154
+                V3<T> org, dir;
+                primary_ray<T>(cam, i, j, s, org, dir);               // :145-155
                 ++st.primary_rays;
                 pc = pc + ray_color<P>(form, org, dir, cam.B, w, s, sky, st);   // :160
             }
@@ -846,6 +863,94 @@ int oracle_hit_world(int precision, int n_spheres, const void* center_radius, in
             const bool any = hit_world<true, T>(w, {r[6 * k], r[6 * k + 1], r[6 * k + 2]}, {r[6 * k + 3], r[6 * k + 4], r[6 * k + 5]}, (T)0.001, std::numeric_limits<T>::infinity(), rec);
             t[k] = any ? rec.t : std::numeric_limits<T>::infinity();
             index_out[k] = any ? rec.idx : -1;
+        }
+    };
+    if (precision == 32) run(float());
+    else if (precision == 64) run(double());
+    else return -1;
+    return 0;
+}
+
+// One scatter call per record (twin of the library's rtiow_debug_scatter, tests/test_scatter.py): everything that follows hit_world in one
+// trip of the loop at camera.h:84, for a caller-supplied (closest, hit) -- the hit record by hit_record (what hit_sphere runs), then
+// scatter<CudaPolicy<T>>; on a miss the attenuation times sky_blend of the supplied unit_direction.y().  Per call
+//   in_real11  {O, D, closest, atten, sky_uy}      in_int2  {hit (-1: miss), depth}      in_state6  {v0..v4, d}
+//   out_real12 {col, O, D, atten}                  out_int2 {status (1: the path ended, col is its colour), depth}      out_state6
+// A path that ends keeps O, D, atten and depth as they came in.
+int oracle_scatter(int precision, int n_spheres, const void* center_radius, const void* albedo_fuzz, const void* ri, const int* type,
+                   int n, const void* in_real11, const int* in_int2, const unsigned int* in_state6,
+                   void* out_real12, int* out_int2, unsigned int* out_state6) {
+    auto run = [&](auto tag) {
+        using T = decltype(tag);
+        typedef CudaPolicy<T> P;
+        World<T> w; world_from_arrays(n_spheres, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)ri, type, w);
+        const T* in = (const T*)in_real11; T* out = (T*)out_real12;
+        for (int k = 0; k < n; ++k) {
+            const T* r = in + 11 * (size_t)k;
+            V3<T> O = {r[0], r[1], r[2]}, D = {r[3], r[4], r[5]}, atten = {r[7], r[8], r[9]}, col = {0, 0, 0};
+            const T closest = r[6], sky_uy = r[10];
+            const int hit = in_int2[2 * (size_t)k];
+            int depth = in_int2[2 * (size_t)k + 1], status = 1;
+            Xorwow s; for (int q = 0; q < 5; ++q) s.v[q] = in_state6[6 * (size_t)k + q]; s.d = in_state6[6 * (size_t)k + 5];
+            if (hit < 0) col = atten * sky_blend<P>(sky_uy);                                   // camera.h:120-124
+            else {
+                Hit<T> rec; hit_record<true>(w.center[hit], w.radius[hit], O, D, closest, rec); rec.idx = hit;
+                V3<T> att, nd;
+                if (scatter<P>(w, D, rec, s, att, nd)) {                                       // camera.h:110-115
+                    atten = atten * att; O = rec.p; D = nd; ++depth; status = 0;
+                }                                                                              // else :117, black
+            }
+            T* o = out + 12 * (size_t)k;
+            o[0] = col.x; o[1] = col.y; o[2] = col.z; o[3] = O.x; o[4] = O.y; o[5] = O.z; o[6] = D.x; o[7] = D.y; o[8] = D.z;
+            o[9] = atten.x; o[10] = atten.y; o[11] = atten.z;
+            out_int2[2 * (size_t)k] = status; out_int2[2 * (size_t)k + 1] = depth;
+            for (int q = 0; q < 5; ++q) out_state6[6 * (size_t)k + q] = s.v[q]; out_state6[6 * (size_t)k + 5] = s.d;
+        }
+    };
+    if (n_spheres <= 0 || n < 0) return -1;
+    for (int k = 0; k < n; ++k) if (in_int2[2 * (size_t)k] >= n_spheres) return -1;
+    if (precision == 32) run(float());
+    else if (precision == 64) run(double());
+    else return -1;
+    return 0;
+}
+
+// random_unit_vector (vec3.h:117-127, CUDA policy) from n states: the vector, the state afterwards and the rounds the loop ran.
+int oracle_random_unit_vector(int precision, int n, unsigned int* state6, void* out3, int* rounds) {
+    auto run = [&](auto tag) {
+        using T = decltype(tag);
+        typedef CudaPolicy<T> P;
+        const uint32_t per_round = sizeof(T) == 8 ? 6u : 3u;                                   // generator steps a candidate takes
+        for (int k = 0; k < n; ++k) {
+            unsigned int* st = state6 + 6 * (size_t)k;
+            Xorwow s; for (int q = 0; q < 5; ++q) s.v[q] = st[q]; s.d = st[5];
+            const uint32_t d0 = s.d;
+            const V3<T> v = random_unit_vector<P>(s);
+            ((T*)out3)[3 * (size_t)k] = v.x; ((T*)out3)[3 * (size_t)k + 1] = v.y; ((T*)out3)[3 * (size_t)k + 2] = v.z;
+            if (rounds) rounds[k] = (int)((s.d - d0) * 945708813u / per_round);                // 362437 * 945708813 == 1 (mod 2^32)
+            for (int q = 0; q < 5; ++q) st[q] = s.v[q]; st[5] = s.d;
+        }
+    };
+    if (precision == 32) run(float());
+    else if (precision == 64) run(double());
+    else return -1;
+    return 0;
+}
+
+// The primary rays (camera.h:145-155) of n pixels {i, j}, each from its own state (advanced): {O, D} and unit(D).y, what the sky reads.
+int oracle_primary_rays(int precision, const int* cam_ints4, const void* cam_flat20, int n, const int* ij, unsigned int* state6, void* rays6, void* sky_uy) {
+    auto run = [&](auto tag) {
+        using T = decltype(tag);
+        Camera<T> c; camera_from_flat(c, cam_ints4, (const T*)cam_flat20);
+        for (int k = 0; k < n; ++k) {
+            unsigned int* st = state6 + 6 * (size_t)k;
+            Xorwow s; for (int q = 0; q < 5; ++q) s.v[q] = st[q]; s.d = st[5];
+            V3<T> org, dir;
+            primary_ray<T>(c, ij[2 * (size_t)k], ij[2 * (size_t)k + 1], s, org, dir);
+            T* r = (T*)rays6 + 6 * (size_t)k;
+            r[0] = org.x; r[1] = org.y; r[2] = org.z; r[3] = dir.x; r[4] = dir.y; r[5] = dir.z;
+            ((T*)sky_uy)[k] = unit<true>(dir).y;                                               // sky_colour's
+            for (int q = 0; q < 5; ++q) st[q] = s.v[q]; st[5] = s.d;
         }
     };
     if (precision == 32) run(float());

@@ -106,7 +106,7 @@ HIP_SYMBOLS = [
 ]
 # include/rtiow_debug.h: exported by lib/librtiow_hip_debug.so (the test build) only
 DEBUG_SYMBOLS = [
-    "rtiow_debug_read_rng", "rtiow_debug_read_costs", "rtiow_debug_timeline", "rtiow_debug_pixel_times", "rtiow_debug_ops", "rtiow_debug_jump_matrices", "rtiow_debug_grid_plan", "rtiow_debug_hit_world",
+    "rtiow_debug_read_rng", "rtiow_debug_read_costs", "rtiow_debug_timeline", "rtiow_debug_pixel_times", "rtiow_debug_ops", "rtiow_debug_jump_matrices", "rtiow_debug_grid_plan", "rtiow_debug_hit_world", "rtiow_debug_scatter",
     "rtiow_debug_gather_schedule", "rtiow_debug_read_order", "rtiow_debug_read_chunk_costs", "rtiow_debug_poison_staged",
 ]
 ORDER_NONE, ORDER_RENDER, ORDER_ACCUMULATE, ORDER_ADAPTIVE = 0, 1, 2, 3     # rtiow_debug_read_order: info["kind"]
@@ -548,6 +548,28 @@ class Renderer:
         self._lib.rtiow_debug_hit_world.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         self._check(self._lib.rtiow_debug_hit_world(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data))
         return t, idx
+
+    def debug_scatter(self, form, O, D, closest, hit, atten, sky_uy, depth, states):
+        """The scatter step alone, one call per lane (calls 64 w ... 64 w + 63 share wave w), from caller-supplied (closest, hit).
+        form 0: shade_step; 1: the bounded shade_step until it stops retrying; 2 (fp64): shade_front, merged_rounds, shade_back.
+        A dict of status [n] (1: the path ended), col / O / D / atten [n, 3], depth, trips, flags [n], states [n, 6] and
+        rounds_per_trip (the build's bound of the rejection loop)."""
+        self._need_debug()
+        dt = _dtype(self.precision)
+        n = len(hit)
+        real = np.zeros((n, 11), dt)
+        real[:, 0:3] = O; real[:, 3:6] = D; real[:, 6] = closest; real[:, 7:10] = atten; real[:, 10] = sky_uy
+        ints = np.ascontiguousarray(np.column_stack([hit, depth]), np.int32)
+        st = np.ascontiguousarray(states, np.uint32)
+        assert st.shape == (n, 6)
+        out = np.zeros((n, 12), dt); oi = np.zeros((n, 4), np.int32); os_ = np.zeros((n, 6), np.uint32)
+        rounds = ctypes.c_int(0)
+        vp = ctypes.c_void_p
+        self._lib.rtiow_debug_scatter.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
+        self._check(self._lib.rtiow_debug_scatter(self._h, form, n, real.ctypes.data, ints.ctypes.data, st.ctypes.data,
+                                                  out.ctypes.data, oi.ctypes.data, os_.ctypes.data, ctypes.addressof(rounds)))
+        return {"status": oi[:, 0].copy(), "col": out[:, 0:3].copy(), "O": out[:, 3:6].copy(), "D": out[:, 6:9].copy(), "atten": out[:, 9:12].copy(),
+                "depth": oi[:, 1].copy(), "trips": oi[:, 2].copy(), "flags": oi[:, 3].copy(), "states": os_, "rounds_per_trip": rounds.value}
 
     def set_schedule(self, schedule, waves_per_simd=0):
         self._check(self._lib.rtiow_set_schedule(self._h, schedule, waves_per_simd))

@@ -491,6 +491,77 @@ __global__ void __launch_bounds__(256) hit_probe_kernel(const RenderParams<T> p,
     }
 }
 
+// The scatter step alone, one call per lane (rtiow_debug_scatter): everything that follows hit_world in a trip, for a caller-supplied
+// (closest, hit).  Calls 64 w ... 64 w + 63 are the lanes of wave w (256-lane workgroups, no grid stride), so the caller decides who
+// shares the wave-level form choices of unit3 and sqrt_wave_checked.  FORM 0: shade_step<T, false>.  FORM 1: shade_step<T, true> with
+// RTIOW_RUV_ROUNDS_PER_ITERATION rounds, called again from the same (closest, hit) while it asks for a retry.  FORM 2 (fp64): shade_front,
+// merged_rounds bounded the same way -- on a lane still looking the next trip runs shade_front again, as persistent_body does -- then
+// shade_back.  A retry must leave O, D, atten and depth alone: checked here, flag bit 0.
+//   in_r 11 T {O, D, closest, atten, sky_uy}, in_i {hit, depth}, in_s 6 words -> out_r 12 T {col, O, D, atten}, out_i {ended, depth, trips, flags}, out_s
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }       // -0 is not +0, a NaN equals itself
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+template <class T> __device__ __forceinline__ bool same3(const V3<T>& a, const V3<T>& b) { return same_bits(a.x, b.x) && same_bits(a.y, b.y) && same_bits(a.z, b.z); }
+template <class T, int FORM>
+__global__ void __launch_bounds__(256) scatter_probe_kernel(const RenderParams<T> p, int n, const T* __restrict__ in_r, const int* __restrict__ in_i, const uint32_t* __restrict__ in_s,
+                                                            T* __restrict__ out_r, int* __restrict__ out_i, uint32_t* __restrict__ out_s) {
+    stage_scene<T, RTIOW_SCENE_SCALAR>(p);               // the shade records, when the launch keeps them in LDS (the loop table is not read)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const T* lds_shade = reinterpret_cast<const T*>(smem_raw + p.shade_offset);
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= (size_t)n) return;
+    const T* r = in_r + 11 * k;
+    PathState<T> st;
+    st.O = {r[0], r[1], r[2]}; st.D = {r[3], r[4], r[5]}; st.atten = {r[7], r[8], r[9]}; st.acc = {0, 0, 0};
+    const T closest = r[6];
+    st.sky_uy = r[10];
+    const int hit = in_i[2 * k];
+    st.sample = 0; st.depth = in_i[2 * k + 1];
+    st.rs.v0 = in_s[6 * k]; st.rs.v1 = in_s[6 * k + 1]; st.rs.v2 = in_s[6 * k + 2]; st.rs.v3 = in_s[6 * k + 3]; st.rs.v4 = in_s[6 * k + 4]; st.rs.d = in_s[6 * k + 5];
+    const V3<T> O0 = st.O, D0 = st.D, A0 = st.atten;
+    const int depth0 = st.depth;
+    V3<T> col = {0, 0, 0};
+    bool ended = false;
+    int trips = 0, flags = 0;
+    auto untouched = [&]() { return same3(st.O, O0) && same3(st.D, D0) && same3(st.atten, A0) && st.depth == depth0; };
+    if constexpr (FORM == 0) {
+        bool retry;
+        ended = shade_step<T, false>(p, lds_shade, st, closest, hit, col, 0, retry);
+        trips = 1;
+    } else if constexpr (FORM == 1) {
+        for (;;) {
+            bool retry;
+            ended = shade_step<T, true>(p, lds_shade, st, closest, hit, col, RTIOW_RUV_ROUNDS_PER_ITERATION, retry);
+            ++trips;
+            if (!retry) break;
+            if (ended || !untouched()) flags |= 1;
+        }
+    } else if constexpr (sizeof(T) == 8) {
+        ShadeCarry<T> sc;
+        sc.nrm = {0, 0, 0}; sc.fuzz = 0; sc.mtype = 0;
+        int f = shade_front<T>(p, lds_shade, st, closest, hit, col, sc);
+        trips = 1;
+        ended = f == SF_TERMINATED;
+        if (f == SF_NEED_RUV) {
+            T cx = 0, cy = 0, cz = 0, cl = 0;
+            for (;;) {
+                int looking = MR_RUV;
+                merged_rounds(st.rs, RTIOW_RUV_ROUNDS_PER_ITERATION, looking, cx, cy, cz, cl);
+                if (looking != MR_RUV) break;
+                if (!untouched()) flags |= 1;
+                f = shade_front<T>(p, lds_shade, st, closest, hit, col, sc);     // the next trip of a lane whose loop goes on
+                if (f != SF_NEED_RUV || !untouched()) flags |= 1;
+                ++trips;
+            }
+            ended = !shade_back<T>(p, lds_shade, st, sc, closest, hit, cx, cy, cz, cl);
+        }
+    }
+    T* o = out_r + 12 * k;
+    o[0] = col.x; o[1] = col.y; o[2] = col.z; o[3] = st.O.x; o[4] = st.O.y; o[5] = st.O.z; o[6] = st.D.x; o[7] = st.D.y; o[8] = st.D.z;
+    o[9] = st.atten.x; o[10] = st.atten.y; o[11] = st.atten.z;
+    out_i[4 * k] = ended ? 1 : 0; out_i[4 * k + 1] = st.depth; out_i[4 * k + 2] = trips; out_i[4 * k + 3] = flags;
+    out_s[6 * k] = st.rs.v0; out_s[6 * k + 1] = st.rs.v1; out_s[6 * k + 2] = st.rs.v2; out_s[6 * k + 3] = st.rs.v3; out_s[6 * k + 4] = st.rs.v4; out_s[6 * k + 5] = st.rs.d;
+}
+
 #endif  // RTIOW_DEBUG_API
 
 }  // namespace

@@ -344,6 +344,22 @@ int launch_probe(rtiow_handle_s* h, int n, const T* rays, T* t_out, int* index_o
     h->stats.scene_source = L.effective_source;
     return 0;
 }
+// rtiow_debug_scatter: the scatter step on n caller records (device memory), one per lane, with the shade records where the persistent launches
+// keep them (LDS or memory).  form 0 / 1 / 2: scatter_probe_kernel; 2 is fp64's rotated trip.
+template <class T>
+int launch_scatter_probe(rtiow_handle_s* h, int form, int n, const T* in_r, const int* in_i, const uint32_t* in_s, T* out_r, int* out_i, uint32_t* out_s) {
+    Launch<T> L{make_params<T>(h)};
+    if (int rc = layout_lds<T>(h, L, 256, true, false)) return rc;
+    void (*k)(const RenderParams<T>, int, const T*, const int*, const uint32_t*, T*, int*, uint32_t*) = nullptr;
+    if (form == 0) k = scatter_probe_kernel<T, 0>;
+    else if (form == 1) k = scatter_probe_kernel<T, 1>;
+    else if constexpr (sizeof(T) == 8) k = scatter_probe_kernel<T, 2>;
+    if (!k) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: form 2 (the rotated trip) exists in fp64 only");
+    HIP_TRY(h, allow_lds(k, L.lds));
+    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), L.lds, h->stream, L.p, n, in_r, in_i, in_s, out_r, out_i, out_s);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
 #endif
 
 // One chunk of progressive rendering (rtiow_accumulate): samples [h->acc_samples, h->acc_samples + samples) of every local pixel through

@@ -1170,6 +1170,33 @@ int rtiow_debug_hit_world(rtiow_handle h, int n, const void* rays, void* t_out, 
     return 0;
 }
 
+int rtiow_debug_scatter(rtiow_handle h, int form, int n, const void* in_real11, const int32_t* in_int2, const uint32_t* in_state6,
+                        void* out_real12, int32_t* out_int4, uint32_t* out_state6, int* rounds_per_trip) {
+    if (!h || n <= 0 || !in_real11 || !in_int2 || !in_state6 || !out_real12 || !out_int4 || !out_state6) return RTIOW_E_BADARG;
+    if (int rc = need_scene(h, "rtiow_debug_scatter")) return rc;
+    if (form < 0 || form > 2) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: form is 0, 1 or 2");
+    if (form == 2 && h->precision != 64) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: form 2 (the rotated trip) exists in fp64 only");
+    for (int k = 0; k < n; ++k)
+        if (in_int2[2 * (size_t)k] >= h->n) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: hit index beyond the scene");   // the kernel indexes the shade records with it
+    if (rounds_per_trip) *rounds_per_trip = RTIOW_RUV_ROUNDS_PER_ITERATION;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), N = (size_t)n;
+    DeviceBuffer<> ir, orr;
+    DeviceBuffer<int> ii, oi;
+    DeviceBuffer<uint32_t> is, os;
+    HIP_TRY(h, ir.ensure(N * 11 * es)); HIP_TRY(h, ii.ensure(N * 2 * sizeof(int))); HIP_TRY(h, is.ensure(N * 6 * sizeof(uint32_t)));
+    HIP_TRY(h, orr.ensure(N * 12 * es)); HIP_TRY(h, oi.ensure(N * 4 * sizeof(int))); HIP_TRY(h, os.ensure(N * 6 * sizeof(uint32_t)));
+    HIP_TRY(h, hipMemcpy(ir, in_real11, N * 11 * es, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(ii, in_int2, N * 2 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(is, in_state6, N * 6 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = by_precision(h, [&](auto t) { using T = decltype(t); return launch_scatter_probe<T>(h, form, n, ir.as<const T>(), ii, is, orr.as<T>(), oi, os); })) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out_real12, orr, N * 12 * es, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out_int4, oi, N * 4 * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out_state6, os, N * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int rtiow_debug_grid_plan(int n, const double* center_radius, const double* centre3, int32_t* dims4, double* params8,
                           uint16_t* cells, size_t cells_cap, int32_t* direct, size_t direct_cap, double* halfwidth) {
     if (n <= 0 || !center_radius || !centre3 || !dims4 || !params8) return RTIOW_E_BADARG;

@@ -155,6 +155,45 @@ class Oracle:
         assert self.L.oracle_hit_world(prec, len(cr), cr.ctypes.data, len(rays), rays.ctypes.data, t.ctypes.data, idx.ctypes.data) == 0
         return t, idx
 
+    def scatter(self, prec, scene, O, D, closest, hit, atten, sky_uy, depth, states):
+        """One scatter call per record on a COMPACT scene (oracle_scatter, the twin of Renderer.debug_scatter): a dict of
+        status [n] (1: the path ended), col / O / D / atten [n, 3], depth [n], states [n, 6]."""
+        dt = _dt(prec)
+        n = len(hit)
+        real = np.zeros((n, 11), dt)
+        real[:, 0:3] = O; real[:, 3:6] = D; real[:, 6] = closest; real[:, 7:10] = atten; real[:, 10] = sky_uy
+        ints = np.ascontiguousarray(np.column_stack([hit, depth]), np.int32)
+        st = np.ascontiguousarray(states, np.uint32)
+        cr = np.ascontiguousarray(scene["center_radius"], dt); af = np.ascontiguousarray(scene["albedo_fuzz"], dt)
+        ri = np.ascontiguousarray(scene["refraction_index"], dt); ty = np.ascontiguousarray(scene["type"], np.int32)
+        out = np.zeros((n, 12), dt); oi = np.zeros((n, 2), np.int32); os_ = np.zeros((n, 6), np.uint32)
+        vp = ctypes.c_void_p
+        self.L.oracle_scatter.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+        assert self.L.oracle_scatter(prec, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data, ty.ctypes.data, n,
+                                     real.ctypes.data, ints.ctypes.data, st.ctypes.data, out.ctypes.data, oi.ctypes.data, os_.ctypes.data) == 0
+        return {"status": oi[:, 0].copy(), "col": out[:, 0:3].copy(), "O": out[:, 3:6].copy(), "D": out[:, 6:9].copy(),
+                "atten": out[:, 9:12].copy(), "depth": oi[:, 1].copy(), "states": os_}
+
+    def random_unit_vector(self, prec, states):
+        """random_unit_vector from states [n, 6]: (vectors [n, 3], states afterwards [n, 6], rounds of the rejection loop [n])."""
+        st = np.array(states, np.uint32, ndmin=2)
+        v = np.zeros((len(st), 3), _dt(prec)); rounds = np.zeros(len(st), np.int32)
+        vp = ctypes.c_void_p
+        self.L.oracle_random_unit_vector.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        assert self.L.oracle_random_unit_vector(prec, len(st), st.ctypes.data, v.ctypes.data, rounds.ctypes.data) == 0
+        return v, st, rounds
+
+    def primary_rays(self, prec, cam, ij, states):
+        """The primary rays of pixels ij [n, 2] = {column, row}, each from its own state: (rays [n, 6], unit(D).y [n], states afterwards)."""
+        dt = _dt(prec)
+        ints, flat = self.camera_to_flat(cam, prec)
+        ij = np.ascontiguousarray(ij, np.int32); st = np.array(states, np.uint32, ndmin=2)
+        rays = np.zeros((len(ij), 6), dt); uy = np.zeros(len(ij), dt)
+        vp = ctypes.c_void_p
+        self.L.oracle_primary_rays.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp, vp]
+        assert self.L.oracle_primary_rays(prec, ints.ctypes.data, flat.ctypes.data, len(ij), ij.ctypes.data, st.ctypes.data, rays.ctypes.data, uy.ctypes.data) == 0
+        return rays, uy, st
+
     def render_serial(self, scene_id, W, H, S, depth, loop_form=RECURSIVE, sky_mode=SKY_CURRENT):
         """Serial-policy render (P3 text).  The defaults are the reference's serial program."""
         cap = W * H * 12 + 64

@@ -577,6 +577,36 @@ def test_rotated_fp64_trip_matches_the_oracle(rt, oracle, S, B, defocus):
     assert _same_bits(again, want)
 
 
+@pytest.mark.parametrize("prec", [32, 64])
+def test_render_on_the_material_lattice(rt, oracle, prec):
+    """The material lattice (tests/lattice.py: fuzz 0 ... 4 unclamped, refraction indices 1e-3 ... 1e3 with 1 and 2/3 among them, albedo
+    components 0 ... 1.5 and a denormal, radii 1e-3 ... 1000, two hollow glass spheres of negative inner radius, a glass sphere around the
+    camera) renders to the oracle's bits from all three scene sources under the static and the sorted schedule."""
+    from tests.lattice import lattice_scene
+    sc = lattice_scene(prec)
+    assert 40 <= len(sc["type"]) <= 60
+    cam = rt.camera(prec, 96, 56, 4, 12)
+    want, _ = oracle.render(prec, sc, cam, 1227)
+    assert np.isfinite(want).all() and float(np.asarray(want, np.float64).std()) > 0.05
+    for source in (rt.SCENE_GRID, rt.SCENE_LDS, rt.SCENE_LDS_EXACT):
+        for sched in (rt.SCHED_STATIC, rt.SCHED_SORTED):
+            got, _ = _render_cam(rt, prec, sc, cam, source, sched=sched)
+            assert _same_bits(got, want), (prec, source, sched, int((got != want).any(axis=2).sum()))
+
+
+def test_rotated_fp64_trip_on_the_material_lattice(rt, oracle):
+    """The lattice at 640 x 448 in fp64, which takes the rotated trip (test_rotated_fp64_trip_matches_the_oracle), against oracle rows
+    from the top, the middle and the bottom of the frame."""
+    from tests.lattice import lattice_scene
+    W, H = 640, 448
+    sc = lattice_scene(64)
+    cam = rt.camera(64, W, H, 2, 12)
+    got, _ = _render_cam(rt, 64, sc, cam, rt.SCENE_GRID)
+    for row0 in (0, 216, 300, 440):
+        want, _ = oracle.render(64, sc, cam, 1227, row0=row0, row1=row0 + 8)
+        assert _same_bits(got[row0:row0 + 8], want), row0
+
+
 def test_primary_ray_normalisation_paths_match_the_oracle(rt, oracle):
     """gen_primary takes 1/sqrt(|D|^2) through the short in-range sequence when the host can bound |D| for the
     whole frame (primary_rays_in_range) and through the compiler's full IEEE sequence otherwise.  The same view

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import compact
+from tests.lattice import lattice_scene
 from tests.test_denoise import _filter_np, _same_bits, _setup
 from tests.test_denoise_variance import _filter_np as _filter_var_np
 
@@ -37,7 +38,7 @@ def chain_np(rt, oracle, prec, scene_id, cam, rows, max_bounces, max_fuzz):
     """(normal', albedo', depth', bounces, facts) as section 12 defines them: hit_world on the CPU oracle once per bounce level for the
     chains still alive, the rest in T with plain operations.  facts counts what the tests want to have met."""
     dt = np.float32 if prec == 32 else np.float64
-    sc = compact(rt.build_scene(scene_id, prec))
+    sc = lattice_scene(prec) if scene_id == LATTICE else compact(rt.build_scene(scene_id, prec))
     cr = np.asarray(sc["center_radius"], dt).reshape(-1, 4)
     af = np.asarray(sc["albedo_fuzz"], dt).reshape(-1, 4)
     eta = np.asarray(sc["refraction_index"], dt).reshape(-1)
@@ -130,10 +131,11 @@ def _reference(rt, oracle, prec, scene_id, W, H, max_bounces, max_fuzz):
     return _references[key]
 
 
-CASES = [(3, 67, 41, 1, INF), (3, 67, 41, 2, INF), (3, 67, 41, 8, INF), (1, 96, 54, 8, INF), (3, 67, 41, 8, 0.25)]
+LATTICE = "lattice"       # tests/lattice.py instead of a built-in scene: refraction indices other than 1.5 (below 1 and exactly 1 among them), hollow spheres
+CASES = [(3, 67, 41, 1, INF), (3, 67, 41, 2, INF), (3, 67, 41, 8, INF), (1, 96, 54, 8, INF), (3, 67, 41, 8, 0.25), (LATTICE, 67, 41, 8, INF)]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "s%d_%dx%d_b%d_f%s" % c)
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "s%s_%dx%d_b%d_f%s" % c)
 @pytest.mark.parametrize("prec", [32, 64])
 def test_filter_guides_are_the_definition(rt, oracle, prec, case):
     scene_id, W, H, max_bounces, max_fuzz = case
@@ -145,13 +147,15 @@ def test_filter_guides_are_the_definition(rt, oracle, prec, case):
         assert (wb >= 2).sum() >= 0.02 * npix, (case, int((wb >= 2).sum()))
     if max_bounces in (1, 2):
         assert facts["specular_at_cap"] >= 1 and int(wb.max()) == max_bounces, (case, facts)
-    if scene_id == 1:
+    if scene_id in (1, LATTICE):
         assert facts["tir"] >= 1, (case, facts)
     if max_fuzz != INF:
         assert facts["rough_metal_first_hit"] >= 1, (case, facts)
     for source in (3, 1):                                # GRID, SCALAR
         with rt.Renderer(0, prec) as r:
-            _setup(r, rt, prec, scene_id, W, H, B=10, source=source)
+            _setup(r, rt, prec, 3 if scene_id == LATTICE else scene_id, W, H, B=10, source=source)
+            if scene_id == LATTICE:
+                r.set_scene(lattice_scene(prec))
             r.set_guide_mode(SPECULAR, max_bounces, max_fuzz)
             n, a, z, b = r.filter_guides()
         where = (prec, case, source)
