@@ -482,6 +482,34 @@ int rtiow_denoise_history_variance(rtiow_handle h, int levels, double sigma_vari
                                    int variance_radius, float* kernel_ms);
 int rtiow_read_history_variance(rtiow_handle h, void* var /* npix T */, size_t npix);
 
+/* ---- Recurrent history: a filtered temporal image as the next base.  rtiow_history_commit hands the raw
+ * temporal image to the next frame, so every frame starts from a history that still carries its full noise.
+ * rtiow_history_commit_filtered is rtiow_history_commit with one step in front: the {C.rgb, M} of the temporal image, as the last
+ * rtiow_history_update(_clipped) wrote it, is replaced by {H'.rgb, M} below before it becomes the base -- one level of the a-trous
+ * filter at step 1, fed back (Schied et al. 2017).  The base keeps its format; nothing new is carried.  Everything in T, left to right
+ * as written, plain * + - /, no fused multiply-add.  For pixel p = (x, y): C, M = the temporal image; N, A, Z = the filter guides of the
+ * current guide mode (normal, albedo, depth), the ones rtiow_denoise_history steers by.
+ *   M_p > 0 is false: H'_p = C_p (which is 0 there), M'_p = M_p, bit for bit.
+ *   Otherwise the taps are q = p + (dx, dy), dy then dx in -2..2, at step 1.  A tap counts when q is inside the frame and M_q > 0.
+ *   kern = K[dx+2] K[dy+2], K = {1/16, 1/4, 3/8, 1/4, 1/16};  ec, en, ea, ez, e = ((ec ic + en i_n) + ea i_a) + ez i_z and
+ *   w = kern / (1 + e) exactly as level 0 of rtiow_denoise: ic = (T)(1 / sigma_color^2) and so on, computed in double and rounded
+ *   once, sigma = +inf turning a term off.  From 0, in tap order, over the taps that count: S = S + w C_q per channel, Wt = Wt + w.
+ *   F = S / Wt per channel.  feedback == 1 (decided on the host): H'_p = F; otherwise H'_p = C_p + (T)feedback (F - C_p) per channel.
+ *   M'_p = M_p: the length is not touched, so rtiow_history_plan still predicts Mout bit for bit.  Comparisons with NaN are false.
+ * After this step the call is rtiow_history_commit: the new base is {H', M'}, the current FIRST-HIT {normal, depth} and the current
+ * camera; the temporal image, the plan and the guides go stale.  The result is written into the buffer that held the old base (the
+ * first commit of a handle allocates it); the buffer of the temporal image is left behind, stale.  Stale guides (e.g. after
+ * rtiow_set_guide_mode) are rendered first, inside kernel_ms; kernel_ms == NULL: asynchronous on the handle's stream.
+ * RTIOW_E_BADARG: a sigma <= 0 or NaN, feedback outside (0, 1] or NaN.  RTIOW_E_STATE: the temporal image is stale; the handle is
+ * sharded.  A failing call leaves the handle as it was.  The call touches nothing else: framebuffer, accumulation, counts and errors,
+ * the denoised buffer, the bits of the next chunk.  Not available on groups.
+ * rtiow_read_history_base copies the base's {H.rgb} and {M} as planes, in the layout of rtiow_read_history (either pointer may be
+ * NULL; npix = height x width of the frame the base was committed at, else RTIOW_E_BADARG), after either commit.  RTIOW_E_STATE: the
+ * base is empty or the handle is sharded. */
+int rtiow_history_commit_filtered(rtiow_handle h, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, double feedback,
+                                  float* kernel_ms);
+int rtiow_read_history_base(rtiow_handle h, void* rgb /* npix*3 T, linear */, void* length /* npix T */, size_t npix);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -99,6 +99,7 @@ HIP_SYMBOLS = [
     "rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget",
     "rtiow_history_update_clipped",
     "rtiow_denoise_history_variance", "rtiow_read_history_variance",
+    "rtiow_history_commit_filtered", "rtiow_read_history_base",
     "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
     "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
     "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
@@ -229,6 +230,9 @@ def load_hip_library(debug=False):
         lib.rtiow_denoise_history_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                        ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_read_history_variance.argtypes = [H, vp, ctypes.c_size_t]
+        lib.rtiow_history_commit_filtered.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                      ctypes.POINTER(ctypes.c_float)]
+        lib.rtiow_read_history_base.argtypes = [H, vp, vp, ctypes.c_size_t]
         lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
         lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
         lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
@@ -453,6 +457,13 @@ HISTORY_CLIP_GAMMA = 0.5
 # 1.00 on scene 3: it does not pay on both yet, and denoise_history() stays the filter the documents recommend for the temporal image.
 HISTORY_VARIANCE_RADIUS = 1
 HISTORY_SIGMA_VARIANCE = 2.0
+# Renderer.history_commit_filtered defaults: the best of scripts/history_feedback_probe.py's sweep by the same rule on the clipped walk at
+# 0.5 degrees a frame, i.e. the smallest worse-of-two-scenes ratio R_T of the temporal image's MSE with filtered commits to its MSE with
+# plain commits, first of equals in grid order (profiles/history_feedback/history_feedback_probe.json).  At these
+# R_T is 0.97 on scene 1 and 0.93 on scene 3, but denoise_history() of that image is worse than after plain commits (1.09 / 1.09): it
+# does not pay yet, and history_commit() stays the commit the documents recommend.
+HISTORY_FEEDBACK_SIGMA_COLOR = 0.05
+HISTORY_FEEDBACK = 1.0
 # The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
 # to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
 # section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
@@ -798,6 +809,25 @@ class Renderer:
         """Make the temporal image, the current guides and the current camera the base of later updates (buffers change owners, nothing
         is copied).  Then move the camera: the temporal image and the guides are stale after the call."""
         self._check(self._lib.rtiow_history_commit(self._h))
+
+    def history_commit_filtered(self, sigma_color=HISTORY_FEEDBACK_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_albedo=DENOISE_SIGMA_ALBEDO,
+                                sigma_depth=DENOISE_SIGMA_DEPTH, feedback=HISTORY_FEEDBACK, sync=True):
+        """history_commit() of a filtered temporal image: one level of denoise_history()'s filter at step 1,
+        over the pixels that hold samples, replaces the colour before it becomes the base, blended with the unfiltered colour by
+        `feedback` in (0, 1] (1: the filtered colour alone); the lengths are kept, so history_plan() predicts as before.  The filter
+        steers by the filter guides of the current guide mode; the base keeps the first-hit guides.  Returns the kernel time in ms
+        (None when sync=False)."""
+        ms = ctypes.c_float(0)
+        self._check(self._lib.rtiow_history_commit_filtered(self._h, float(sigma_color), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                            float(feedback), ctypes.byref(ms) if sync else None))
+        return ms.value if sync else None
+
+    def history_base(self):
+        """(rgb [H, W, 3] linear, length [H, W]) of the base the last history_commit() or history_commit_filtered() left."""
+        rgb = np.empty((self.local_rows, self.width, 3), self.dtype)
+        length = np.empty((self.local_rows, self.width), self.dtype)
+        self._check(self._lib.rtiow_read_history_base(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
+        return rgb, length
 
     def history(self):
         """(rgb [H, W, 3] linear, length [H, W]) of the temporal image: the blended colour and its history length in samples."""

@@ -647,6 +647,26 @@ int launch_history_clip(rtiow_handle_s* h, double depth_tol, double normal_cos, 
     return 0;
 }
 
+// feedback_filter_kernel over the temporal image and the filter guides (rtiow_history_commit_filtered): {H', M} goes straight into
+// h->hist_base_hm, the buffer of the old base, which is dead at a commit (the first commit of a handle, or one at a larger frame, gets
+// its storage here).  inv2[4] = 1 / sigma^2 of colour, normal, albedo, depth (double), rounded to T here as launch_denoise's level 0
+// does.  feedback == 1 is decided here: the kernel then stores the filtered colour itself.  The caller has checked state and arguments,
+// made the guides current and makes the result the base.
+template <class T>
+int launch_feedback(rtiow_handle_s* h, const double inv2[4], double feedback) {
+    const int W = img_w(h), rows = h->local_rows;
+    const size_t npix = (size_t)W * rows;
+    HIP_TRY(h, h->hist_base_hm.ensure(npix * 4 * sizeof(T)));
+    FilterWeights<T> fw;
+    fw.ic = (T)inv2[0]; fw.in = (T)inv2[1]; fw.ia = (T)inv2[2]; fw.iz = (T)inv2[3];
+    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    hipLaunchKernelGGL(feedback_filter_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, fw, feedback == 1.0 ? 0 : 1, (T)feedback,
+                       h->hist_cm.as<const Vec4<T>>(), filter_nd(h).as<const Vec4<T>>(), filter_alb(h).as<const Vec4<T>>(),
+                       h->hist_base_hm.as<Vec4<T>>());
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
 // history_length_kernel over the current guides and the base into h->plan_m (rtiow_history_plan): the m of launch_history for the same
 // tolerances, before any sample of the frame; the count of pixels with m > 0 goes to h->plan_ctr.  The caller has checked state and
 // arguments and made the guides current.

@@ -65,6 +65,7 @@
 #include "device/denoise_variance.h"
 #include "device/history.h"
 #include "device/history_clip.h"
+#include "device/history_feedback.h"
 #include "device/history_budget.h"
 #include "device/temporal_noise.h"
 #include "device/guide_chain.h"
@@ -822,6 +823,54 @@ int rtiow_history_commit(rtiow_handle h) {
     h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
     h->hist_base_ok = true;
     h->hist_ok = false; h->plan_ok = false; h->guides_ok = false;
+    return 0;
+}
+
+// ---- The filtered commit
+int rtiow_history_commit_filtered(rtiow_handle h, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, double feedback,
+                                  float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
+    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_commit_filtered: every sigma must be > 0 (+inf turns its term off)");
+    if (!(feedback > 0 && feedback <= 1)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_commit_filtered: need feedback in (0, 1]");
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit_filtered: not on a sharded handle");
+    if (!h->have_camera || h->n == 0 || !h->hist_ok)
+        return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit_filtered: no temporal image for the current camera (rtiow_history_update)");
+    double inv2[4];
+    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_feedback<decltype(t)>(h, inv2, feedback); }))) return rc;
+    if ((rc = timed_end(h, kernel_ms))) return rc;
+    // the kernel wrote {H', M} into the buffer of the old base, so only the guides change owners; the temporal image stays where it
+    // is and goes stale, as after rtiow_history_commit
+    std::swap(h->hist_base_nd, h->guide_nd);
+    h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
+    h->hist_base_ok = true;
+    h->hist_ok = false; h->plan_ok = false; h->guides_ok = false;
+    return 0;
+}
+
+int rtiow_read_history_base(rtiow_handle h, void* rgb, void* length, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_base: not on a sharded handle");
+    if (!h->hist_base_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_base: no history base (rtiow_history_commit)");
+    // the base keeps the frame it was committed at (it survives rtiow_set_camera)
+    const size_t want = h->precision == 64 ? (size_t)h->hist_cam64.img_width * (size_t)h->hist_cam64.img_height
+                                           : (size_t)h->hist_cam32.img_width * (size_t)h->hist_cam32.img_height;
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_base: npix must be height x width of the base's frame");
+    if (!rgb && !length) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h);
+    std::vector<unsigned char> hm(want * 4 * es);
+    if (int rc = copy_out(h, hm.data(), h->hist_base_hm, hm.size())) return rc;
+    for (size_t k = 0; k < want; ++k) {                  // {H.rgb, M} -> planes
+        if (rgb) std::memcpy((unsigned char*)rgb + 3 * k * es, hm.data() + 4 * k * es, 3 * es);
+        if (length) std::memcpy((unsigned char*)length + k * es, hm.data() + (4 * k + 3) * es, es);
+    }
     return 0;
 }
 
