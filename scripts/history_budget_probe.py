@@ -5,10 +5,10 @@
       one of rtiow_accumulate_adaptive at equal active count -- none, so that the chunk is its select and its finish and only the select
       differs -- the calls alternating in one process; HIP-event kernel times, medians of --runs (at least 20) after one warm-up each.
       The plan gathers the update's taps and moves less, so its median must not exceed the update's (exit status 1 otherwise);
-  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/test_history.py (8 cameras, 0.5 degrees apart,
+  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/preview_drive.py (8 cameras, 0.5 degrees apart,
       independent noise, update and commit every frame), against 1024 samples at the last camera: the walk with 4 uniform samples a
       frame next to the walk with plan and budget chunks to convergence every frame, at the defaults of raytracingincuda_amd/api.py
-      (tests/test_history_budget.py's walk, uniform_sampler, budget_sampler, compare; test_it_pays asserts on these): primary rays of the
+      (tests/preview_drive.py's walk, uniform_sampler, budget_sampler, compare; test_it_pays asserts on these): primary rays of the
       whole walk, linear MSE of the temporal image at the last frame over the whole frame and over the pixels with m = 0 in the last
       frame's plan;
   (c) --sweep: the same over target x min_samples x chunk x max_history.  A setting is eligible if its walk traces no more primary rays
@@ -42,7 +42,7 @@ BIG = 2 ** 31 - 1
 
 def cost(prec, runs):
     import raytracingincuda_amd as rt
-    from tests.test_history import _orbit
+    from tests.preview_drive import orbit
     a = rt.api
     W, H = 1920, 1080
     params = (a.HISTORY_DEPTH_TOL, a.HISTORY_NORMAL_COS, a.HISTORY_MAX)
@@ -50,7 +50,7 @@ def cost(prec, runs):
         r.set_camera(rt.camera_look(prec, W, H, 1, 50)); r.set_scene(rt.build_scene(3, prec)); r.init_rng(1227)
         r.accumulate_adaptive(4, 0.0, min_samples=4)
         r.history_update(); r.history_commit()
-        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=_orbit(0.5))); r.init_rng(1228)
+        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=orbit(0.5))); r.init_rng(1228)
         r.accumulate_adaptive(4, 0.0, min_samples=4)
         r.render_guides()
 
@@ -82,8 +82,7 @@ def cost(prec, runs):
 
 def quality(sweep):
     import raytracingincuda_amd as rt
-    from tests.test_history import orbit_reference
-    from tests.test_history_budget import budget_sampler, compare, uniform_sampler, walk
+    from tests.preview_drive import budget_sampler, compare, orbit_reference, uniform_sampler, walk
     a = rt.api
     default = (a.BUDGET_TARGET, a.BUDGET_MIN_SAMPLES, a.BUDGET_CHUNK, a.HISTORY_MAX)
     grid = list(itertools.product(SWEEP_TARGET, SWEEP_MIN_SAMPLES, SWEEP_CHUNK, SWEEP_MAX_HISTORY)) if sweep else []

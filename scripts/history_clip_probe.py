@@ -6,7 +6,7 @@ scripts/history_probe.py:
       (levels = 1, default sigmas) in the same process, the five calls alternating; HIP-event kernel times, medians of --runs (at least
       20) after one warm-up each.  The rule of DESIGN.md section 4.10 applies to radius 1: its median must not exceed the filter
       level's (exit status 1 otherwise); radii 2 and 3 are reported;
-  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/test_history_clip.py (clip_walk: 8 cameras, 4
+  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/preview_drive.py (clip_walk: 8 cameras, 4
       samples each with independent noise, seeds 1227 + frame, update and commit every frame) at 0.5 and at 2 degrees a frame, against
       1024 samples at the last camera: clip_radius x clip_gamma x max_history swept, each walk's linear MSE divided by that of the
       plain walk at the same max_history -- for the temporal image (r_t) and for denoise_history() of it (r_dt), over the whole frame
@@ -41,7 +41,7 @@ SPEEDS = (0.5, 2.0)
 
 def cost(prec, runs):
     import raytracingincuda_amd as rt
-    from tests.test_history import _orbit
+    from tests.preview_drive import orbit
     a = rt.api
     W, H = 1920, 1080
     params = (a.HISTORY_DEPTH_TOL, a.HISTORY_NORMAL_COS, a.HISTORY_MAX)
@@ -49,7 +49,7 @@ def cost(prec, runs):
         r.set_camera(rt.camera_look(prec, W, H, 1, 50)); r.set_scene(rt.build_scene(3, prec)); r.init_rng(1227)
         r.accumulate(4)
         r.history_update(); r.history_commit()
-        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=_orbit(0.5))); r.init_rng(1228)
+        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=orbit(0.5))); r.init_rng(1228)
         r.accumulate(4)
         r.render_guides()
 
@@ -92,8 +92,8 @@ def name(radius, gamma, cap):
 def quality(step_deg):
     import numpy as np
     import raytracingincuda_amd as rt
-    from tests.test_history import _begin, _orbit
-    from tests.test_history_clip import clip_walk, mse
+    from tests.preview_drive import begin, clip_walk, orbit
+    from tests.preview_model import mse
     a = rt.api
     prec, W, H, B, frames = 32, 320, 180, 50, 8
     grid = list(itertools.product(SWEEP_RADIUS, SWEEP_GAMMA, SWEEP_MAX_HISTORY))
@@ -101,7 +101,7 @@ def quality(step_deg):
     for scene_id in (1, 3):
         scene = "scene%d" % scene_id
         with rt.Renderer(0, prec) as r:                                    # the reference and the mask at the last camera
-            _begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * (frames - 1))))
+            begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(step_deg * (frames - 1))))
             r.accumulate(1024)
             ref = r.read_linear().astype(np.float64)
             r.set_guide_mode(rt.GUIDES_SPECULAR, 8, float("inf"))

@@ -61,9 +61,9 @@ def clip_of(rt, update):
 def reference_and_mask(rt, scene_id, step_deg, frame, W=320, H=180, B=50, prec=32, samples=1024):
     """The linear image of `samples` samples at camera `frame` of the walk, and the pixels whose centre ray meets a mirror or glass."""
     import numpy as np
-    from tests.test_history import _begin, _orbit
+    from tests.preview_drive import begin, orbit
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * frame)))
+        begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(step_deg * frame)))
         r.accumulate(samples)
         ref = r.read_linear().astype(np.float64)
         r.set_guide_mode(rt.GUIDES_SPECULAR, 8, float("inf"))
@@ -74,8 +74,8 @@ def reference_and_mask(rt, scene_id, step_deg, frame, W=320, H=180, B=50, prec=3
 def quality(step_deg):
     import numpy as np
     import raytracingincuda_amd as rt
-    from tests.test_history_clip import mse
-    from tests.test_history_feedback import feedback_walk
+    from tests.preview_drive import feedback_walk
+    from tests.preview_model import mse
     frames, spp = 8, 4
     grid = list(itertools.product(SWEEP_SIGMA, SWEEP_FEEDBACK))
     out = {u: {"sweep": {name(*p): {} for p in grid}, "plain_commit_mse": {}} for u in UPDATES}
@@ -117,25 +117,25 @@ def blur(frames):
     """Part (c): two handles walk side by side, one committing plainly, one through the filter at the defaults."""
     import numpy as np
     import raytracingincuda_amd as rt
-    from tests.test_history import _begin, _move, _orbit
-    from tests.test_history_clip import mse
+    from tests.preview_drive import begin, move, orbit
+    from tests.preview_model import mse
     a = rt.api
     step_deg, spp, W, H, B, prec = 0.5, 4, 320, 180, 50, 32
     clip = clip_of(rt, "clipped_update")
     out = {"frames": frames, "degrees_a_frame": step_deg, "setting": name(a.HISTORY_FEEDBACK_SIGMA_COLOR, a.HISTORY_FEEDBACK)}
     for scene_id in (1, 3):
-        cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * k)) for k in range(frames)]
+        cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(step_deg * k)) for k in range(frames)]
         curve = []
         with rt.Renderer(0, prec) as plain, rt.Renderer(0, prec) as filt, rt.Renderer(0, prec) as truth:
             for r in (plain, filt, truth):
-                _begin(r, rt, prec, scene_id, cams[0])
+                begin(r, rt, prec, scene_id, cams[0])
             for k, cam in enumerate(cams):
-                _move(truth, cam, 99)
+                move(truth, cam, 99)
                 truth.accumulate(1024)
                 ref = truth.read_linear().astype(np.float64)
                 err = []
                 for r in (plain, filt):
-                    _move(r, cam, 1227 + k)
+                    move(r, cam, 1227 + k)
                     r.accumulate(spp)
                     r.history_update_clipped(*clip)
                     err.append(mse(r.history()[0].astype(np.float64), ref))
@@ -151,12 +151,12 @@ def blur(frames):
 
 def probe_frame(rt, r, prec):
     """scripts/history_clip_probe.py's frame with a clipped update on top."""
-    from tests.test_history import _orbit
+    from tests.preview_drive import orbit
     W, H = 1920, 1080
     r.set_camera(rt.camera_look(prec, W, H, 1, 50)); r.set_scene(rt.build_scene(3, prec)); r.init_rng(1227)
     r.accumulate(4)
     r.history_update_clipped(); r.history_commit()
-    r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=_orbit(0.5))); r.init_rng(1228)
+    r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=orbit(0.5))); r.init_rng(1228)
     r.accumulate(4)
     r.render_guides()
     r.history_update_clipped()

@@ -4,7 +4,7 @@
       guides current; rtiow_history_update next to ONE level of rtiow_denoise (levels = 1, default sigmas) in the same process, the
       two calls alternating; HIP-event kernel times, medians of --runs (at least 20) after one warm-up each.  The update gathers 4
       taps where a filter level gathers 25, so its median must not exceed the level's (exit status 1 otherwise);
-  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/test_history.py (orbit_walk: 8 cameras, 0.5
+  (b) quality at 320 x 180, 50 bounces, fp32, scenes 1 and 3, over the walk of tests/preview_drive.py (orbit_walk: 8 cameras, 0.5
       degrees apart, 4 samples each with independent noise, update and commit every frame), against 1024 samples at the last camera:
       q_t = linear MSE of the temporal image / MSE of the noisy accumulation, q_dt = MSE of denoise_history() / MSE of denoise(),
       at the defaults of raytracingincuda_amd/api.py (tests/test_history.py asserts on these);
@@ -36,14 +36,14 @@ SWEEP_MAX_HISTORY = (8.0, 16.0, 64.0, float("inf"))
 
 def cost(prec, runs):
     import raytracingincuda_amd as rt
-    from tests.test_history import _orbit
+    from tests.preview_drive import orbit
     a = rt.api
     W, H = 1920, 1080
     with rt.Renderer(0, prec) as r:
         r.set_camera(rt.camera_look(prec, W, H, 1, 50)); r.set_scene(rt.build_scene(3, prec)); r.init_rng(1227)
         r.accumulate(4)
         r.history_update(); r.history_commit()
-        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=_orbit(0.5))); r.init_rng(1228)
+        r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=orbit(0.5))); r.init_rng(1228)
         r.accumulate(4)
         r.render_guides()
 
@@ -68,7 +68,8 @@ def cost(prec, runs):
 
 def quality(sweep):
     import raytracingincuda_amd as rt
-    from tests.test_history import orbit_reference, orbit_walk, quality as q_of
+    from tests.preview_drive import orbit_reference, orbit_walk
+    from tests.preview_model import quality as q_of
     a = rt.api
     default = (a.HISTORY_DEPTH_TOL, a.HISTORY_NORMAL_COS, a.HISTORY_MAX)
     grid = list(itertools.product(SWEEP_DEPTH_TOL, SWEEP_NORMAL_COS, SWEEP_MAX_HISTORY)) if sweep else []

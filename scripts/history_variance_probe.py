@@ -49,13 +49,13 @@ ROUTES = ("spatial", "measured")
 
 def probe_frame(rt, r, prec, route):
     """scripts/history_clip_probe.py's frame with a clipped update on top."""
-    from tests.test_history import _orbit
+    from tests.preview_drive import orbit
     W, H = 1920, 1080
     chunk = r.accumulate if route == "spatial" else r.accumulate_with_variance
     r.set_camera(rt.camera_look(prec, W, H, 1, 50)); r.set_scene(rt.build_scene(3, prec)); r.init_rng(1227)
     chunk(4)
     r.history_update_clipped(); r.history_commit()
-    r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=_orbit(0.5))); r.init_rng(1228)
+    r.set_camera(rt.camera_look(prec, W, H, 1, 50, lookfrom=orbit(0.5))); r.init_rng(1228)
     chunk(4)
     r.render_guides()
     r.history_update_clipped()
@@ -151,14 +151,14 @@ def walk(rt, scene_id, step_deg, route, grid, frames=8, spp=4, W=320, H=180, B=5
     """The walk of (c); returns the linear images of the last frame: denoise_history() at its defaults and denoise_history_variance()
     at every grid point and at the defaults."""
     import numpy as np
-    from tests.test_history import _begin, _move, _orbit
+    from tests.preview_drive import begin, move, orbit
     a = rt.api
-    cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * k)) for k in range(frames)]
+    cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(step_deg * k)) for k in range(frames)]
     out = {}
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cams[0])
+        begin(r, rt, prec, scene_id, cams[0])
         for k, cam in enumerate(cams):
-            _move(r, cam, 1227 + k)
+            move(r, cam, 1227 + k)
             if route == "spatial":
                 r.accumulate(spp)
             else:
@@ -177,8 +177,8 @@ def walk(rt, scene_id, step_deg, route, grid, frames=8, spp=4, W=320, H=180, B=5
 def quality(step_deg):
     import numpy as np
     import raytracingincuda_amd as rt
-    from tests.test_history import _begin, _orbit
-    from tests.test_history_clip import mse
+    from tests.preview_drive import begin, orbit
+    from tests.preview_model import mse
     a = rt.api
     prec, W, H, B, frames = 32, 320, 180, 50, 8
     grid = list(itertools.product(SWEEP_SIGMA, SWEEP_RADIUS))
@@ -186,7 +186,7 @@ def quality(step_deg):
     for scene_id in (1, 3):
         scene = "scene%d" % scene_id
         with rt.Renderer(0, prec) as r:                                    # the reference and the mask at the last camera
-            _begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * (frames - 1))))
+            begin(r, rt, prec, scene_id, rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(step_deg * (frames - 1))))
             r.accumulate(1024)
             ref = r.read_linear().astype(np.float64)
             r.set_guide_mode(rt.GUIDES_SPECULAR, 8, float("inf"))

@@ -2,6 +2,7 @@
 framebuffer holds the very bits rtiow_render leaves with samples_per_pixel = k1 + ... + ki -- whatever the chunk sizes, schedule, scene
 source or shard layout -- because a pixel's samples are one sequential RNG chain summed in sample order and every chunk resumes each
 pixel from its exact state."""
+import functools
 import hashlib
 import json
 import os
@@ -10,12 +11,16 @@ import zlib
 import numpy as np
 import pytest
 
+from tests import preview_drive
 from tests.conftest import compact
+from tests.preview_drive import one_shot
+from tests.preview_model import same_bits
 
 pytestmark = pytest.mark.gpu
 
 SCHEDULES = (0, 1, 2)        # RTIOW_SCHED_STATIC, PERSISTENT, SORTED
 SOURCES = (0, 1, 2, 3)       # RTIOW_SCENE_LDS, SCALAR, LDS_EXACT, GRID
+_setup = functools.partial(preview_drive.setup, B=50, sched=2)
 
 
 @pytest.fixture(scope="module")
@@ -23,27 +28,6 @@ def rt(native):
     import torch
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     return native
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _setup(r, rt, prec, scene_id, W, H, S=1, B=50, source=3, sched=2, shard=None, seed=1227):
-    r.set_camera(rt.camera(prec, W, H, S, B))
-    r.set_scene(rt.build_scene(scene_id, prec))
-    r.set_scene_source(source)
-    r.set_schedule(sched, 0)
-    if shard:
-        r.set_shard(*shard)
-    r.init_rng(seed)
-
-
-def _one_shot(rt, prec, scene_id, W, H, S, B, source=3, sched=2, shard=None):
-    with rt.Renderer(0, prec) as r:
-        _setup(r, rt, prec, scene_id, W, H, S, B, source, sched, shard)
-        r.render(0)
-        return r.read_framebuffer()
 
 
 def test_previews_equal_one_shot_renders(rt):
@@ -59,7 +43,7 @@ def test_previews_equal_one_shot_renders(rt):
                     total += k
                     assert ms > 0 and r.accumulated_samples == total
                     got = r.read_framebuffer()
-                    assert _same_bits(got, _one_shot(rt, prec, scene_id, W, H, total, B)), (prec, scene_id, total)
+                    assert same_bits(got, one_shot(rt, prec, scene_id, W, H, total, B)), (prec, scene_id, total)
                 st = r.stats()
                 assert st["phases"] == 1 and st["prepass_samples"] == 0 and st["primary_rays"] == W * H * chunks[-1]
 
@@ -75,13 +59,13 @@ def test_previews_equal_the_oracle(rt, oracle):
                 r.accumulate(k)
                 total += k
                 want, _ = oracle.render(prec, sc, rt.camera(prec, W, H, total, B), 1227)
-                assert _same_bits(r.read_framebuffer(), want), (prec, total)
+                assert same_bits(r.read_framebuffer(), want), (prec, total)
 
 
 def test_schedule_and_source_do_not_change_the_bits(rt):
     W, H, B = 96, 72, 25                                      # 6912 pixels: the sorted schedule ranks the second chunk
     for prec in (32, 64):
-        want = _one_shot(rt, prec, 3, W, H, 10, B)
+        want = one_shot(rt, prec, 3, W, H, 10, B)
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 3, W, H, B=B)
             for sched in SCHEDULES:
@@ -91,7 +75,7 @@ def test_schedule_and_source_do_not_change_the_bits(rt):
                     r.reset_accumulation()
                     r.accumulate(5, threads=8)
                     r.accumulate(5)
-                    assert _same_bits(r.read_framebuffer(), want), (prec, sched, source)
+                    assert same_bits(r.read_framebuffer(), want), (prec, sched, source)
             # the schedule switched between two chunks, without a reset
             for first, second in ((0, 2), (2, 1), (1, 0), (2, 0)):
                 r.set_scene_source(3)
@@ -101,7 +85,7 @@ def test_schedule_and_source_do_not_change_the_bits(rt):
                 r.set_schedule(second, 0)
                 r.accumulate(5)
                 assert r.accumulated_samples == 10
-                assert _same_bits(r.read_framebuffer(), want), (prec, first, second)
+                assert same_bits(r.read_framebuffer(), want), (prec, first, second)
 
 
 @pytest.mark.parametrize("name,chunks", [("config3_headline_scene3_1920x1080_100spp_50b_f32", [1, 9, 40, 50]),
@@ -125,7 +109,7 @@ def test_full_frames_accumulated_match_the_goldens(rt, golden_dir, name, chunks)
 def test_sharded_chunks_assemble_to_the_one_shot_image(rt):
     W, H, B, nranks, strip = 322, 183, 25, 3, 2
     for prec in (32, 64):
-        want = _one_shot(rt, prec, 3, W, H, 8, B)
+        want = one_shot(rt, prec, 3, W, H, 8, B)
         full = np.zeros_like(want)
         rows = 0
         for rank in range(nranks):
@@ -136,7 +120,7 @@ def test_sharded_chunks_assemble_to_the_one_shot_image(rt):
                 part = r.read_framebuffer()
             rows += part.shape[0]
             rt.place_rows(full, part, rank, nranks, strip)
-        assert rows == H and _same_bits(full, want), prec
+        assert rows == H and same_bits(full, want), prec
 
 
 def test_render_and_count_between_chunks_leave_the_accumulation_alone(rt):
@@ -146,17 +130,17 @@ def test_render_and_count_between_chunks_leave_the_accumulation_alone(rt):
             _setup(r, rt, prec, 3, W, H, S=5, B=B)              # the camera's own 5 spp: what render / count_segments use
             r.accumulate(3)
             r.render(0)                                          # the sorted schedule's own prepass records and hand-over
-            assert _same_bits(r.read_framebuffer(), _one_shot(rt, prec, 3, W, H, 5, B))
+            assert same_bits(r.read_framebuffer(), one_shot(rt, prec, 3, W, H, 5, B))
             r.count_segments(0)
             r.accumulate(4)
             assert r.accumulated_samples == 7
-            assert _same_bits(r.read_framebuffer(), _one_shot(rt, prec, 3, W, H, 7, B)), prec
+            assert same_bits(r.read_framebuffer(), one_shot(rt, prec, 3, W, H, 7, B)), prec
 
 
 def test_what_resets_the_accumulation(rt):
     W, H, B = 96, 72, 25
     prec = 32
-    want1 = _one_shot(rt, prec, 3, W, H, 1, B)
+    want1 = one_shot(rt, prec, 3, W, H, 1, B)
     cam = rt.camera(prec, W, H, 1, B)
     resets = {
         "set_camera": lambda r: r.set_camera(cam),
@@ -174,7 +158,7 @@ def test_what_resets_the_accumulation(rt):
             assert r.accumulated_samples == 0, name
             r.init_rng(1227)                                     # set_camera / set_shard ask for it again
             r.accumulate(1)
-            assert _same_bits(r.read_framebuffer(), want1), name
+            assert same_bits(r.read_framebuffer(), want1), name
         # a new scene source, schedule or framebuffer does not change the image: the total goes on
         r.reset_accumulation()
         r.accumulate(2)
@@ -183,7 +167,7 @@ def test_what_resets_the_accumulation(rt):
         assert r.accumulated_samples == 2
         r.accumulate(3)
         assert r.accumulated_samples == 5
-        assert _same_bits(r.read_framebuffer(), _one_shot(rt, prec, 3, W, H, 5, B))
+        assert same_bits(r.read_framebuffer(), one_shot(rt, prec, 3, W, H, 5, B))
 
 
 def test_errors_and_a_bound_torch_framebuffer(rt, oracle):
@@ -222,4 +206,4 @@ def test_errors_and_a_bound_torch_framebuffer(rt, oracle):
         full = g.gather()
         stream.synchronize()
         assert r.accumulated_samples == S
-    assert _same_bits(full.cpu().numpy(), want)
+    assert same_bits(full.cpu().numpy(), want)

@@ -1,15 +1,21 @@
 """Adaptive progressive rendering (rtiow_accumulate_adaptive) on the GPU.  Every pixel stops at its own sample count, and the bar is still
 BIT-EXACT: a pixel with count n holds the very bits rtiow_render (and the CPU oracle) give that pixel with samples_per_pixel = n, because
 its samples are one sequential RNG chain summed in sample order and every chunk resumes it from its exact state."""
+import functools
+
 import numpy as np
 import pytest
 
+from tests import preview_drive
 from tests.conftest import compact
+from tests.preview_drive import one_shot, run_mixed
+from tests.preview_model import luminance, same_bits
 
 pytestmark = pytest.mark.gpu
 
 SCHEDULES = (0, 1, 2)        # RTIOW_SCHED_STATIC, PERSISTENT, SORTED
 SOURCES = (0, 1, 2, 3)       # RTIOW_SCENE_LDS, SCALAR, LDS_EXACT, GRID
+_setup = functools.partial(preview_drive.setup, sched=2)
 
 
 @pytest.fixture(scope="module")
@@ -19,60 +25,22 @@ def rt(native):
     return native
 
 
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _setup(r, rt, prec, scene_id, W, H, S=1, B=25, source=3, sched=2, shard=None, seed=1227):
-    r.set_camera(rt.camera(prec, W, H, S, B))
-    r.set_scene(rt.build_scene(scene_id, prec))
-    r.set_scene_source(source)
-    r.set_schedule(sched, 0)
-    if shard:
-        r.set_shard(*shard)
-    r.init_rng(seed)
-
-
-def _one_shot(rt, prec, scene_id, W, H, S, B, source=3, sched=2):
-    with rt.Renderer(0, prec) as r:
-        _setup(r, rt, prec, scene_id, W, H, S, B, source, sched)
-        r.render(0)
-        return r.read_framebuffer()
-
-
-def _luminance(c):
-    return 0.2126 * c[..., 0] + 0.7152 * c[..., 1] + 0.0722 * c[..., 2]
-
-
-def _run_mixed(r, calls):
-    """min_samples = 4, samples = 4: the first call runs everyone, later calls use the frame's median error as the threshold (a mix of
-    counts).  Returns the thresholds so that other configurations can replay the same calls."""
-    thresholds = []
-    r.accumulate_adaptive(4, 0.0, min_samples=4)
-    for _ in range(calls - 1):
-        _, err = r.adaptive_state()
-        thr = float(np.median(err)) if not thresholds else thresholds[0]
-        thresholds.append(thr)
-        r.accumulate_adaptive(4, thr, min_samples=4)
-    return thresholds
-
-
 def test_every_pixel_is_exact_at_its_own_count(rt):
     W, H, B = 320, 192, 25
     for prec in (32, 64):
         for scene_id in (3, 1):
             with rt.Renderer(0, prec) as r:
                 _setup(r, rt, prec, scene_id, W, H, B=B)
-                _run_mixed(r, 4)
+                run_mixed(r, 4)
                 counts, _ = r.adaptive_state()
                 img = r.read_framebuffer()
                 assert r.accumulated_samples == counts.max()
             distinct = np.unique(counts)
             assert len(distinct) >= 2, (prec, scene_id, distinct)            # the threshold left a mix
             for n in distinct:
-                want = _one_shot(rt, prec, scene_id, W, H, int(n), B)
+                want = one_shot(rt, prec, scene_id, W, H, int(n), B)
                 sel = counts == n
-                assert _same_bits(img[sel], want[sel]), (prec, scene_id, n)
+                assert same_bits(img[sel], want[sel]), (prec, scene_id, n)
 
 
 def test_every_pixel_matches_the_oracle_at_its_own_count(rt, oracle):
@@ -81,14 +49,14 @@ def test_every_pixel_matches_the_oracle_at_its_own_count(rt, oracle):
         sc = compact(oracle.build_scene(3, prec))
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 3, W, H, B=B)
-            _run_mixed(r, 3)
+            run_mixed(r, 3)
             counts, _ = r.adaptive_state()
             img = r.read_framebuffer()
         assert len(np.unique(counts)) >= 2
         for n in np.unique(counts):
             want, _ = oracle.render(prec, sc, rt.camera(prec, W, H, int(n), B), 1227)
             sel = counts == n
-            assert _same_bits(img[sel], want[sel]), (prec, n)
+            assert same_bits(img[sel], want[sel]), (prec, n)
 
 
 def test_the_decision_rule(rt):
@@ -120,11 +88,11 @@ def test_the_error_estimate(rt):
         for n in range(1, N + 1):
             r.accumulate(1)
             acc = n * r.read_framebuffer().astype(np.float64) ** 2
-            ys.append(_luminance(acc - prev))
+            ys.append(luminance(acc - prev))
             prev = acc
     ys = np.array(ys)
     s2 = (ys ** 2).sum(axis=0)
-    m = _luminance(prev) / N
+    m = luminance(prev) / N
     var = np.maximum(0.0, (s2 - N * m * m) / (N - 1))
     want = np.sqrt(var / N) / (m + 1e-3)
     with rt.Renderer(0, prec) as r:
@@ -151,7 +119,7 @@ def test_limits(rt):
                 total += k
                 counts, _ = a.adaptive_state()
                 assert active == W * H and (counts == total).all() and a.accumulated_samples == total
-                assert _same_bits(a.read_framebuffer(), p.read_framebuffer()), (prec, total)
+                assert same_bits(a.read_framebuffer(), p.read_framebuffer()), (prec, total)
         # rel_error = 0: a pixel stops only when its error is exactly 0 (no spread left that the sums resolve)
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 3, W, H, B=B)
@@ -171,7 +139,7 @@ def test_limits(rt):
                 assert active == 0
             counts, _ = r.adaptive_state()
             assert (counts == 4).all()
-            assert _same_bits(r.read_framebuffer(), _one_shot(rt, prec, 3, W, H, 4, B))
+            assert same_bits(r.read_framebuffer(), one_shot(rt, prec, 3, W, H, 4, B))
         # max_samples is never passed, not even for a pixel below min_samples
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 3, W, H, B=B)
@@ -188,7 +156,7 @@ def test_schedule_source_and_shards_do_not_change_counts_or_bits(rt):
     for prec in (32, 64):
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 3, W, H, B=B)
-            thresholds = _run_mixed(r, 3)
+            thresholds = run_mixed(r, 3)
             want_counts, _ = r.adaptive_state()
             want_img = r.read_framebuffer()
         assert len(np.unique(want_counts)) >= 2
@@ -208,7 +176,7 @@ def test_schedule_source_and_shards_do_not_change_counts_or_bits(rt):
                     replay(r)
                     counts, _ = r.adaptive_state()
                     assert np.array_equal(counts, want_counts), (prec, sched, source)
-                    assert _same_bits(r.read_framebuffer(), want_img), (prec, sched, source)
+                    assert same_bits(r.read_framebuffer(), want_img), (prec, sched, source)
         nranks, strip = 2, 8
         full = np.zeros_like(want_img)
         full_counts = np.zeros_like(want_counts)
@@ -221,7 +189,7 @@ def test_schedule_source_and_shards_do_not_change_counts_or_bits(rt):
                 rows = r.local_row_map()
             rt.place_rows(full, part, rank, nranks, strip)
             full_counts[rows] = counts
-        assert np.array_equal(full_counts, want_counts) and _same_bits(full, want_img), prec
+        assert np.array_equal(full_counts, want_counts) and same_bits(full, want_img), prec
 
 
 def test_render_between_calls_leaves_the_state_alone(rt):
@@ -235,12 +203,12 @@ def test_render_between_calls_leaves_the_state_alone(rt):
             _, err = a.adaptive_state()
             thr = float(np.median(err))
             b.render(0)
-            assert _same_bits(b.read_framebuffer(), _one_shot(rt, prec, 3, W, H, 5, B))
+            assert same_bits(b.read_framebuffer(), one_shot(rt, prec, 3, W, H, 5, B))
             b.count_segments(0)
             a.accumulate_adaptive(4, thr, min_samples=4)
             b.accumulate_adaptive(4, thr, min_samples=4)
             assert np.array_equal(a.adaptive_state()[0], b.adaptive_state()[0])
-            assert _same_bits(a.read_framebuffer(), b.read_framebuffer()), prec
+            assert same_bits(a.read_framebuffer(), b.read_framebuffer()), prec
 
 
 def test_modes_resets_and_errors(rt):
@@ -287,7 +255,7 @@ def test_modes_resets_and_errors(rt):
             "init_rng": lambda r: r.init_rng(1227),
             "reset_accumulation": lambda r: r.reset_accumulation(),
         }
-        want2 = _one_shot(rt, prec, 3, W, H, 2, B, source=0, sched=1)
+        want2 = one_shot(rt, prec, 3, W, H, 2, B, source=0, sched=1)
         for name, reset in resets.items():
             r.reset_accumulation()
             r.accumulate_adaptive(2, 0.0)
@@ -298,7 +266,7 @@ def test_modes_resets_and_errors(rt):
             r.accumulate(1)                                      # plain chunks are allowed again
             r.reset_accumulation()
             _, active = r.accumulate_adaptive(2, 0.0)
-            assert active == W * H and _same_bits(r.read_framebuffer(), want2), name
+            assert active == W * H and same_bits(r.read_framebuffer(), want2), name
 
 
 def test_a_bound_torch_framebuffer_receives_the_preview(rt, oracle):
@@ -315,4 +283,4 @@ def test_a_bound_torch_framebuffer_receives_the_preview(rt, oracle):
         r.synchronize()
         assert r.accumulated_samples == 3
     torch.cuda.synchronize()
-    assert _same_bits(fb.cpu().numpy(), want)
+    assert same_bits(fb.cpu().numpy(), want)

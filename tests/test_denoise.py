@@ -1,17 +1,17 @@
 """Denoised previews of progressive rendering on the GPU: the linear read of the accumulation, the first-hit
 guide buffers and the edge-avoiding a-trous filter.  Every output is defined operation by operation in T with plain * + - / and sqrt,
-so each is checked BIT FOR BIT against a numpy restatement (the guides' hit distances against the CPU oracle's hit_world)."""
+so each is checked BIT FOR BIT against its numpy restatement in tests/preview_model.py (the guides' hit distances against the CPU oracle's
+hit_world)."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from tests.conftest import compact
+from tests.preview_drive import E_BADARG, E_STATE, run_mixed
+from tests.preview_drive import setup as _setup    # not a bare `setup`: older pytests take that name for a module hook
+from tests.preview_model import filter_np, gamma, guides_np, same_bits
 
 pytestmark = pytest.mark.gpu
-
-E_BADARG, E_STATE = -1, -2
-K = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
 
 
 @pytest.fixture(scope="module")
@@ -19,100 +19,6 @@ def rt(native):
     import torch
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     return native
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _setup(r, rt, prec, scene_id, W, H, S=1, B=25, source=3, shard=None):
-    r.set_camera(rt.camera(prec, W, H, S, B))
-    r.set_scene(rt.build_scene(scene_id, prec))
-    r.set_scene_source(source)
-    if shard:
-        r.set_shard(*shard)
-    r.init_rng(1227)
-
-
-def _run_mixed(r, calls):
-    """tests/test_adaptive.py's pattern: everyone 4 samples, then the frame's median error as the threshold (a mix of counts)."""
-    r.accumulate_adaptive(4, 0.0, min_samples=4)
-    thr = None
-    for _ in range(calls - 1):
-        if thr is None:
-            thr = float(np.median(r.adaptive_state()[1]))
-        r.accumulate_adaptive(4, thr, min_samples=4)
-
-
-def _gamma(x):
-    z = np.zeros_like(x)
-    pos = x > 0
-    z[pos] = np.sqrt(x[pos])
-    return z
-
-
-# ---- numpy restatements of section 9
-
-def _guides_np(rt, oracle, prec, scene_id, cam, rows):
-    """(normal, albedo, depth) as defined: centre ray per pixel, hit_world on the CPU oracle, the rest in T with plain ops."""
-    dt = np.float32 if prec == 32 else np.float64
-    sc = compact(rt.build_scene(scene_id, prec))
-    cr = np.asarray(sc["center_radius"], dt).reshape(-1, 4)
-    W = cam.img_width
-    O = np.array(cam.center[:], dt)
-    p00, du, dv = (np.array(v[:], dt) for v in (cam.pixel00_loc, cam.pixel_delta_u, cam.pixel_delta_v))
-    fi = np.arange(W).astype(dt)[None, :, None]
-    fj = np.asarray(rows).astype(dt)[:, None, None]
-    ps = (p00 + fi * du) + fj * dv
-    D = ps - O
-    rays = np.concatenate([np.broadcast_to(O, D.shape), D], axis=-1).reshape(-1, 6)
-    t, k = oracle.hit_world(prec, cr, rays)
-    t = t.reshape(len(rows), W); k = k.reshape(len(rows), W)
-    hit = k >= 0
-    kk = np.where(hit, k, 0)
-    with np.errstate(all="ignore"):
-        P = O + t[..., None] * D
-        inv_r = dt(1) / cr[kk, 3]
-        out = (P - cr[kk, :3]) * inv_r[..., None]
-        dn = (D[..., 0] * out[..., 0] + D[..., 1] * out[..., 1]) + D[..., 2] * out[..., 2]
-    normal = np.where((dn < 0)[..., None], out, -out)
-    af = np.asarray(sc["albedo_fuzz"], dt).reshape(-1, 4)
-    glass = (np.asarray(sc["type"]) == 2)[kk]
-    albedo = np.where(glass[..., None], dt(1), af[kk, :3])
-    normal = np.where(hit[..., None], normal, dt(0)).astype(dt)
-    albedo = np.where(hit[..., None], albedo, dt(0)).astype(dt)
-    depth = np.where(hit, t, dt(0)).astype(dt)
-    return normal, albedo, depth, hit
-
-
-def _filter_np(c0, normal, albedo, depth, levels, sc, sn, sa, sz):
-    dt = c0.dtype.type
-    H, W, _ = c0.shape
-    inv = [1.0 / (s * s) for s in (sc, sn, sa, sz)]
-    c = c0
-    for k in range(levels):
-        s = 1 << k
-        ic, i_n, i_a, i_z = dt(inv[0] * 4.0 ** k), dt(inv[1]), dt(inv[2]), dt(inv[3])
-        S = np.zeros_like(c); Wt = np.zeros((H, W), c.dtype)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                ys = np.arange(H) + dy * s; xs = np.arange(W) + dx * s
-                vy = (ys >= 0) & (ys < H); vx = (xs >= 0) & (xs < W)
-                valid = vy[:, None] & vx[None, :]
-                yq = np.clip(ys, 0, H - 1); xq = np.clip(xs, 0, W - 1)
-                cq = c[yq][:, xq]; nq = normal[yq][:, xq]; aq = albedo[yq][:, xq]; zq = depth[yq][:, xq]
-                kern = dt(K[dx + 2]) * dt(K[dy + 2])
-                d = cq - c; dn = nq - normal; da = aq - albedo; dz = zq - depth
-                ec = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-                en = (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]
-                ea = (da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2]
-                ez = dz * dz
-                e = ((ec * ic + en * i_n) + ea * i_a) + ez * i_z
-                w = kern / (dt(1) + e)
-                S = np.where(valid[..., None], S + w[..., None] * cq, S)
-                Wt = np.where(valid, Wt + w, Wt)
-        c = S / Wt[..., None]
-    return _gamma(c)
 
 
 # ---- 1. the linear read
@@ -127,13 +33,13 @@ def test_linear_read_is_exact(rt):
                 r.accumulate(k)
                 lin = r.read_linear()
                 assert lin.dtype == r.dtype and lin.shape == (H, W, 3)
-                assert _same_bits(_gamma(lin), r.read_framebuffer()), (prec, k)
+                assert same_bits(gamma(lin), r.read_framebuffer()), (prec, k)
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 1, W, H)
-            _run_mixed(r, 3)
+            run_mixed(r, 3)
             counts, _ = r.adaptive_state()
             assert len(np.unique(counts)) >= 2
-            assert _same_bits(_gamma(r.read_linear()), r.read_framebuffer()), prec
+            assert same_bits(gamma(r.read_linear()), r.read_framebuffer()), prec
 
 
 # ---- 2. the guides
@@ -148,12 +54,12 @@ def test_guides_are_exact(rt, oracle, prec):
             _setup(r, rt, prec, scene_id, W, H, B=10, source=source, shard=shard)
             rows = r.local_row_map()
             n, a, z = r.guides()
-        wn, wa, wz, hit = _guides_np(rt, oracle, prec, scene_id, cam, rows)
+        wn, wa, wz, hit = guides_np(rt, oracle, prec, scene_id, cam, rows)
         assert 0.2 < hit.mean() < 0.99, (scene_id, hit.mean())
         where = (prec, scene_id, source, shard)
-        assert _same_bits(z, wz), where
-        assert _same_bits(n, wn), where
-        assert _same_bits(a, wa), where
+        assert same_bits(z, wz), where
+        assert same_bits(n, wn), where
+        assert same_bits(a, wa), where
 
 
 # ---- 3. the filter
@@ -162,8 +68,8 @@ def _check_filter(r, levels, sig):
     lin = r.read_linear()
     n, a, z = r.guides()
     got = r.denoise(levels, *sig)
-    want = _filter_np(lin, n, a, z, levels, *sig)
-    return _same_bits(got, want)
+    want = filter_np(lin, n, a, z, levels, *sig)
+    return same_bits(got, want)
 
 
 @pytest.mark.parametrize("prec", [32, 64])
@@ -178,7 +84,7 @@ def test_filter_is_exact(rt, prec):
             assert _check_filter(r, levels, sig), ("plain", prec, levels, sig)
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 1, W, H)
-        _run_mixed(r, 3)
+        run_mixed(r, 3)
         for levels, sig in ((1, (1.0, 0.2, 0.3, 2.0)), (5, (0.5, 0.1, 0.1, 1.0)), (3, (inf, 0.1, inf, inf))):
             assert _check_filter(r, levels, sig), ("adaptive", prec, levels, sig)
 
@@ -199,21 +105,21 @@ def test_denoise_leaves_the_accumulation_alone(rt):
             r.denoise()
             r.denoise(3, 0.2, 0.3, 0.4, 0.5, sync=False)
             r.synchronize()
-            assert _same_bits(r.read_framebuffer(), fb), prec
+            assert same_bits(r.read_framebuffer(), fb), prec
             assert r.accumulated_samples == 4
             r.accumulate(4)
-            assert _same_bits(r.read_framebuffer(), want), prec
+            assert same_bits(r.read_framebuffer(), want), prec
             assert r.accumulated_samples == 8
             ptr, nbytes = r.denoised_device_ptr()
             assert ptr and nbytes == W * H * 3 * (prec // 8)
         with rt.Renderer(0, prec) as r:                  # adaptive: counts, errors and preview stay
             _setup(r, rt, prec, 1, W, H)
-            _run_mixed(r, 3)
+            run_mixed(r, 3)
             c0, e0 = r.adaptive_state()
             fb = r.read_framebuffer()
             r.denoise()
             c1, e1 = r.adaptive_state()
-            assert _same_bits(c1, c0) and _same_bits(e1, e0) and _same_bits(r.read_framebuffer(), fb), prec
+            assert same_bits(c1, c0) and same_bits(e1, e0) and same_bits(r.read_framebuffer(), fb), prec
 
 
 def test_guides_go_stale_and_error_codes(rt):
@@ -247,7 +153,7 @@ def test_guides_go_stale_and_error_codes(rt):
         # rtiow_denoise renders stale guides first, and they are those of rtiow_render_guides
         r.denoise(2)
         n1, _, z1 = r.guides()
-        assert _same_bits(n1, n0) and _same_bits(z1, z0)
+        assert same_bits(n1, n0) and same_bits(z1, z0)
         r.reset_accumulation()
         assert lib.rtiow_denoise(r._h, 5, 1.0, 1.0, 1.0, 1.0, None) == E_STATE
     with rt.Renderer(0, 32) as r:                        # a sharded handle: guides yes, denoise no

@@ -1,18 +1,17 @@
 """Variance-guided denoising on the GPU: the variance plane of an adaptive accumulation and the a-trous
 filter whose colour edge-stop follows it.  The plane is checked against the error the library already publishes and against numpy on
-rebuilt samples; the filter, defined operation by operation in T with plain * + - /, BIT FOR BIT against a numpy restatement and, with
-the colour term off, against rtiow_denoise itself."""
+rebuilt samples; the filter, defined operation by operation in T with plain * + - /, BIT FOR BIT against its numpy restatement in
+tests/preview_model.py and, with the colour term off, against rtiow_denoise itself."""
 import ctypes
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from tests.preview_drive import E_BADARG, E_STATE, INF, check_against_err, run_mixed
+from tests.preview_drive import setup as _setup    # not a bare `setup`: older pytests take that name for a module hook
+from tests.preview_model import luminance, same_bits, variance_filter_np
 
-E_BADARG, E_STATE = -1, -2
-K = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
-B3 = (1 / 4, 1 / 2, 1 / 4)
-INF = float("inf")
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -22,117 +21,12 @@ def rt(native):
     return native
 
 
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _setup(r, rt, prec, scene_id, W, H, S=1, B=25, source=3, shard=None):
-    r.set_camera(rt.camera(prec, W, H, S, B))
-    r.set_scene(rt.build_scene(scene_id, prec))
-    r.set_scene_source(source)
-    if shard:
-        r.set_shard(*shard)
-    r.init_rng(1227)
-
-
-def _run_mixed(r, calls):
-    """tests/test_adaptive.py's pattern: everyone 4 samples, then the frame's median error as the threshold (a mix of counts)."""
-    r.accumulate_adaptive(4, 0.0, min_samples=4)
-    thr = None
-    for _ in range(calls - 1):
-        if thr is None:
-            thr = float(np.median(r.adaptive_state()[1]))
-        r.accumulate_adaptive(4, thr, min_samples=4)
-
-
-def _gamma(x):
-    z = np.zeros_like(x)
-    pos = x > 0
-    z[pos] = np.sqrt(x[pos])
-    return z
-
-
-def _luminance(c):
-    return (0.2126 * c[..., 0] + 0.7152 * c[..., 1]) + 0.0722 * c[..., 2]
-
-
 def _variance_call(r, npix):
     buf = np.empty(max(npix, 1), r.dtype)
     return r._lib.rtiow_read_variance(r._h, buf.ctypes.data, npix)
 
 
-# ---- numpy restatement of section 10
-
-def _shifted(a, dy, dx):
-    """(a at p + (dx, dy), clamped; whether that tap lies in the frame)."""
-    H, W = a.shape[:2]
-    ys = np.arange(H) + dy; xs = np.arange(W) + dx
-    valid = ((ys >= 0) & (ys < H))[:, None] & ((xs >= 0) & (xs < W))[None, :]
-    return a[np.clip(ys, 0, H - 1)][:, np.clip(xs, 0, W - 1)], valid
-
-
-def _filter_np(c0, v0, normal, albedo, depth, levels, sv, sn, sa, sz):
-    dt = c0.dtype.type
-    H, W, _ = c0.shape
-    with np.errstate(over="ignore"):
-        sv2 = dt(sv * sv)
-    colour_on = bool(np.isfinite(sv2))
-    i_n, i_a, i_z = (dt(1.0 / (s * s)) for s in (sn, sa, sz))
-    eps = dt(1e-8)
-    c, v = c0, v0
-    for k in range(levels):
-        s = 1 << k
-        if colour_on:
-            gv = np.zeros((H, W), c.dtype); gw = np.zeros((H, W), c.dtype)
-            for dy in range(-1, 2):
-                for dx in range(-1, 2):
-                    vq, valid = _shifted(v, dy, dx)
-                    b = dt(B3[dx + 1]) * dt(B3[dy + 1])
-                    gv = np.where(valid, gv + b * vq, gv)
-                    gw = np.where(valid, gw + b, gw)
-            g = gv / gw
-            ip = dt(4.0 ** k) / (sv2 * g + eps)
-        else:
-            ip = np.zeros((H, W), c.dtype)
-        S = np.zeros_like(c); Wt = np.zeros((H, W), c.dtype); U = np.zeros((H, W), c.dtype)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                cq, valid = _shifted(c, dy * s, dx * s)
-                vq, _ = _shifted(v, dy * s, dx * s)
-                nq, _ = _shifted(normal, dy * s, dx * s); aq, _ = _shifted(albedo, dy * s, dx * s); zq, _ = _shifted(depth, dy * s, dx * s)
-                kern = dt(K[dx + 2]) * dt(K[dy + 2])
-                d = cq - c; dn = nq - normal; da = aq - albedo; dz = zq - depth
-                ec = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-                en = (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]
-                ea = (da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2]
-                ez = dz * dz
-                e = ((ec * ip + en * i_n) + ea * i_a) + ez * i_z
-                w = kern / (dt(1) + e)
-                S = np.where(valid[..., None], S + w[..., None] * cq, S)
-                Wt = np.where(valid, Wt + w, Wt)
-                U = np.where(valid, U + (w * w) * vq, U)
-        c = S / Wt[..., None]
-        v = U / (Wt * Wt)
-    assert c.dtype == c0.dtype and v.dtype == c0.dtype
-    return _gamma(c)
-
-
 # ---- 4. the variance plane
-
-def _check_against_err(r, where):
-    """(a): sqrt(V) / (m + 1e-3) is the published err where n >= 2; (c): V == 0 exactly where n < 2."""
-    counts, err = r.adaptive_state()
-    V = r.variance()
-    assert V.dtype == r.dtype and V.shape == counts.shape, where
-    assert (V >= 0).all() and np.isfinite(V).all(), where
-    assert (V[counts < 2] == 0).all(), where
-    m = _luminance(r.read_linear().astype(np.float64))
-    have = counts >= 2
-    assert have.any() or (counts < 2).all(), where
-    np.testing.assert_allclose(np.sqrt(V.astype(np.float64))[have] / (m[have] + 1e-3), err[have].astype(np.float64), rtol=1e-5, atol=1e-12,
-                               err_msg=str(where))
-    return counts, V
-
 
 @pytest.mark.parametrize("prec", [32, 64])
 def test_variance_matches_the_published_error(rt, prec):
@@ -140,28 +34,28 @@ def test_variance_matches_the_published_error(rt, prec):
     with rt.Renderer(0, prec) as r:                      # uniform with variance
         _setup(r, rt, prec, 3, W, H)
         r.accumulate_with_variance(5); r.accumulate_with_variance(3)
-        counts, V = _check_against_err(r, ("uniform", prec))
+        counts, V = check_against_err(r, ("uniform", prec))
         assert (counts == 8).all() and (V > 0).mean() > 0.5
     with rt.Renderer(0, prec) as r:                      # (d) a mix of counts
         _setup(r, rt, prec, 1, W, H)
-        _run_mixed(r, 3)
-        counts, V = _check_against_err(r, ("mixed", prec))
+        run_mixed(r, 3)
+        counts, V = check_against_err(r, ("mixed", prec))
         assert len(np.unique(counts)) >= 2
     with rt.Renderer(0, prec) as r:                      # (d) a shard
         _setup(r, rt, prec, 3, W, H, shard=(1, 3, 8))
-        _run_mixed(r, 2)
-        counts, V = _check_against_err(r, ("shard", prec))
+        run_mixed(r, 2)
+        counts, V = check_against_err(r, ("shard", prec))
         assert V.shape == (r.local_rows, W) and 0 < r.local_rows < H
     # (c) counts below two: everyone at 1 sample, and nobody sampled at all (4 more samples would pass max_samples = 3)
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 3, W, H)
         r.accumulate_adaptive(1, 0.0, min_samples=1, max_samples=1)
-        counts, V = _check_against_err(r, ("one sample", prec))
+        counts, V = check_against_err(r, ("one sample", prec))
         assert (counts == 1).all() and (V == 0).all()
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 3, W, H)
         _, active = r.accumulate_adaptive(4, 0.0, min_samples=0, max_samples=3)
-        counts, V = _check_against_err(r, ("no sample", prec))
+        counts, V = check_against_err(r, ("no sample", prec))
         assert active == 0 and (counts == 0).all() and (V == 0).all()
 
 
@@ -175,11 +69,11 @@ def test_variance_against_rebuilt_samples(rt):
         for n in range(1, N + 1):
             r.accumulate(1)
             acc = n * r.read_framebuffer().astype(np.float64) ** 2
-            ys.append(_luminance(acc - prev))
+            ys.append(luminance(acc - prev))
             prev = acc
     ys = np.array(ys)
     s2 = (ys ** 2).sum(axis=0)
-    m = _luminance(prev) / N
+    m = luminance(prev) / N
     var = np.maximum(0.0, (s2 - N * m * m) / (N - 1))
     want = var / N
     with rt.Renderer(0, prec) as r:
@@ -200,11 +94,11 @@ def _check_filter(r, levels, sig):
     V = r.variance()
     n, a, z = r.guides()
     got = r.denoise_variance(levels, *sig)
-    want = _filter_np(lin, V, n, a, z, levels, *sig)
+    want = variance_filter_np(lin, V, n, a, z, levels, *sig)
     assert np.isfinite(got).all()
     if sig[0] == INF:                                    # the recurrences coincide: the committed kernel gives the same colour
-        assert _same_bits(got, r.denoise(levels, *sig)), ("against denoise()", levels, sig)
-    return _same_bits(got, want)
+        assert same_bits(got, r.denoise(levels, *sig)), ("against denoise()", levels, sig)
+    return same_bits(got, want)
 
 
 @pytest.mark.parametrize("prec", [32, 64])
@@ -219,7 +113,7 @@ def test_filter_is_exact(rt, prec):
             assert _check_filter(r, levels, sig), ("uniform", prec, 3, levels, sig)
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 1, W, H)
-        _run_mixed(r, 3)
+        run_mixed(r, 3)
         assert len(np.unique(r.adaptive_state()[0])) >= 2
         for levels, sig in cases:
             assert _check_filter(r, levels, sig), ("mixed", prec, 1, levels, sig)
@@ -230,7 +124,7 @@ def test_filter_is_exact(rt, prec):
             assert _check_filter(r, levels, sig), ("uniform", prec, 1, levels, sig)
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 3, W, H)
-        _run_mixed(r, 3)
+        run_mixed(r, 3)
         for levels, sig in cases[1:3] + cases[5:6]:
             assert _check_filter(r, levels, sig), ("mixed", prec, 3, levels, sig)
 
@@ -244,7 +138,7 @@ def test_uniform_with_variance_is_the_plain_accumulation(rt):
             for k in (3, 5):
                 assert a.accumulate_with_variance(k) >= 0
                 p.accumulate(k)
-                assert _same_bits(a.read_framebuffer(), p.read_framebuffer()) and _same_bits(a.read_linear(), p.read_linear()), (prec, k)
+                assert same_bits(a.read_framebuffer(), p.read_framebuffer()) and same_bits(a.read_linear(), p.read_linear()), (prec, k)
             assert a.accumulate_with_variance(2, sync=False) is None
             a.synchronize()
             assert a.accumulated_samples == 10
@@ -257,38 +151,38 @@ def test_the_new_calls_leave_everything_else_alone(rt):
     for prec in (32, 64):
         with rt.Renderer(0, prec) as ref:
             _setup(ref, rt, prec, 1, W, H)
-            _run_mixed(ref, 4)
+            run_mixed(ref, 4)
             want_fb = ref.read_framebuffer()
             want_counts, want_err = ref.adaptive_state()
         with rt.Renderer(0, prec) as r:
             _setup(r, rt, prec, 1, W, H)
-            _run_mixed(r, 3)
+            run_mixed(r, 3)
             fb = r.read_framebuffer()
             c0, e0 = r.adaptive_state()
             lin = r.read_linear()
             d0 = r.denoise()
             v0 = r.variance()
             dv = r.denoise_variance()
-            assert _same_bits(r.read_denoised(), dv), prec               # the last call's image
-            assert not _same_bits(dv, d0), prec
+            assert same_bits(r.read_denoised(), dv), prec               # the last call's image
+            assert not same_bits(dv, d0), prec
             assert r.denoise_variance(3, 2.0, 0.2, 0.3, 0.4, sync=False) is None
             r.synchronize()
-            assert _same_bits(r.read_denoised(), r.denoise_variance(3, 2.0, 0.2, 0.3, 0.4)), prec
+            assert same_bits(r.read_denoised(), r.denoise_variance(3, 2.0, 0.2, 0.3, 0.4)), prec
             ptr, nbytes = r.denoised_device_ptr()
             assert ptr and nbytes == W * H * 3 * (prec // 8)
-            assert _same_bits(r.denoise(), d0), prec                       # denoise() before and after
-            assert _same_bits(r.read_denoised(), d0), prec
-            assert _same_bits(r.variance(), v0) and _same_bits(r.read_linear(), lin), prec
+            assert same_bits(r.denoise(), d0), prec                       # denoise() before and after
+            assert same_bits(r.read_denoised(), d0), prec
+            assert same_bits(r.variance(), v0) and same_bits(r.read_linear(), lin), prec
             c1, e1 = r.adaptive_state()
-            assert _same_bits(c1, c0) and _same_bits(e1, e0) and _same_bits(r.read_framebuffer(), fb), prec
-            # the next chunk's bits: the fourth call of _run_mixed, with its threshold (the median error after the first call)
+            assert same_bits(c1, c0) and same_bits(e1, e0) and same_bits(r.read_framebuffer(), fb), prec
+            # the next chunk's bits: the fourth call of run_mixed, with its threshold (the median error after the first call)
             with rt.Renderer(0, prec) as t:
                 _setup(t, rt, prec, 1, W, H)
                 t.accumulate_adaptive(4, 0.0, min_samples=4)
                 thr = float(np.median(t.adaptive_state()[1]))
             r.accumulate_adaptive(4, thr, min_samples=4)
             c2, e2 = r.adaptive_state()
-            assert _same_bits(r.read_framebuffer(), want_fb) and _same_bits(c2, want_counts) and _same_bits(e2, want_err), prec
+            assert same_bits(r.read_framebuffer(), want_fb) and same_bits(c2, want_counts) and same_bits(e2, want_err), prec
 
 
 # ---- 7. states and errors
@@ -367,10 +261,10 @@ def test_it_denoises_at_every_sample_count(rt, capsys):
                 p.accumulate(total - n)
                 n = total
                 lin = r.read_linear()
-                assert _same_bits(lin, p.read_linear()), (scene_id, n)
+                assert same_bits(lin, p.read_linear()), (scene_id, n)
                 mse_noisy = float(np.mean((lin.astype(np.float64) - ref) ** 2))
                 fixed = r.denoise().astype(np.float64) ** 2
-                assert _same_bits(r.read_denoised(), p.denoise()), (scene_id, n)       # the committed filter sees the same accumulation
+                assert same_bits(r.read_denoised(), p.denoise()), (scene_id, n)       # the committed filter sees the same accumulation
                 var = r.denoise_variance().astype(np.float64) ** 2
                 q[scene_id, n] = (float(np.mean((fixed - ref) ** 2)) / mse_noisy, float(np.mean((var - ref) ** 2)) / mse_noisy)
     with capsys.disabled():

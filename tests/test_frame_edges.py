@@ -1,7 +1,7 @@
 """The preview chain and the render at the edges of frame, camera and sample count.
 
-The numpy restatements of tests/test_denoise.py, tests/test_denoise_variance.py and tests/test_history.py are run here on the inputs
-those modules never feed them: frames of one pixel, one column, one row, below and around an 8 x 8 guide tile, a 16 x 16 filter
+The numpy restatements of tests/preview_model.py are run here on the inputs that tests/test_denoise.py, tests/test_denoise_variance.py
+and tests/test_history.py never feed them: frames of one pixel, one column, one row, below and around an 8 x 8 guide tile, a 16 x 16 filter
 workgroup and the sorted schedule's 4096-pixel threshold (section A); cameras inside a sphere, straight above, grazing, far outside the
 grid, facing the sky, and history across moves that put pixels behind the base camera, off its frame, on its edge and onto other
 surfaces (B); accumulations in which nobody, or everybody exactly once, was sampled (C); frames whose hand-out order does not fit
@@ -21,24 +21,22 @@ in-frame rejected / carried; edge overlaps the last two):
     65536 x 2 (vfov 0.004, base the same view, a step of 13 columns along the camera's u axis)   0/16/65649/8/131048
 """
 import ctypes
+import functools
 import math
 
 import numpy as np
 import pytest
 
 from tests.conftest import compact
-from tests.test_denoise import _filter_np, _gamma, _guides_np, _same_bits
-from tests.test_denoise_variance import _check_against_err
-from tests.test_denoise_variance import _filter_np as _variance_filter_np
+from tests.preview_drive import E_BADARG, E_STATE, INF, begin, check_against_err, check_update, move, orbit, run_mixed, state
+from tests.preview_model import as_base, dot, filter_np, gamma, guides_np, reproject, same_bits, update_np, variance_filter_np, vec
 from tests.test_grid_plan import _plan
-from tests.test_history import _as_base, _base_constants, _check_update, _dot, _move, _orbit, _state, _update_np, _v
 
-E_BADARG, E_STATE = -1, -2
-INF = float("inf")
 SIG = (0.5, 0.1, 0.1, 1.0)                                  # denoise: colour, normal, albedo, depth
 VSIG_ON, VSIG_OFF = (4.0, 0.1, 0.2, 0.05), (INF, 0.1, 0.2, 0.05)  # denoise_variance: the colour term on and off
 LOOSE = (0.0, -1.0, INF)                                    # history_update at the ends of its ranges
 B = 8                                                       # bounce limit of sections A to C
+_begin = functools.partial(begin, sched=2)                  # every handle here sets RTIOW_SCHED_SORTED before its RNG
 
 # (W, H): smallest; thin; below a guide tile; a guide tile and one over; around a filter workgroup; the LDS halo ends at the frame;
 # either side of the sorted schedule's threshold
@@ -59,7 +57,7 @@ PLACEMENTS = {
     "large_lens": dict(defocus_angle=5),
 }
 MOVES = {
-    "orbit25": dict(lookfrom=_orbit(25)),
+    "orbit25": dict(lookfrom=orbit(25)),
     "tele": dict(vfov=11),
     "zoomout": dict(vfov=40),
     "near": dict(lookfrom=(6.5, 1, 1.5)),
@@ -97,29 +95,13 @@ def _oracle_image(rt, oracle, prec, scene_id, W, H, S, bounces, **look):
     return _ORACLE[key]
 
 
-def _begin(r, rt, prec, scene_id, cam, source=3, sched=2):
-    r.set_camera(cam)
-    r.set_scene(rt.build_scene(scene_id, prec))
-    r.set_scene_source(source)
-    r.set_schedule(sched)
-    r.init_rng(1227)
-
-
-def _run_mixed(r, calls):
-    """tests/test_adaptive.py's pattern: everyone 4 samples, then the frame's median error as the threshold."""
-    r.accumulate_adaptive(4, 0.0, min_samples=4)
-    thr = float(np.median(r.adaptive_state()[1]))
-    for _ in range(calls - 1):
-        r.accumulate_adaptive(4, thr, min_samples=4)
-
-
 def _check_denoise(r, levels_list, where, history=False):
     """denoise() -- or denoise_history() -- against the restatement on what the handle itself reads back."""
     src = r.history()[0] if history else r.read_linear()
     n, a, z = r.guides()
     for levels in levels_list:
         got = (r.denoise_history if history else r.denoise)(levels, *SIG)
-        assert _same_bits(got, _filter_np(src, n, a, z, levels, *SIG)), (where, levels)
+        assert same_bits(got, filter_np(src, n, a, z, levels, *SIG)), (where, levels)
         assert np.isfinite(got).all(), (where, levels)
 
 
@@ -130,17 +112,17 @@ def _check_denoise_variance(r, levels_list, where, sigmas=(VSIG_ON, VSIG_OFF)):
         for levels in levels_list:
             got = r.denoise_variance(levels, *sig)
             assert np.isfinite(got).all(), (where, levels, sig)
-            assert _same_bits(got, _variance_filter_np(lin, V, n, a, z, levels, *sig)), (where, levels, sig)
+            assert same_bits(got, variance_filter_np(lin, V, n, a, z, levels, *sig)), (where, levels, sig)
             if sig[0] == INF:                             # the recurrences coincide
-                assert _same_bits(got, r.denoise(levels, *sig)), (where, levels, "against denoise()")
+                assert same_bits(got, r.denoise(levels, *sig)), (where, levels, "against denoise()")
 
 
 def _check_guides(r, rt, oracle, prec, scene_id, cam, where):
     n, a, z = r.guides()
-    wn, wa, wz, hit = _guides_np(rt, oracle, prec, scene_id, cam, r.local_row_map())
-    assert _same_bits(z, wz), where
-    assert _same_bits(n, wn), where
-    assert _same_bits(a, wa), where
+    wn, wa, wz, hit = guides_np(rt, oracle, prec, scene_id, cam, r.local_row_map())
+    assert same_bits(z, wz), where
+    assert same_bits(n, wn), where
+    assert same_bits(a, wa), where
     return hit
 
 
@@ -159,33 +141,33 @@ def test_render_and_filters_on_edge_frames(rt, oracle, prec, frame):
         for sched, threads in ((rt.SCHED_STATIC, 8), (rt.SCHED_PERSISTENT, 0), (rt.SCHED_SORTED, 0)):
             r.set_schedule(sched)
             r.render(threads)
-            assert _same_bits(r.read_framebuffer(), at(S)), ("render", sched)
+            assert same_bits(r.read_framebuffer(), at(S)), ("render", sched)
         assert r.stats()["phases"] == (2 if W * H >= 4096 else 1)
         # plain chunks, the linear read, the guides, the fixed filter
         for chunk, total in ((2, 2), (3, 5)):
             r.accumulate(chunk)
-            assert _same_bits(r.read_framebuffer(), at(total)), ("accumulate", total)
-        assert _same_bits(_gamma(r.read_linear()), r.read_framebuffer())
+            assert same_bits(r.read_framebuffer(), at(total)), ("accumulate", total)
+        assert same_bits(gamma(r.read_linear()), r.read_framebuffer())
         _check_guides(r, rt, oracle, prec, 3, rt.camera(prec, W, H, S, B), "guides")
         _check_denoise(r, (1, 3, 8), "plain")               # at 8 the step exceeds the frame: only the centre tap is left
         # uniform chunks that keep the second moment
         r.reset_accumulation()
         r.accumulate_with_variance(2); r.accumulate_with_variance(3)
-        assert _same_bits(r.read_framebuffer(), at(5))
-        counts, _ = _check_against_err(r, ("uniform", prec, frame))
+        assert same_bits(r.read_framebuffer(), at(5))
+        counts, _ = check_against_err(r, ("uniform", prec, frame))
         assert (counts == 5).all()
         _check_denoise_variance(r, (1, 3, 5), "uniform")
         # a mix of counts
         r.reset_accumulation()
-        _run_mixed(r, 3)
-        counts, _ = _check_against_err(r, ("mixed", prec, frame))
+        run_mixed(r, 3)
+        counts, _ = check_against_err(r, ("mixed", prec, frame))
         if W * H >= 1024:
             assert len(np.unique(counts)) >= 2
         img = r.read_framebuffer()
         for n in np.unique(counts):
             sel = counts == n
-            assert _same_bits(img[sel], at(int(n))[sel]), ("adaptive", n)
-        assert _same_bits(_gamma(r.read_linear()), img)
+            assert same_bits(img[sel], at(int(n))[sel]), ("adaptive", n)
+        assert same_bits(gamma(r.read_linear()), img)
         _check_denoise(r, (1, 3), "mixed")
         _check_denoise_variance(r, (1, 3, 5), "mixed")
 
@@ -200,20 +182,20 @@ def test_history_on_edge_frames(rt, prec, frame):
     with rt.Renderer(0, prec) as r:
         _begin(r, rt, prec, 3, home)
         r.accumulate(3)
-        cur = _state(r, False)
-        c0, m0, count = _check_update(r, home, cur, None, default, "no base")
+        cur = state(r, False)
+        c0, m0, count = check_update(r, home, cur, None, default, "no base")
         assert count == 0
         _check_denoise(r, (1, 3), "first frame", history=True)
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
+        base = as_base(home, cur, c0, m0)
         carried = 0
         for name, kw in MOVES.items():
             cam = rt.camera_look(prec, W, H, 1, B, **kw)
-            _move(r, cam, 1228)
+            move(r, cam, 1228)
             r.accumulate(2)
-            cur = _state(r, False)
-            _check_update(r, cam, cur, base, LOOSE, (prec, frame, name, LOOSE))
-            carried += _check_update(r, cam, cur, base, default, (prec, frame, name))[2]
+            cur = state(r, False)
+            check_update(r, cam, cur, base, LOOSE, (prec, frame, name, LOOSE))
+            carried += check_update(r, cam, cur, base, default, (prec, frame, name))[2]
             _check_denoise(r, (1, 3), (prec, frame, name), history=True)
         assert carried > 0
 
@@ -231,14 +213,14 @@ def test_render_and_guides_of_a_placement(rt, oracle, prec, name, scene_id, fram
     want = _oracle_image(rt, oracle, prec, scene_id, W, H, S, B, **PLACEMENTS[name])
     assert np.isfinite(want).all()
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cam, rt.SCENE_GRID, rt.SCHED_SORTED)
+        _begin(r, rt, prec, scene_id, cam, source=rt.SCENE_GRID, sched=rt.SCHED_SORTED)
         r.render(0)
-        assert _same_bits(r.read_framebuffer(), want), "sorted, grid"
+        assert same_bits(r.read_framebuffer(), want), "sorted, grid"
         assert r.stats()["phases"] == (2 if W * H >= 4096 else 1)
         _check_guides(r, rt, oracle, prec, scene_id, cam, "grid")
         r.set_scene_source(rt.SCENE_LDS_EXACT); r.set_schedule(rt.SCHED_STATIC)
         r.render(8)
-        assert _same_bits(r.read_framebuffer(), want), "static, exact"
+        assert same_bits(r.read_framebuffer(), want), "static, exact"
         r.set_scene_source(rt.SCENE_SCALAR)
         r.set_camera(cam); r.init_rng(1227)                 # stale guides: rendered again, from the scalar loop
         _check_guides(r, rt, oracle, prec, scene_id, cam, "scalar")
@@ -255,25 +237,25 @@ def test_history_across_large_moves(rt, prec, frame, adaptive):
 
     def sample(r):
         if adaptive:
-            _run_mixed(r, 2)
+            run_mixed(r, 2)
         else:
             r.accumulate(3)
 
     with rt.Renderer(0, prec) as r:
         _begin(r, rt, prec, 3, home)
         sample(r)
-        cur = _state(r, adaptive)
-        c0, m0, _ = _check_update(r, home, cur, None, default, "no base")
+        cur = state(r, adaptive)
+        c0, m0, _ = check_update(r, home, cur, None, default, "no base")
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
+        base = as_base(home, cur, c0, m0)
         counts = {}
         for name, kw in MOVES.items():
             cam = rt.camera_look(prec, W, H, 1, B, **kw)
-            _move(r, cam, 1228)
+            move(r, cam, 1228)
             sample(r)
-            cur = _state(r, adaptive)
-            _check_update(r, cam, cur, base, LOOSE, (prec, frame, adaptive, name, LOOSE))
-            counts[name] = _check_update(r, cam, cur, base, default, (prec, frame, adaptive, name))[2]
+            cur = state(r, adaptive)
+            check_update(r, cam, cur, base, LOOSE, (prec, frame, adaptive, name, LOOSE))
+            counts[name] = check_update(r, cam, cur, base, default, (prec, frame, adaptive, name))[2]
         assert counts["elsewhere"] == 0 and 0 < counts["opposite"] < counts["orbit25"] < counts["near"], counts
 
 
@@ -285,7 +267,7 @@ def test_history_across_large_moves(rt, prec, frame, adaptive):
 def test_nobody_sampled_goes_through_the_chain(rt, prec, frame):
     W, H = frame
     default = (rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS, rt.api.HISTORY_MAX)
-    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(1.5))
+    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(1.5))
     with rt.Renderer(0, prec) as r:
         _begin(r, rt, prec, 3, home)
         _, active = r.accumulate_adaptive(4, 0.0, min_samples=0, max_samples=3)     # 4 more samples would pass max_samples
@@ -295,23 +277,23 @@ def test_nobody_sampled_goes_through_the_chain(rt, prec, frame):
         assert (lin == 0).all() and (r.read_framebuffer() == 0).all() and (r.variance() == 0).all()
         _check_denoise(r, (1, 3), "nobody sampled")
         _check_denoise_variance(r, (1, 3), "nobody sampled", sigmas=(VSIG_ON,))
-        cur = _state(r, True)
-        c0, m0, count = _check_update(r, home, cur, None, default, "nobody sampled, no base")
+        cur = state(r, True)
+        c0, m0, count = check_update(r, home, cur, None, default, "nobody sampled, no base")
         assert count == 0 and (m0 == 0).all() and (c0 == 0).all()
         _check_denoise(r, (1, 3), "nobody sampled", history=True)
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
-        _move(r, moved, 1228)                               # a base whose M is 0 everywhere carries nothing
+        base = as_base(home, cur, c0, m0)
+        move(r, moved, 1228)                               # a base whose M is 0 everywhere carries nothing
         r.accumulate(3)
-        cur = _state(r, False)
+        cur = state(r, False)
         for params in (default, LOOSE):
-            c1, m1, count = _check_update(r, moved, cur, base, params, ("after an empty base", params))
-            assert count == 0 and _same_bits(c1, cur["c"]) and (m1 == 3).all()
+            c1, m1, count = check_update(r, moved, cur, base, params, ("after an empty base", params))
+            assert count == 0 and same_bits(c1, cur["c"]) and (m1 == 3).all()
         r.history_commit()
-        base = _as_base(moved, cur, c1, m1)
-        _move(r, home, 1229)                                # ... and the frame after that carries again
+        base = as_base(moved, cur, c1, m1)
+        move(r, home, 1229)                                # ... and the frame after that carries again
         r.accumulate(2)
-        _, _, count = _check_update(r, home, _state(r, False), base, default, "after a sampled base")
+        _, _, count = check_update(r, home, state(r, False), base, default, "after a sampled base")
         assert count > 0.5 * W * H
 
 
@@ -321,24 +303,24 @@ def test_nobody_sampled_goes_through_the_chain(rt, prec, frame):
 def test_one_sample_each_goes_through_the_chain(rt, oracle, prec, frame):
     W, H = frame
     default = (rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS, rt.api.HISTORY_MAX)
-    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(1.5))
+    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(1.5))
     with rt.Renderer(0, prec) as r:
         _begin(r, rt, prec, 3, home)
         _, active = r.accumulate_adaptive(1, 0.0, min_samples=1, max_samples=1)
         counts, err = r.adaptive_state()
         assert active == W * H and (counts == 1).all() and np.isinf(err).all() and (r.variance() == 0).all()
-        assert _same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, prec, 3, W, H, 1, B))
+        assert same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, prec, 3, W, H, 1, B))
         _check_denoise(r, (1, 3), "one sample")
         _check_denoise_variance(r, (1, 3, 5), "one sample")  # V == 0: i_p = f_k / eps, finite
-        cur = _state(r, True)
-        c0, m0, _ = _check_update(r, home, cur, None, default, "one sample, no base")
+        cur = state(r, True)
+        c0, m0, _ = check_update(r, home, cur, None, default, "one sample, no base")
         assert (m0 == 1).all()
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
-        _move(r, moved, 1228)
+        base = as_base(home, cur, c0, m0)
+        move(r, moved, 1228)
         r.accumulate_adaptive(1, 0.0, min_samples=1, max_samples=1)
-        cur = _state(r, True)
-        _, m1, count = _check_update(r, moved, cur, base, default, "one sample on one sample")
+        cur = state(r, True)
+        _, m1, count = check_update(r, moved, cur, base, default, "one sample on one sample")
         assert count > 0.5 * W * H and float(m1.max()) == 2
         _check_denoise(r, (1, 3), "one sample on one sample", history=True)
 
@@ -349,22 +331,22 @@ def test_one_sample_each_goes_through_the_chain(rt, oracle, prec, frame):
 def test_max_history_at_its_lower_end(rt, prec, frame):
     W, H = frame
     tol, cos = rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS
-    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(1.5))
+    home, moved = rt.camera_look(prec, W, H, 1, B), rt.camera_look(prec, W, H, 1, B, lookfrom=orbit(1.5))
     with rt.Renderer(0, prec) as r:
         _begin(r, rt, prec, 3, home)
         r.accumulate(3)
         # include/rtiow.h: max_history <= 0 is RTIOW_E_BADARG, and the refused call writes no temporal image
         assert r._lib.rtiow_history_update(r._h, tol, cos, 0.0, None, None) == E_BADARG
         assert r._lib.rtiow_read_history(r._h, None, None, W * H) == E_STATE
-        cur = _state(r, False)
-        c0, m0, _ = _check_update(r, home, cur, None, (tol, cos, 0.5), "no base, cap 0.5")      # the cap is on m, not on n
+        cur = state(r, False)
+        c0, m0, _ = check_update(r, home, cur, None, (tol, cos, 0.5), "no base, cap 0.5")      # the cap is on m, not on n
         assert (m0 == 3).all()
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
-        _move(r, moved, 1228)
+        base = as_base(home, cur, c0, m0)
+        move(r, moved, 1228)
         r.accumulate(2)
-        cur = _state(r, False)
-        _, m1, count = _check_update(r, moved, cur, base, (tol, cos, 0.5), "cap 0.5 below every count")
+        cur = state(r, False)
+        _, m1, count = check_update(r, moved, cur, base, (tol, cos, 0.5), "cap 0.5 below every count")
         assert count > 0.5 * W * H and float(m1.max()) == 2.5 and set(np.unique(m1)) == {2.0, 2.5}
 
 
@@ -392,7 +374,7 @@ def test_unfit_frame_renders(rt, oracle, prec, frame, view):
         for sched, threads in ((rt.SCHED_STATIC, 8), (rt.SCHED_PERSISTENT, 0), (rt.SCHED_SORTED, 0)):
             r.set_schedule(sched)
             r.render(threads)
-            assert _same_bits(r.read_framebuffer(), want), sched
+            assert same_bits(r.read_framebuffer(), want), sched
 
 
 @pytest.mark.gpu
@@ -412,7 +394,7 @@ def test_unfit_frame_is_never_ranked(rt, oracle, frame, view):
             st = r.stats()
             assert st["phases"] == 1 and st["order_reused"] == 0 and st["prepass_samples"] == 0 and st["staged_stores"] == 0, st
             assert _no_order(r, rt)
-        assert _same_bits(r.read_framebuffer(), want)
+        assert same_bits(r.read_framebuffer(), want)
 
 
 @pytest.mark.gpu
@@ -424,17 +406,17 @@ def test_unfit_frame_accumulates_and_refuses_adaptive(rt, oracle, frame):
     with rt.Renderer(0, 32, debug=True) as r:
         _begin(r, rt, 32, 3, rt.camera(32, W, H, 2, bounces))
         r.accumulate(1)
-        assert _same_bits(r.read_framebuffer(), at(1))
+        assert same_bits(r.read_framebuffer(), at(1))
         active = ctypes.c_int(-1)
         assert r._lib.rtiow_accumulate_adaptive(r._h, 1, 0, 0.0, 8, None, ctypes.byref(active)) == E_BADARG and active.value == 0
         r.accumulate(1)                                     # the refused call changed nothing: the second chunk, unranked
-        assert r.accumulated_samples == 2 and _same_bits(r.read_framebuffer(), at(2))
+        assert r.accumulated_samples == 2 and same_bits(r.read_framebuffer(), at(2))
         assert _no_order(r, rt)
         r.reset_accumulation()                              # ... refused on an empty accumulation too
         assert r._lib.rtiow_accumulate_adaptive(r._h, 1, 0, 0.0, 8, None, None) == E_BADARG
         assert r._lib.rtiow_read_variance(r._h, None, W * H) == E_STATE
         r.render(0)
-        assert _same_bits(r.read_framebuffer(), at(2))
+        assert same_bits(r.read_framebuffer(), at(2))
 
 
 @pytest.mark.gpu
@@ -444,8 +426,8 @@ def test_unfit_frame_guides_and_filter(rt, oracle):
     with rt.Renderer(0, 32) as r:
         _begin(r, rt, 32, 3, cam)
         r.accumulate(2)
-        assert _same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, 32, 3, W, H, 2, bounces, **NARROW))
-        assert _same_bits(_gamma(r.read_linear()), r.read_framebuffer())
+        assert same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, 32, 3, W, H, 2, bounces, **NARROW))
+        assert same_bits(gamma(r.read_linear()), r.read_framebuffer())
         assert _check_guides(r, rt, oracle, 32, 3, cam, "guides").all()
         _check_denoise(r, (3,), "65536 x 2")
 
@@ -458,14 +440,14 @@ def test_unfit_frame_history(rt):
     with rt.Renderer(0, 32) as r:
         _begin(r, rt, 32, 3, home)
         r.accumulate(2)
-        cur = _state(r, False)
-        c0, m0, _ = _check_update(r, home, cur, None, default, "no base")
+        cur = state(r, False)
+        c0, m0, _ = check_update(r, home, cur, None, default, "no base")
         r.history_commit()
-        base = _as_base(home, cur, c0, m0)
-        _move(r, moved, 1228)
+        base = as_base(home, cur, c0, m0)
+        move(r, moved, 1228)
         r.accumulate(1)
-        cur = _state(r, False)
-        _, _, count = _check_update(r, moved, cur, base, default, "a step sideways")
+        cur = state(r, False)
+        _, _, count = check_update(r, moved, cur, base, default, "a step sideways")
         assert count > 0.5 * W * H
         _check_denoise(r, (2,), "65536 x 2", history=True)
 
@@ -491,8 +473,8 @@ def test_tall_frame_fits_in_two_shards(rt, oracle):
             _, active = r.accumulate_adaptive(2, 0.0, min_samples=2)
             assert active == W * 16384 and r.debug_read_order()[0]["kind"] == rt.api.ORDER_ADAPTIVE
             rt.place_rows(adaptive, r.read_framebuffer(), rank, 2, 8)
-    assert _same_bits(plain, want)
-    assert _same_bits(adaptive, want)
+    assert same_bits(plain, want)
+    assert same_bits(adaptive, want)
 
 
 @pytest.mark.gpu
@@ -503,7 +485,7 @@ def test_largest_frames_whose_order_fits(rt, oracle, frame):
     with rt.Renderer(0, 32, debug=True) as r:
         _begin(r, rt, 32, 3, rt.camera(32, W, H, S, bounces))
         r.render(0)
-        assert _same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, 32, 3, W, H, S, bounces))
+        assert same_bits(r.read_framebuffer(), _oracle_image(rt, oracle, 32, 3, W, H, S, bounces))
         st = r.stats()
         assert st["phases"] == 2 and st["staged_stores"] == 1, st
         info, order, slot_of, _ = r.debug_read_order()
@@ -521,38 +503,23 @@ def test_largest_frames_whose_order_fits(rt, oracle, frame):
         listed = order[order >= 0]
         assert info["kind"] == rt.api.ORDER_ACCUMULATE and len(np.unique(listed)) == W * H
         assert int((listed & 0xffff).max()) == W - 1 and int((listed >> 16).max()) == H - 1
-        assert _same_bits(r.read_framebuffer(), want)
+        assert same_bits(r.read_framebuffer(), want)
         r.reset_accumulation()
         _, active = r.accumulate_adaptive(2, 0.0, min_samples=2)
         info, order, _, _ = r.debug_read_order()
         listed = order[order >= 0]
         assert active == W * H and info["kind"] == rt.api.ORDER_ADAPTIVE and len(np.unique(listed)) == W * H
         assert int((listed & 0xffff).max()) == W - 1 and int((listed >> 16).max()) == H - 1
-        assert _same_bits(r.read_framebuffer(), want)
+        assert same_bits(r.read_framebuffer(), want)
 
 
 # ---- E. the cases reach what they are for: the CPU oracle alone (no GPU)
 
-def _reproject(cam, cur, base_cam):
-    """(den, u, v) of section 11 for every pixel of `cam` in the frame of `base_cam`: the first lines of _update_np."""
-    dt = cur["t"].dtype.type
-    Hh, W = cur["t"].shape
-    k = _base_constants(base_cam, dt)
-    O, p00, du, dv = (_v(f, dt) for f in (cam.center, cam.pixel00_loc, cam.pixel_delta_u, cam.pixel_delta_v))
-    fi = np.arange(W).astype(dt)[None, :, None]
-    fj = np.arange(Hh).astype(dt)[:, None, None]
-    with np.errstate(all="ignore"):
-        D = ((p00 + fi * du) + fj * dv) - O
-        d = np.where((cur["t"] > 0)[..., None], (O + cur["t"][..., None] * D) - k["O"], D)
-        den = _dot(d, k["w"])
-        e = (k["f"] / den)[..., None] * d - k["a"]
-        return den, _dot(e, k["du"]) * k["iu"], _dot(e, k["dv"]) * k["iv"]
-
 
 def _oracle_state(rt, oracle, prec, cam, n=2):
-    """A current frame for _update_np from the oracle's guides alone: constant colour, n samples everywhere."""
+    """A current frame for update_np from the oracle's guides alone: constant colour, n samples everywhere."""
     W, H = cam.img_width, cam.img_height
-    normal, _, depth, _ = _guides_np(rt, oracle, prec, 3, cam, np.arange(H))
+    normal, _, depth, _ = guides_np(rt, oracle, prec, 3, cam, np.arange(H))
     return {"c": np.ones((H, W, 3), depth.dtype), "n": np.full((H, W), n, np.int32), "N": normal, "t": depth}
 
 
@@ -561,13 +528,13 @@ def _classes(rt, oracle, prec, W, H, base_look, look, params):
     gathering through its edge, in its frame with every tap rejected, carried.  The edge class overlaps the last two."""
     base_cam, cam = rt.camera_look(prec, W, H, 1, B, **base_look), rt.camera_look(prec, W, H, 1, B, **look)
     b, cur = _oracle_state(rt, oracle, prec, base_cam), _oracle_state(rt, oracle, prec, cam)
-    base = _as_base(base_cam, b, b["c"], b["n"].astype(b["c"].dtype))
-    den, u, v = _reproject(cam, cur, base_cam)
+    base = as_base(base_cam, b, b["c"], b["n"].astype(b["c"].dtype))
+    den, u, v = reproject(cam, cur, base_cam)
     with np.errstate(invalid="ignore"):
         front = den > 0
         window = front & (u > -1) & (u < W) & (v > -1) & (v < H)
         edge = window & ((u < 0) | (u > W - 1) | (v < 0) | (v > H - 1))
-    _, m_out, count = _update_np(cam, cur, base, *params)
+    _, m_out, count = update_np(cam, cur, base, *params)
     carried = m_out > cur["n"]
     assert count == carried.sum() and not (carried & ~window).any()
     got = {"behind": int((~front).sum()), "off": int((front & ~window).sum()), "edge": int(edge.sum()),
@@ -617,17 +584,17 @@ def test_cpu_placements_are_what_they_claim(native, oracle, prec, scene_id):
         hit_share = {}
         for name, kw in PLACEMENTS.items():
             cam = native.camera_look(prec, W, H, 1, B, **kw)
-            normal, _, depth, hit = _guides_np(native, oracle, prec, scene_id, cam, np.arange(H))
+            normal, _, depth, hit = guides_np(native, oracle, prec, scene_id, cam, np.arange(H))
             hit_share[name] = float(hit.mean())
             if name.startswith("inside"):
                 # guide_kernel flips the outward normal iff !(D . outward < 0): here every pixel hits, and every hit is from inside
                 O = np.array(cam.center[:], dt)
                 fi, fj = np.arange(W).astype(dt)[None, :, None], np.arange(H).astype(dt)[:, None, None]
-                D = ((_v(cam.pixel00_loc, dt) + fi * _v(cam.pixel_delta_u, dt)) + fj * _v(cam.pixel_delta_v, dt)) - O
+                D = ((vec(cam.pixel00_loc, dt) + fi * vec(cam.pixel_delta_u, dt)) + fj * vec(cam.pixel_delta_v, dt)) - O
                 P = O + depth[..., None] * D
                 k = np.argmin(np.abs(np.linalg.norm(P[..., None, :].astype(np.float64) - cr[None, None, :, :3], axis=-1) - cr[:, 3]), axis=-1)
                 outward = (P - cr[k, :3]) / cr[k, 3:4]
-                assert hit.all() and (_dot(D, outward) > 0).all() and (_dot(D, normal) < 0).all(), (name, W, H)
+                assert hit.all() and (dot(D, outward) > 0).all() and (dot(D, normal) < 0).all(), (name, W, H)
         assert hit_share["all_sky"] == 0 and hit_share["straight_down"] == 1 and 0 < hit_share["grazing"] < 1 and 0 < hit_share["wide"] < 1, hit_share
     # every primary ray of the far placement starts beyond the grid's Rfar (the far-ray clip), about the library's recentring point
     plan = _plan(native, cr)

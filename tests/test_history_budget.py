@@ -1,28 +1,22 @@
 """History-guided sample budgets on the GPU: rtiow_history_plan computes the history length m every pixel of
 the current camera will carry before the first sample of the frame is traced, and rtiow_accumulate_budget is an adaptive chunk whose rule
-is "sample pixel p while n_p + m_p is below a target".  The plan is section 11's m, so it is checked BIT FOR BIT against the numpy
-restatement of tests/test_history.py; the rule is integer and T arithmetic, so active sets and counts are predicted exactly; and every
+is "sample pixel p while n_p + m_p is below a target".  The plan is section 11's m, so it is checked BIT FOR BIT against
+tests/preview_model.py's plan_np; the rule is integer and T arithmetic, so active sets and counts are predicted exactly; and every
 pixel still holds the bits rtiow_render leaves at its own count."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from tests.test_adaptive import _one_shot
-from tests.test_denoise import _same_bits
-from tests.test_history import (INF, LOOKFROM, _as_base, _begin, _check_update, _move, _moves, _orbit, _sample, _state, _update_np, orbit_reference)
+from tests.preview_drive import (CAP_LOW, CAP_MIX, E_BADARG, E_STATE, INF, SLACK, begin, budget_moves, budget_sampler, check_update,
+                                 commit_base, compare, history_defaults, move, one_shot, orbit_reference, sample, state, uniform_sampler, walk)
+from tests.preview_model import budget_rule, plan_np, same_bits, update_np
 
 pytestmark = pytest.mark.gpu
 
-E_BADARG, E_STATE = -1, -2
 BIG = 2 ** 31 - 1
 BUDGET_MOVES = ("orbit", "dolly", "roll")
-# (base view, current view) of every plan below; tests/test_history_budget_abi.py counts their classes of pixel on the CPU
-BUDGET_PAIRS = (("home", "orbit"), ("home", "dolly"), ("home", "roll"), ("orbit", "home"), ("roll", "home"))
 SIZES = ((9, 9), (67, 41), (203, 117))             # neither of the larger two a multiple of 8 or 16; one tile and a bit
-# The base of these tests is committed after tests/test_history.py's adaptive pattern: every pixel 4 or 8 samples.  Caps: below both
-# counts (every covered pixel at the cap), between them (all three classes in one plan), and the default 16 (every covered pixel below).
-CAP_LOW, CAP_MIX = 2.5, 6.0
 
 
 @pytest.fixture(scope="module")
@@ -30,37 +24,6 @@ def rt(native):
     import torch
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     return native
-
-
-def _budget_moves(rt, prec, W, H, B=10):
-    """The views of this module: the home view and the orbit of tests/test_history.py's _moves, with a dolly and a roll of its own.
-    That module's dolly (4 % towards the scene) and roll (vup tilted mostly along the view axis) leave under 1 % of these frames without
-    history; a dolly 4 % AWAY from the scene brings a border into view and vup tilted across the view axis rolls the frame by about 6
-    degrees, which leave 4 to 10 % (tests/test_history_budget_abi.py counts them on the CPU)."""
-    cams = _moves(rt, prec, W, H, B)
-    cams["dolly"] = rt.camera_look(prec, W, H, 1, B, lookfrom=tuple(1.04 * v for v in LOOKFROM))
-    cams["roll"] = rt.camera_look(prec, W, H, 1, B, vup=(0.0, 1.0, 0.1))
-    return cams
-
-
-def _default(rt):
-    return (rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS, rt.api.HISTORY_MAX)
-
-
-def _commit_base(r, cam, params):
-    """The current accumulation becomes the base (no base before it); returns it as the restatement takes it."""
-    cur = _state(r, True)
-    c0, m0, _ = _check_update(r, cam, cur, None, params, "the base frame")
-    r.history_commit()
-    return _as_base(cam, cur, c0, m0)
-
-
-def _plan_np(r, cam, base, params):
-    """(m, pixels with m > 0) of the restatement: section 11 with c = 0 and n = 0, where Mout is m itself."""
-    normal, _, depth = r.guides()
-    cur = {"c": np.zeros(normal.shape, r.dtype), "n": np.zeros(depth.shape, np.int32), "N": normal, "t": depth}
-    _, m, count = _update_np(cam, cur, base, *params)
-    return m, count
 
 
 def _classes(m, cap):
@@ -71,12 +34,12 @@ def _classes(m, cap):
 def _mixed_plan(r, rt, prec, scene_id, W, H, first="orbit", then="home", source=3, cap=CAP_MIX, B=10):
     """A base after a mix of counts at view `first`, the camera moved to `then`, the plan at `cap` read back and checked to hold all
     three classes of pixel (CAP_LOW: the two it can hold).  Returns (cams, base, params, plane)."""
-    cams = _budget_moves(rt, prec, W, H, B)
-    params = _default(rt)[:2] + (cap,)
-    _begin(r, rt, prec, scene_id, cams[first], source)
-    _sample(r, True)
-    base = _commit_base(r, cams[first], params)
-    _move(r, cams[then])
+    cams = budget_moves(rt, prec, W, H, B)
+    params = history_defaults(rt)[:2] + (cap,)
+    begin(r, rt, prec, scene_id, cams[first], source)
+    sample(r, True)
+    base = commit_base(r, cams[first], params)
+    move(r, cams[then])
     count = r.history_plan(*params)
     m = r.history_plan_lengths()
     assert count == int((m > 0).sum())
@@ -89,19 +52,12 @@ def _mixed_plan(r, rt, prec, scene_id, W, H, first="orbit", then="home", source=
     return cams, base, params, m
 
 
-def _predict(counts, m, samples, target, min_samples, max_samples):
-    """The rule: the sum and the comparison in T."""
-    dt = m.dtype.type
-    have = counts.astype(m.dtype) + m
-    return ((counts < min_samples) | (have < dt(target))) & (counts.astype(np.int64) + samples <= max_samples)
-
-
 def _run_budget(r, m, samples, target, min_samples, max_samples=BIG, limit=40):
     """Budget chunks until none is active, every chunk's active set and counts predicted from the plane and the counts before it."""
     chunks = 0
     while True:
         before = r.adaptive_state()[0]
-        mask = _predict(before, m, samples, target, min_samples, max_samples)
+        mask = budget_rule(before, m, samples, target, min_samples, max_samples)
         _, active = r.accumulate_budget(samples, target, min_samples, max_samples)
         after = r.adaptive_state()[0]
         where = (samples, target, min_samples, max_samples, chunks)
@@ -128,7 +84,7 @@ def _shot(rt, prec, scene_id, W, H, n, B):
     """rtiow_render at samples_per_pixel = n and the home view, rendered once per configuration."""
     key = (prec, scene_id, W, H, int(n), B)
     if key not in _SHOTS:
-        _SHOTS[key] = _one_shot(rt, prec, scene_id, W, H, int(n), B)
+        _SHOTS[key] = one_shot(rt, prec, scene_id, W, H, int(n), B)
     return _SHOTS[key]
 
 
@@ -138,7 +94,7 @@ def _exact_at_own_count(rt, img, counts, prec, scene_id, W, H, B, where):
         if n == 0:
             assert (img[sel] == 0).all(), where                       # never sampled: reads 0
             continue
-        assert _same_bits(img[sel], _shot(rt, prec, scene_id, W, H, n, B)[sel]), (where, int(n))
+        assert same_bits(img[sel], _shot(rt, prec, scene_id, W, H, n, B)[sel]), (where, int(n))
 
 
 # ---- 1. the plan is section 11's m, bit for bit
@@ -148,24 +104,25 @@ def _exact_at_own_count(rt, img, counts, prec, scene_id, W, H, B, where):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_the_plan_is_the_updates_length(rt, prec, scene_id, size):
     W, H = size
-    default = _default(rt)
-    cams = _budget_moves(rt, prec, W, H)
+    default = history_defaults(rt)
+    cams = budget_moves(rt, prec, W, H)
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cams["home"])
-        _sample(r, True)
+        begin(r, rt, prec, scene_id, cams["home"])
+        sample(r, True)
         assert sorted(np.unique(r.adaptive_state()[0])) in ([4, 8], [4], [8])
-        base = _commit_base(r, cams["home"], default)
+        base = commit_base(r, cams["home"], default)
         sweeps = {"orbit": [default, default[:2] + (CAP_LOW,), default[:2] + (CAP_MIX,), (0.0, -1.0, INF)],
                   "dolly": [default, (default[0], -1.0, CAP_LOW), (0.0, -1.0, INF)],
                   "roll": [default, (0.0, default[1], CAP_LOW), default[:2] + (INF,)]}
         for name in BUDGET_MOVES:
-            _move(r, cams[name], 1228)
+            move(r, cams[name], 1228)
             for params in sweeps[name]:
                 count = r.history_plan(*params)
                 m = r.history_plan_lengths()
-                want_m, want_count = _plan_np(r, cams[name], base, params)
+                normal, _, depth = r.guides()
+                want_m, want_count = plan_np(cams[name], normal, depth, base, params)
                 where = (prec, scene_id, size, name, params)
-                assert m.dtype == r.dtype and _same_bits(m, want_m), where
+                assert m.dtype == r.dtype and same_bits(m, want_m), where
                 assert count == want_count == int((m > 0).sum()), where
                 if W * H < 1000 or params[0] == 0.0:
                     continue
@@ -184,7 +141,7 @@ def test_the_plan_is_the_updates_length(rt, prec, scene_id, size):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_no_base_means_an_empty_plan(rt, prec):
     W, H = 67, 41
-    cams = _budget_moves(rt, prec, W, H)
+    cams = budget_moves(rt, prec, W, H)
 
     def empty(r, where):
         assert r.history_plan() == 0, where
@@ -194,22 +151,22 @@ def test_no_base_means_an_empty_plan(rt, prec):
     with rt.Renderer(0, prec) as r:
         r.set_camera(cams["home"]); r.set_scene(rt.build_scene(3, prec))
         empty(r, "no base, no RNG and no chunk")
-        r.init_rng(1227); _sample(r, True)
+        r.init_rng(1227); sample(r, True)
         empty(r, "before any commit")
         r.history_update(); r.history_commit()
-        _move(r, cams["orbit"])
+        move(r, cams["orbit"])
         assert r.history_plan() > 0
         assert r.history_plan(sync=False) is None and r.history_plan_lengths().any()
         r.history_reset()
         empty(r, "after history_reset")
-        _sample(r, True); r.history_update(); r.history_commit()
+        sample(r, True); r.history_update(); r.history_commit()
         r.set_scene(rt.build_scene(3, prec))
         empty(r, "after set_scene")
-        r.init_rng(1227); _sample(r, True); r.history_update(); r.history_commit()
-        _move(r, rt.camera_look(prec, W + 10, H, 1, 10))
+        r.init_rng(1227); sample(r, True); r.history_update(); r.history_commit()
+        move(r, rt.camera_look(prec, W + 10, H, 1, 10))
         empty(r, "a base of another frame size")
-        _sample(r, True); r.history_update(); r.history_commit()
-        _move(r, rt.camera_look(prec, W + 10, H, 1, 10, lookfrom=(13.0, 2.0, 3.0), lookat=(26.0, 4.0, 6.0)))
+        sample(r, True); r.history_update(); r.history_commit()
+        move(r, rt.camera_look(prec, W + 10, H, 1, 10, lookfrom=(13.0, 2.0, 3.0), lookat=(26.0, 4.0, 6.0)))
         empty(r, "a camera facing away")
         # an empty plan is a plan: the target is everybody's
         n, _ = _run_budget(r, r.history_plan_lengths(), 2, 3.0, 0)
@@ -227,11 +184,11 @@ def test_the_plan_agrees_with_the_update(rt, prec, scene_id, size):
         cams, base, params, m = _mixed_plan(r, rt, prec, scene_id, W, H, first="home", then="orbit")
         n, _ = _run_budget(r, m, 2, 8.0, 1)
         assert len(np.unique(n)) >= 3                                 # 2, 4 and 8 samples at least
-        _, want_m, want_count = _check_update(r, cams["orbit"], _state(r, True), base, params, (prec, scene_id, size))
-        assert _same_bits(r.history()[1], m + n.astype(r.dtype))      # Mout = m + (T)n, in T
-        assert _same_bits(want_m, m + n.astype(r.dtype))
+        _, want_m, want_count = check_update(r, cams["orbit"], state(r, True), base, params, (prec, scene_id, size))
+        assert same_bits(r.history()[1], m + n.astype(r.dtype))      # Mout = m + (T)n, in T
+        assert same_bits(want_m, m + n.astype(r.dtype))
         assert want_count == int((m > 0).sum())
-        assert _same_bits(r.history_plan_lengths(), m)                # the update leaves the plan alone
+        assert same_bits(r.history_plan_lengths(), m)                # the update leaves the plan alone
 
 
 # ---- 3. the rule
@@ -268,7 +225,7 @@ def test_the_rule(rt, prec, scene_id, size):
 @pytest.mark.parametrize("scene_id", [1, 3])
 @pytest.mark.parametrize("prec", [32, 64])
 def test_every_pixel_is_exact_at_its_own_count(rt, prec, scene_id):
-    """The camera ends at the home view, where rtiow_render's one-shot images are (tests/test_adaptive.py's _one_shot); a chunk of 2 and a
+    """The camera ends at the home view, where rtiow_render's one-shot images are (tests/preview_drive.py's one_shot); a chunk of 2 and a
     target of 8 over a plan with m in {0} + [4, 6] leave three counts: 8, 4 and 2."""
     W, H, B = 67, 41, 10
     for source, sched in ((0, 0), (1, 1), (2, 2), (3, 2)):
@@ -299,14 +256,14 @@ def test_a_fully_covered_pixel_keeps_its_history(rt, prec, scene_id):
         covered = m > 0
         assert (n[covered] == 0).all() and (n[~covered] == 4).all() and chunks == 3
         assert (r.read_framebuffer()[covered] == 0).all()
-        cur = _state(r, True)
-        c, length, _ = _check_update(r, cams["roll"], cur, base, params, (prec, scene_id))
-        gathered = _update_np(cams["roll"], dict(cur, c=np.zeros_like(cur["c"]), n=np.zeros_like(cur["n"])), base, *params)[0]
+        cur = state(r, True)
+        c, length, _ = check_update(r, cams["roll"], cur, base, params, (prec, scene_id))
+        gathered = update_np(cams["roll"], dict(cur, c=np.zeros_like(cur["c"]), n=np.zeros_like(cur["n"])), base, *params)[0]
         rgb = r.history()[0]
-        assert _same_bits(rgb[covered], gathered[covered])           # Cout = h
+        assert same_bits(rgb[covered], gathered[covered])           # Cout = h
         assert gathered[covered].any()
-        assert _same_bits(rgb[~covered], cur["c"][~covered])         # no history: Cout = c
-        assert _same_bits(length, m + n.astype(r.dtype))
+        assert same_bits(rgb[~covered], cur["c"][~covered])         # no history: Cout = c
+        assert same_bits(length, m + n.astype(r.dtype))
 
 
 # ---- 6. alternating with rtiow_accumulate_adaptive; nothing else moved
@@ -319,7 +276,7 @@ def test_budget_and_adaptive_chunks_alternate(rt, prec):
 
         def budget(samples, target, min_samples):
             before = r.adaptive_state()[0]
-            mask = _predict(before, m, samples, target, min_samples, BIG)
+            mask = budget_rule(before, m, samples, target, min_samples, BIG)
             assert r.accumulate_budget(samples, target, min_samples)[1] == int(mask.sum())
             assert np.array_equal(r.adaptive_state()[0], before + samples * mask.astype(np.int32))
 
@@ -344,20 +301,20 @@ def test_budget_and_adaptive_chunks_alternate(rt, prec):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_a_plan_leaves_everything_else_alone(rt, prec):
     W, H = 67, 41
-    cams = _budget_moves(rt, prec, W, H)
+    cams = budget_moves(rt, prec, W, H)
 
     def run(with_plan):
         out = []
         plan = (lambda *a: r.history_plan(*a)) if with_plan else (lambda *a: None)
         with rt.Renderer(0, prec) as r:
-            _begin(r, rt, prec, 1, cams["home"])
+            begin(r, rt, prec, 1, cams["home"])
             plan()
-            _sample(r, True)
+            sample(r, True)
             r.history_update(); r.history_commit()
-            _move(r, cams["orbit"])
+            move(r, cams["orbit"])
             plan(0.0, -1.0, INF)
             plan()
-            _sample(r, True)
+            sample(r, True)
             plan(0.05, 0.5, 3.0)
             out += [r.read_framebuffer(), r.read_linear()] + list(r.adaptive_state())
             out += [np.array([r.history_update()])] + list(r.history())
@@ -366,7 +323,7 @@ def test_a_plan_leaves_everything_else_alone(rt, prec):
             r.render(0)
             out += [r.read_framebuffer()]
             r.history_commit()
-            _move(r, cams["roll"])
+            move(r, cams["roll"])
             plan()
             r.accumulate(3)
             out += [r.read_framebuffer(), np.array([r.history_update()])] + list(r.history())
@@ -375,7 +332,7 @@ def test_a_plan_leaves_everything_else_alone(rt, prec):
     plain, touched = run(False), run(True)
     assert len(plain) == len(touched)
     for k, (a, b) in enumerate(zip(plain, touched)):
-        assert _same_bits(a, b), (prec, k)
+        assert same_bits(a, b), (prec, k)
 
 
 # ---- 7. states and error codes
@@ -383,7 +340,7 @@ def test_a_plan_leaves_everything_else_alone(rt, prec):
 def test_states_and_error_codes(rt):
     W, H = 96, 64
     npix = W * H
-    cams = _budget_moves(rt, 32, W, H)
+    cams = budget_moves(rt, 32, W, H)
     nul = (None, None)
     with rt.Renderer(0, 32) as r:
         lib = r._lib
@@ -415,19 +372,19 @@ def test_states_and_error_codes(rt):
         before = [r.read_framebuffer()] + list(r.adaptive_state())
         assert budget(0, 1, 8.0, 100) == E_BADARG
         for x, y in zip(before, [r.read_framebuffer()] + list(r.adaptive_state())):
-            assert _same_bits(x, y)
+            assert same_bits(x, y)
         # the plan survives every chunk, an accumulation reset, init_rng and a new guide mode ...
         r.accumulate_adaptive(1, 0.0, min_samples=3)
         r.set_guide_mode(rt.api.GUIDES_SPECULAR)
         kept = r.history_plan_lengths()
         r.reset_accumulation(); r.init_rng(3)
-        assert _same_bits(r.history_plan_lengths(), kept)
+        assert same_bits(r.history_plan_lengths(), kept)
         r.set_guide_mode(rt.api.GUIDES_FIRST_HIT)
         # ... plain chunks shut the budget chunk out until the next reset, and change nothing when it is refused
         r.accumulate(2)
         plain = r.read_framebuffer()
         assert budget() == E_STATE and active.value == 0
-        assert r.accumulated_samples == 2 and _same_bits(r.read_framebuffer(), plain)
+        assert r.accumulated_samples == 2 and same_bits(r.read_framebuffer(), plain)
         r.reset_accumulation()
         assert budget() == 0 and active.value == npix
         # ... and it goes stale exactly when the temporal image does: commit, set_camera, set_scene, set_shard, history_reset
@@ -447,7 +404,7 @@ def test_states_and_error_codes(rt):
                 assert (before == 2).all() and np.array_equal(r.adaptive_state()[0], before)
     with rt.Renderer(0, 32) as r:                        # a sharded handle: no plan, so no budget chunk
         lib = r._lib
-        _begin(r, rt, 32, 3, cams["home"])
+        begin(r, rt, 32, 3, cams["home"])
         r.set_shard(1, 3, 8); r.init_rng(1227)
         assert lib.rtiow_history_plan(r._h, 0.1, 0.9, 8.0, *nul) == E_STATE
         assert lib.rtiow_read_history_plan(r._h, None, W * r.local_rows) == E_STATE
@@ -457,70 +414,16 @@ def test_states_and_error_codes(rt):
 
 # ---- 8. it pays
 
-# scripts/history_budget_probe.py measured, on the walk of tests/test_history.py (8 cameras 0.5 degrees apart, 320 x 180, 50 bounces, fp32)
+# scripts/history_budget_probe.py measured, on tests/preview_drive.py's walk (8 cameras 0.5 degrees apart, 320 x 180, 50 bounces, fp32)
 # at the defaults of raytracingincuda_amd/api.py against that walk with 4 uniform samples a frame, per scene
 # (profiles/history_budget/history_budget_probe.json): primary rays, whole-frame MSE and MSE over the disoccluded set (m = 0 in the last
 # frame's plan) of the temporal image at the last frame, each as budget / uniform.  The budget walk traces fewer rays and brings the
 # disoccluded set's MSE to a quarter; it does NOT lower the whole-frame MSE -- no setting of the sweep that stays within the uniform
 # walk's rays does (DESIGN.md section 4.12 has the table) -- so for the whole frame the test asserts what was measured, not <= 1.  The
-# slack is the 15 % of tests/test_history.py; the comparison is against the uniform walk of the same run.
+# slack is tests/preview_drive.py's 15 %; the comparison is against the uniform walk of the same run.
 R_RAYS = {1: 0.9844, 3: 0.9736}
 R_FRAME = {1: 1.2121, 3: 1.1394}
 R_DISOCCLUDED = {1: 0.2498, 3: 0.2462}
-SLACK = 1.15
-
-
-def walk(rt, scene_id, sample, params=None, frames=8, step_deg=0.5, W=320, H=180, B=50, prec=32):
-    """tests/test_history.py's orbit_walk with the frame's sampling left to `sample(r)`: `frames` cameras, lookfrom turned step_deg about
-    the y axis per frame, independent noise (init_rng(1227 + frame)), the plan, the samples, update and commit every frame.  Returns the
-    primary rays of the whole walk (summed from stats()), the temporal image of the last frame and that frame's plan."""
-    params = params or _default(rt)
-    cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * k)) for k in range(frames)]
-    out = {"rays": 0}
-    with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cams[0])
-        for k, cam in enumerate(cams):
-            _move(r, cam, 1227 + k)
-            r.history_plan(*params)
-            out["rays"] += sample(r)
-            r.history_update(*params)
-            if k == frames - 1:
-                out["temporal"] = r.history()[0].astype(np.float64)
-                out["plan"] = r.history_plan_lengths()
-            else:
-                r.history_commit()
-    return out
-
-
-def uniform_sampler(spp=4):
-    def sample(r):
-        r.accumulate(spp)
-        return r.stats()["primary_rays"]
-    return sample
-
-
-def budget_sampler(chunk, target, min_samples):
-    def sample(r):
-        rays = 0
-        while True:
-            active = r.accumulate_budget(chunk, target, min_samples)[1]
-            rays += r.stats()["primary_rays"]
-            if active == 0:
-                return rays
-    return sample
-
-
-def compare(uniform, budget, ref):
-    """{rays, frame, disoccluded}: budget / uniform of the walk's primary rays, the whole-frame MSE and the MSE over the pixels without
-    history in the last frame's plan (the budget walk's; the uniform walk's is the same set wherever both bases are non-empty)."""
-    gone = budget["plan"] == 0
-    mse = lambda w, sel: float(np.mean((w["temporal"][sel] - ref[sel]) ** 2))
-    everything = np.ones_like(gone)
-    return {"rays": budget["rays"] / uniform["rays"], "frame": mse(budget, everything) / mse(uniform, everything),
-            "disoccluded": mse(budget, gone) / mse(uniform, gone), "disoccluded_pixels": int(gone.sum()),
-            "mse_uniform": mse(uniform, everything), "mse_budget": mse(budget, everything),
-            "mse_uniform_disoccluded": mse(uniform, gone), "mse_budget_disoccluded": mse(budget, gone),
-            "rays_uniform": int(uniform["rays"]), "rays_budget": int(budget["rays"])}
 
 
 def test_it_pays(rt, capsys):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT
+from tests.preview_drive import BUDGET_PAIRS, CAP_LOW, budget_moves
+from tests.preview_model import guides_np, update_np
 
 BUDGET_SYMBOLS = ["rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget"]
 
@@ -91,7 +93,7 @@ def test_budget_kernels_have_no_scratch_and_no_vgpr_spills(metadata):
 def test_the_view_pairs_hold_every_class_of_pixel(native, oracle, scene_id, size):
     """The plan's three classes -- m = 0 (no history: disoccluded, or outside the base's frame), 0 < m < cap, m at the cap -- each hold at
     least 1 % of the frame for every (base view, current view) of tests/test_history_budget.py (BUDGET_PAIRS), from the CPU oracle's
-    first-hit guides alone.  The GPU tests commit the base after tests/test_history.py's adaptive pattern, which leaves every pixel 4 or
+    first-hit guides alone.  The GPU tests commit the base after tests/preview_drive.py's adaptive sample(), which leaves every pixel 4 or
     8 samples, so a gathered length is 0 or lies in [4, 8] whatever the mix; here the base is given 4 everywhere and 8 everywhere in
     turn.  The covered pixels are the same in both, so under CAP_LOW = 2.5 every covered pixel is at the cap and under the default cap
     of 16 every covered pixel is below it; the GPU tests use both caps (and CAP_MIX = 6, between the two counts, where all three classes
@@ -102,16 +104,13 @@ def test_the_view_pairs_hold_every_class_of_pixel(native, oracle, scene_id, size
       scene 1  203 x 117        1372         2006        1149         1300        1130      of 23751
       scene 3  203 x 117         990         1815        1120          900        1124"""
     from raytracingincuda_amd import api
-    from tests.test_denoise import _guides_np
-    from tests.test_history import _update_np
-    from tests.test_history_budget import BUDGET_PAIRS, CAP_LOW, _budget_moves
     W, H = size
     prec, dt = 32, np.float32
-    cams = _budget_moves(native, prec, W, H)
+    cams = budget_moves(native, prec, W, H)
     rows = np.arange(H)
     guides = {}
     for view in {v for pair in BUDGET_PAIRS for v in pair}:
-        normal, _, depth, _ = _guides_np(native, oracle, prec, scene_id, cams[view], rows)
+        normal, _, depth, _ = guides_np(native, oracle, prec, scene_id, cams[view], rows)
         guides[view] = (normal, depth)
     zero = np.zeros((H, W, 3), dt)
     floor = 0.01 * W * H
@@ -121,7 +120,7 @@ def test_the_view_pairs_hold_every_class_of_pixel(native, oracle, scene_id, size
         for count in (4, 8):
             base = {"cam": cams[first], "H": zero, "M": np.full((H, W), count, dt), "N": guides[first][0], "z": guides[first][1]}
             for cap in (CAP_LOW, api.HISTORY_MAX):
-                _, m, carried = _update_np(cams[then], cur, base, api.HISTORY_DEPTH_TOL, api.HISTORY_NORMAL_COS, cap)
+                _, m, carried = update_np(cams[then], cur, base, api.HISTORY_DEPTH_TOL, api.HISTORY_NORMAL_COS, cap)
                 assert carried == int((m > 0).sum())
                 if covered is None:
                     covered = m > 0

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT, compact
+from tests.preview_drive import moves
+from tests.preview_model import as_base, clipped_np, guides_np, update_np
 
 SYMBOL = "rtiow_history_update_clipped"
 
@@ -88,16 +90,13 @@ def test_clip_kernel_has_no_scratch_and_no_vgpr_spills(metadata):
 @pytest.mark.parametrize("scene_id", [1, 3])
 def test_the_orbit_holds_clipped_and_unclipped_history(native, oracle, scene_id):
     """At r = 1, gamma = 0.75 at least 1 % of the 203 x 117 frame is clipped and at least 1 % is carried and not clipped after the move
-    home -> orbit of tests/test_history.py's _moves: 6 samples a frame from the CPU oracle (its images squared back to linear), seeds
+    home -> orbit of tests/preview_drive.py's moves: 6 samples a frame from the CPU oracle (its images squared back to linear), seeds
     1227 and 1228, its first-hit guides, the default tolerances."""
     from raytracingincuda_amd import api
-    from tests.test_denoise import _guides_np
-    from tests.test_history import _as_base, _moves, _update_np
-    from tests.test_history_clip import _clipped_np
     W, H, S = 203, 117, 6
     prec, dt = 32, np.float32
     params = (api.HISTORY_DEPTH_TOL, api.HISTORY_NORMAL_COS, api.HISTORY_MAX)
-    cams = _moves(native, prec, W, H)
+    cams = moves(native, prec, W, H)
     scene = compact(native.build_scene(scene_id, prec))
     state = {}
     for view, seed in (("home", 1227), ("orbit", 1228)):
@@ -105,11 +104,11 @@ def test_the_orbit_holds_clipped_and_unclipped_history(native, oracle, scene_id)
         cam.samples_per_pixel = S
         cam.pixel_samples_scale = dt(1) / dt(S)
         img, _ = oracle.render(prec, scene, cam, seed)
-        normal, _, depth, _ = _guides_np(native, oracle, prec, scene_id, cam, np.arange(H))
+        normal, _, depth, _ = guides_np(native, oracle, prec, scene_id, cam, np.arange(H))
         state[view] = {"c": (img.astype(dt) * img.astype(dt)).reshape(H, W, 3), "n": np.full((H, W), S, np.int32), "N": normal, "t": depth}
-    c0, m0, _ = _update_np(cams["home"], state["home"], None, *params)
-    base = _as_base(cams["home"], state["home"], c0, m0)
-    want = _clipped_np(cams["orbit"], state["orbit"], base, params, 1, 0.75)
+    c0, m0, _ = update_np(cams["home"], state["home"], None, *params)
+    base = as_base(cams["home"], state["home"], c0, m0)
+    want = clipped_np(cams["orbit"], state["orbit"], base, params, 1, 0.75)
     kept = int(((want["m"] > 0) & ~want["mask"]).sum())
     print("scene %d: clipped %d, carried and not clipped %d of %d" % (scene_id, want["clipped"], kept, W * H))
     assert want["clipped"] + kept == want["reprojected"]

@@ -1,15 +1,14 @@
 """Recurrent history on the GPU: rtiow_history_commit_filtered replaces the colour of the temporal image by
 one level of the a-trous filter at step 1 -- over the pixels that hold samples, steered by the filter guides, blended by `feedback` --
 before it becomes the base, and rtiow_read_history_base reads the base back.  Every value is defined operation by operation in T with
-plain * + - /, so the base is checked BIT FOR BIT against the numpy restatement below."""
+plain * + - /, so the base is checked BIT FOR BIT against tests/preview_model.py's feedback_np."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from tests.test_denoise import K, _same_bits
-from tests.test_history import E_BADARG, E_STATE, INF, _as_base, _begin, _move, _moves, _sample, _state, _update_np
-from tests.test_history_clip import _clipped_np
+from tests.preview_drive import E_BADARG, E_STATE, INF, begin, filter_state, guide_sigmas, history_defaults, move, moves, sample, state
+from tests.preview_model import as_base, clipped_np, feedback_np, same_bits, update_np
 
 pytestmark = pytest.mark.gpu
 
@@ -24,63 +23,17 @@ def rt(native):
     return native
 
 
-def _default(rt):
-    return (rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS, rt.api.HISTORY_MAX)
-
-
-def _guide_sigmas(rt):
-    return (rt.api.DENOISE_SIGMA_NORMAL, rt.api.DENOISE_SIGMA_ALBEDO, rt.api.DENOISE_SIGMA_DEPTH)
-
-
-# ---- the numpy restatement of section 16
-
-def _feedback_np(C, M, N, A, Z, sigmas, feedback):
-    """(H', M').  C [H, W, 3], M [H, W]: the temporal image; N, A, Z: the filter guides; sigmas = (colour, normal, albedo, depth)."""
-    dt = C.dtype.type
-    Hh, W = M.shape
-    ic, i_n, i_a, i_z = (dt(1.0 / (s * s)) for s in sigmas)
-    S = np.zeros_like(C); Wt = np.zeros((Hh, W), C.dtype)
-    pad = lambda a: np.pad(a, ((2, 2), (2, 2)) + ((0, 0),) * (a.ndim - 2))
-    Cp, Np, Ap, Zp = pad(C), pad(N), pad(A), pad(Z)
-    ok_p = np.pad(M > 0, 2)                                  # outside the frame: does not count; NaN > 0 is false
-    with np.errstate(all="ignore"):
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                win = lambda a: a[2 + dy:2 + dy + Hh, 2 + dx:2 + dx + W]
-                cq, nq, aq, zq, ok = win(Cp), win(Np), win(Ap), win(Zp), win(ok_p)
-                kern = dt(K[dx + 2]) * dt(K[dy + 2])
-                d = cq - C; dn = nq - N; da = aq - A; dz = zq - Z
-                ec = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-                en = (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2]
-                ea = (da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2]
-                ez = dz * dz
-                e = ((ec * ic + en * i_n) + ea * i_a) + ez * i_z
-                w = kern / (dt(1) + e)
-                S = np.where(ok[..., None], S + w[..., None] * cq, S)
-                Wt = np.where(ok, Wt + w, Wt)
-        F = S / Wt[..., None]
-        out = F if feedback == 1 else C + dt(feedback) * (F - C)
-    out = np.where((M > 0)[..., None], out, C).astype(C.dtype)
-    assert out.dtype == S.dtype == Wt.dtype == C.dtype
-    return out, M.copy()
-
-
-def _filter_state(r):
-    n, a, z, _ = r.filter_guides()
-    return n, a, z
-
-
 def _commit_and_check(r, rt, pair, where):
     """Commit the temporal image the handle holds through the filter at `pair` and compare the base with the restatement; returns it."""
     C, M = r.history()
-    N, A, Z = _filter_state(r)
-    sig = (pair[0],) + _guide_sigmas(rt)
+    N, A, Z = filter_state(r)
+    sig = (pair[0],) + guide_sigmas(rt)
     ms = r.history_commit_filtered(sig[0], *sig[1:], feedback=pair[1])
     assert ms > 0, where
     rgb, length = r.history_base()
-    want, want_m = _feedback_np(C, M, N, A, Z, sig, pair[1])
-    assert _same_bits(length, want_m) and _same_bits(length, M), where
-    assert _same_bits(rgb, want), (where, int((rgb != want).any(axis=-1).sum()))
+    want, want_m = feedback_np(C, M, N, A, Z, sig, pair[1])
+    assert same_bits(length, want_m) and same_bits(length, M), where
+    assert same_bits(rgb, want), (where, int((rgb != want).any(axis=-1).sum()))
     return C, M, rgb
 
 
@@ -94,36 +47,36 @@ def _update(r, rt, clipped, params):
 
 def _exact(rt, prec, scene_id, adaptive, specular):
     W, H = 203, 117                                     # not a multiple of 16 in either direction
-    params = _default(rt)
-    cams = _moves(rt, prec, W, H)
+    params = history_defaults(rt)
+    cams = moves(rt, prec, W, H)
     for clipped in (False, True):
         for pair in PAIRS:
             where = (prec, scene_id, adaptive, specular, clipped, pair)
             with rt.Renderer(0, prec) as r:
                 if specular:
                     r.set_guide_mode(rt.GUIDES_SPECULAR, 8, INF)
-                _begin(r, rt, prec, scene_id, cams["home"])
-                _sample(r, adaptive)
-                home = _state(r, adaptive)
+                begin(r, rt, prec, scene_id, cams["home"])
+                sample(r, adaptive)
+                home = state(r, adaptive)
                 _update(r, rt, clipped, params)
                 C0, M0, H0 = _commit_and_check(r, rt, pair, where + ("home",))      # the first commit of the handle: it allocates the base
-                assert _same_bits(C0, home["c"])
-                base = _as_base(cams["home"], home, H0, M0)
-                _move(r, cams["orbit"], 1228)
-                _sample(r, adaptive)
-                cur = _state(r, adaptive)
+                assert same_bits(C0, home["c"])
+                base = as_base(cams["home"], home, H0, M0)
+                move(r, cams["orbit"], 1228)
+                sample(r, adaptive)
+                cur = state(r, adaptive)
                 count = _update(r, rt, clipped, params)
                 assert count > 0.5 * W * H, where
                 # the update gathers from the filtered base by the first-hit guides the commit kept, whatever the guide mode
-                want = _clipped_np(cams["orbit"], cur, base, params, *CLIP) if clipped else None
-                want_c, want_m = (want["C"], want["M"]) if clipped else _update_np(cams["orbit"], cur, base, *params)[:2]
+                want = clipped_np(cams["orbit"], cur, base, params, *CLIP) if clipped else None
+                want_c, want_m = (want["C"], want["M"]) if clipped else update_np(cams["orbit"], cur, base, *params)[:2]
                 C, M = r.history()
-                assert _same_bits(M, want_m) and _same_bits(C, want_c), where
+                assert same_bits(M, want_m) and same_bits(C, want_c), where
                 if specular:
-                    fn, fa, fz = _filter_state(r)
-                    assert not _same_bits(fn, cur["N"]) and not _same_bits(fz, cur["t"]), where
+                    fn, fa, fz = filter_state(r)
+                    assert not same_bits(fn, cur["N"]) and not same_bits(fz, cur["t"]), where
                 _, _, H1 = _commit_and_check(r, rt, pair, where + ("orbit",))
-                assert not _same_bits(H1, C), where                                  # the filter did something
+                assert not same_bits(H1, C), where                                  # the filter did something
 
 
 @pytest.mark.parametrize("adaptive", [False, True])
@@ -145,13 +98,13 @@ def test_feedback_one_is_a_level_of_denoise_history(rt, prec):
     """Every pixel is sampled, so every tap inside the frame counts, and feedback = 1 stores the filtered colour itself: its gamma has
     the bits of denoise_history(levels=1) at the same sigmas, taken just before the commit."""
     W, H = 150, 90
-    cams = _moves(rt, prec, W, H)
+    cams = moves(rt, prec, W, H)
     sig = (0.5, 0.1, 0.1, 1.0)
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, 3, cams["home"])
+        begin(r, rt, prec, 3, cams["home"])
         r.accumulate(4)
         r.history_update(); r.history_commit()
-        _move(r, cams["orbit"], 7)
+        move(r, cams["orbit"], 7)
         r.accumulate(4)
         assert r.history_update() > 0
         assert (r.history()[1] > 0).all()
@@ -160,8 +113,8 @@ def test_feedback_one_is_a_level_of_denoise_history(rt, prec):
         rgb, _ = r.history_base()
         gamma = np.zeros_like(rgb)
         gamma[rgb > 0] = np.sqrt(rgb[rgb > 0])
-        assert _same_bits(gamma, shown), prec
-        assert _same_bits(r.read_denoised(), shown)      # the commit left the denoised buffer alone
+        assert same_bits(gamma, shown), prec
+        assert same_bits(r.read_denoised(), shown)      # the commit left the denoised buffer alone
 
 
 # ---- 3. tile and frame edges
@@ -171,14 +124,14 @@ def test_feedback_one_is_a_level_of_denoise_history(rt, prec):
 def test_tiles_at_tile_and_frame_edges(rt, prec, frame):
     """The same camera twice with independent noise: the halo exceeds the frame, crosses workgroup borders and is cut by the frame's edge."""
     W, H = frame
-    params = _default(rt)
+    params = history_defaults(rt)
     cam = rt.camera_look(prec, W, H, 1, 10)
     for pair in PAIRS:
         with rt.Renderer(0, prec) as r:
-            _begin(r, rt, prec, 3, cam)
+            begin(r, rt, prec, 3, cam)
             r.accumulate(3)
             r.history_update(*params); r.history_commit()
-            _move(r, cam, 1228)
+            move(r, cam, 1228)
             r.accumulate(3)
             assert r.history_update(*params) == W * H
             _commit_and_check(r, rt, pair, (prec, frame, pair))
@@ -190,13 +143,13 @@ def test_tiles_at_tile_and_frame_edges(rt, prec, frame):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_unsampled_pixels_do_not_count(rt, prec, scene_id):
     W, H = 203, 117
-    cams = _moves(rt, prec, W, H)
-    params = _default(rt)
+    cams = moves(rt, prec, W, H)
+    params = history_defaults(rt)
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cams["home"])
+        begin(r, rt, prec, scene_id, cams["home"])
         r.accumulate(3)
         r.history_update(*params); r.history_commit()
-        _move(r, cams["orbit"], 1228)
+        move(r, cams["orbit"], 1228)
         _, active = r.accumulate_adaptive(4, 0.0, min_samples=0, max_samples=3)     # 4 more samples would pass max_samples
         assert active == 0 and (r.adaptive_state()[0] == 0).all()
         r.history_update(*params)
@@ -222,31 +175,31 @@ def test_unsampled_pixels_do_not_count(rt, prec, scene_id):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_a_chain_of_filtered_commits_is_exact(rt, prec, adaptive):
     W, H = 203, 117
-    cams = _moves(rt, prec, W, H)
+    cams = moves(rt, prec, W, H)
     params = (rt.api.HISTORY_DEPTH_TOL, rt.api.HISTORY_NORMAL_COS, 12.0)
-    sig = (0.3,) + _guide_sigmas(rt)
+    sig = (0.3,) + guide_sigmas(rt)
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, 3, cams["home"])
+        begin(r, rt, prec, 3, cams["home"])
         base = None
         for k, name in enumerate(("home", "orbit", "dolly")):
             where = (prec, adaptive, name)
             if k:
-                _move(r, cams[name], 1227 + k)
+                move(r, cams[name], 1227 + k)
             assert (r.history_plan(*params) > 0) == (k > 0)
             plan = r.history_plan_lengths()
-            _sample(r, adaptive)
-            cur = _state(r, adaptive)
+            sample(r, adaptive)
+            cur = state(r, adaptive)
             count = r.history_update(*params)
             C, M = r.history()
-            want_c, want_m, want_count = _update_np(cams[name], cur, base, *params)      # base: the restatement's own output
-            assert _same_bits(M, want_m) and _same_bits(C, want_c) and count == want_count, where
-            assert _same_bits(M, plan + cur["n"].astype(r.dtype)), where
-            N, A, Z = _filter_state(r)
+            want_c, want_m, want_count = update_np(cams[name], cur, base, *params)      # base: the restatement's own output
+            assert same_bits(M, want_m) and same_bits(C, want_c) and count == want_count, where
+            assert same_bits(M, plan + cur["n"].astype(r.dtype)), where
+            N, A, Z = filter_state(r)
             r.history_commit_filtered(*sig, feedback=0.5)
             rgb, length = r.history_base()
-            Hn, Mn = _feedback_np(want_c, want_m, N, A, Z, sig, 0.5)
-            assert _same_bits(rgb, Hn) and _same_bits(length, Mn) and _same_bits(length, M), where
-            base = _as_base(cams[name], cur, Hn, Mn)
+            Hn, Mn = feedback_np(want_c, want_m, N, A, Z, sig, 0.5)
+            assert same_bits(rgb, Hn) and same_bits(length, Mn) and same_bits(length, M), where
+            base = as_base(cams[name], cur, Hn, Mn)
         assert float(base["M"].max()) > float(cur["n"].max())
 
 
@@ -255,22 +208,22 @@ def test_a_chain_of_filtered_commits_is_exact(rt, prec, adaptive):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_plain_commit_is_unchanged(rt, prec):
     W, H = 150, 90
-    cams = _moves(rt, prec, W, H)
+    cams = moves(rt, prec, W, H)
     with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, 1, cams["home"])
+        begin(r, rt, prec, 1, cams["home"])
         for k, name in enumerate(("home", "orbit", "dolly")):
             if k:
-                _move(r, cams[name], 1227 + k)
+                move(r, cams[name], 1227 + k)
             r.accumulate(3)
             r.history_update()
             C, M = r.history()
             if k == 1:
                 r.history_commit_filtered()              # a filtered commit between two plain ones: the buffers keep their roles
-                assert not _same_bits(r.history_base()[0], C)
+                assert not same_bits(r.history_base()[0], C)
             else:
                 r.history_commit()
                 rgb, length = r.history_base()
-                assert _same_bits(rgb, C) and _same_bits(length, M), (prec, name)
+                assert same_bits(rgb, C) and same_bits(length, M), (prec, name)
 
 
 # ---- 7. nothing else moved
@@ -279,16 +232,16 @@ def test_plain_commit_is_unchanged(rt, prec):
 @pytest.mark.parametrize("prec", [32, 64])
 def test_filtered_commit_leaves_everything_else_alone(rt, prec, adaptive):
     W, H = 128, 72
-    cams = _moves(rt, prec, W, H)
+    cams = moves(rt, prec, W, H)
 
     def run(with_commit):
         out = []
         with rt.Renderer(0, prec) as r:
-            _begin(r, rt, prec, 1, cams["home"])
-            _sample(r, adaptive)
+            begin(r, rt, prec, 1, cams["home"])
+            sample(r, adaptive)
             r.history_update(); r.history_commit()
-            _move(r, cams["orbit"])
-            _sample(r, adaptive, calls=1)
+            move(r, cams["orbit"])
+            sample(r, adaptive, calls=1)
             r.history_update()
             r.denoise_history(2)
             if with_commit:
@@ -314,7 +267,7 @@ def test_filtered_commit_leaves_everything_else_alone(rt, prec, adaptive):
     plain, touched = run(False), run(True)
     assert len(plain) == len(touched)
     for k, (a, b) in enumerate(zip(plain, touched)):
-        assert _same_bits(a, b), (prec, adaptive, k)
+        assert same_bits(a, b), (prec, adaptive, k)
 
 
 # ---- 8. states and error codes
@@ -322,14 +275,14 @@ def test_filtered_commit_leaves_everything_else_alone(rt, prec, adaptive):
 def test_states_and_error_codes(rt):
     W, H = 96, 64
     npix = W * H
-    cams = _moves(rt, 32, W, H)
+    cams = moves(rt, 32, W, H)
     nan = float("nan")
     good = (0.1, 0.1, 0.2, 0.05, 1.0)
     with rt.Renderer(0, 32) as r:
         lib = r._lib
         commit = lambda *a: lib.rtiow_history_commit_filtered(r._h, *a, None)
         read = lambda n=npix: lib.rtiow_read_history_base(r._h, None, None, n)
-        _begin(r, rt, 32, 3, cams["home"])
+        begin(r, rt, 32, 3, cams["home"])
         assert commit(*good) == E_STATE and read() == E_STATE                            # no temporal image, no base
         r.accumulate(2)
         assert commit(*good) == E_STATE and read() == E_STATE                            # a chunk, but no update
@@ -339,7 +292,7 @@ def test_states_and_error_codes(rt):
         assert read() == 0 and read(npix + 1) == E_BADARG and read(0) == E_BADARG
         assert commit(*good) == E_STATE                                                  # the commit made the temporal image stale
         old = r.history_base()
-        _move(r, cams["orbit"], 1228)
+        move(r, cams["orbit"], 1228)
         assert commit(*good) == E_STATE                                                  # a new camera: nothing to commit
         r.accumulate(2)
         assert commit(*good) == E_STATE
@@ -355,41 +308,41 @@ def test_states_and_error_codes(rt):
         assert lib.rtiow_history_commit_filtered(r._h, *good[:4], nan, ctypes.byref(ms)) == E_BADARG and ms.value == 0.0
         # the refused calls left the temporal image readable and the old base in place ...
         after = r.history()
-        assert _same_bits(before[0], after[0]) and _same_bits(before[1], after[1])
+        assert same_bits(before[0], after[0]) and same_bits(before[1], after[1])
         kept = r.history_base()
-        assert _same_bits(kept[0], old[0]) and _same_bits(kept[1], old[1])
+        assert same_bits(kept[0], old[0]) and same_bits(kept[1], old[1])
         r.history_commit()                                                               # ... and a plain commit gives what it would have
         got = r.history_base()
-        assert _same_bits(got[0], before[0]) and _same_bits(got[1], before[1])
+        assert same_bits(got[0], before[0]) and same_bits(got[1], before[1])
         # the ends of the ranges, asynchronous (kernel_ms == NULL); every sigma off: the kernel of K over the pixels that count
-        _move(r, cams["dolly"], 1229); r.accumulate(2); r.history_update()
+        move(r, cams["dolly"], 1229); r.accumulate(2); r.history_update()
         C, M = r.history()
-        N, A, Z = _filter_state(r)
+        N, A, Z = filter_state(r)
         assert commit(INF, INF, INF, INF, 1e-3) == 0
         r.synchronize()
         rgb, length = r.history_base()
-        want, _ = _feedback_np(C, M, N, A, Z, (INF,) * 4, 1e-3)
-        assert _same_bits(rgb, want) and _same_bits(length, M)
+        want, _ = feedback_np(C, M, N, A, Z, (INF,) * 4, 1e-3)
+        assert same_bits(rgb, want) and same_bits(length, M)
         assert lib.rtiow_read_history(r._h, None, None, npix) == E_STATE                 # stale, as after a plain commit
         assert commit(*good) == E_STATE
         # stale guides are rendered by the call: a new guide mode between update and commit
-        _move(r, cams["roll"], 1230); r.accumulate(2); r.history_update()
+        move(r, cams["roll"], 1230); r.accumulate(2); r.history_update()
         r.set_guide_mode(rt.GUIDES_SPECULAR, 8, INF)
         C, M = r.history()
         assert isinstance(r.history_commit_filtered(), float)
         rgb, _ = r.history_base()
         r.render_guides()
-        N, A, Z = _filter_state(r)
+        N, A, Z = filter_state(r)
         a = rt.api
         sig = (a.HISTORY_FEEDBACK_SIGMA_COLOR, a.DENOISE_SIGMA_NORMAL, a.DENOISE_SIGMA_ALBEDO, a.DENOISE_SIGMA_DEPTH)
-        assert _same_bits(rgb, _feedback_np(C, M, N, A, Z, sig, a.HISTORY_FEEDBACK)[0])
+        assert same_bits(rgb, feedback_np(C, M, N, A, Z, sig, a.HISTORY_FEEDBACK)[0])
         # the base survives set_camera; set_scene, history_reset and set_shard empty it; a base of another frame size keeps its own
         r.set_camera(rt.camera_look(32, W + 10, H, 1, 10))
         assert read() == 0 and read((W + 10) * H) == E_BADARG
         r.history_reset()
         assert read() == E_STATE
     with rt.Renderer(0, 32) as r:                        # a sharded handle: neither call
-        _begin(r, rt, 32, 3, cams["home"])
+        begin(r, rt, 32, 3, cams["home"])
         r.set_shard(1, 3, 8); r.init_rng(1227)
         r.accumulate(2)
         assert r._lib.rtiow_history_commit_filtered(r._h, *good, None) == E_STATE
@@ -398,33 +351,3 @@ def test_states_and_error_codes(rt):
 
 # ---- 9. the walks of scripts/history_feedback_probe.py
 
-def feedback_walk(rt, scene_id, step_deg, clip, commit, frames=8, spp=4, W=320, H=180, B=50, prec=32, each_frame=None):
-    """tests/test_history_clip.py's clip_walk with the commit chosen: commit = None is history_commit(), otherwise the keyword arguments of
-    history_commit_filtered() ({}: its defaults).  clip = None: the plain update.  Returns the linear images of the last frame -- temporal
-    image and denoise_history() of it (squared back to linear) -- and its length plane; each_frame(k, r), if given, is called after every
-    update."""
-    from tests.test_history import _orbit
-    a = rt.api
-    params = (a.HISTORY_DEPTH_TOL, a.HISTORY_NORMAL_COS, a.HISTORY_MAX)
-    cams = [rt.camera_look(prec, W, H, 1, B, lookfrom=_orbit(step_deg * k)) for k in range(frames)]
-    out = {}
-    with rt.Renderer(0, prec) as r:
-        _begin(r, rt, prec, scene_id, cams[0])
-        for k, cam in enumerate(cams):
-            _move(r, cam, 1227 + k)
-            r.accumulate(spp)
-            if clip is None:
-                out["reprojected"] = r.history_update(*params)
-            else:
-                out["reprojected"] = r.history_update_clipped(*clip, *params)[0]
-            if each_frame is not None:
-                each_frame(k, r)
-            if k == frames - 1:
-                rgb, length = r.history()
-                out["temporal"], out["length"] = rgb.astype(np.float64), length.astype(np.float64)
-                out["denoise_history"] = r.denoise_history().astype(np.float64) ** 2
-            elif commit is None:
-                r.history_commit()
-            else:
-                r.history_commit_filtered(**commit)
-    return out

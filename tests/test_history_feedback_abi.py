@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT
+from tests.preview_drive import moves
+from tests.preview_model import as_base, guides_np, update_np
 
 SYMBOLS = ("rtiow_history_commit_filtered", "rtiow_read_history_base")
 
@@ -89,26 +91,24 @@ def test_feedback_kernel_has_no_scratch_and_no_vgpr_spills(metadata):
 
 @pytest.mark.parametrize("scene_id", [1, 3])
 def test_the_unsampled_frame_holds_pixels_with_and_without_history(native, oracle, scene_id):
-    """After the move home -> orbit of tests/test_history.py's _moves, a base of 3 samples everywhere and no sample at the new camera, M
+    """After the move home -> orbit of tests/preview_drive.py's moves, a base of 3 samples everywhere and no sample at the new camera, M
     of the update is the gathered history length alone: 0 in at least 1 % of the 203 x 117 frame (disoccluded, or off the base's frame),
     positive in at least 50 %, and at least one pixel with history has a pixel without inside its 5 x 5 window.  The lengths depend on
     the cameras and the first-hit guides only, so the CPU oracle's guides and the default tolerances decide it."""
     from raytracingincuda_amd import api
-    from tests.test_denoise import _guides_np
-    from tests.test_history import _as_base, _moves, _update_np
     W, H = 203, 117
     prec, dt = 32, np.float32
     params = (api.HISTORY_DEPTH_TOL, api.HISTORY_NORMAL_COS, api.HISTORY_MAX)
-    cams = _moves(native, prec, W, H)
+    cams = moves(native, prec, W, H)
     guides = {}
     for view in ("home", "orbit"):
-        normal, _, depth, _ = _guides_np(native, oracle, prec, scene_id, cams[view], np.arange(H))
+        normal, _, depth, _ = guides_np(native, oracle, prec, scene_id, cams[view], np.arange(H))
         guides[view] = (normal, depth)
     blank = lambda view, count: {"c": np.zeros((H, W, 3), dt), "n": np.full((H, W), count, np.int32), "N": guides[view][0], "t": guides[view][1]}
     home = blank("home", 3)
-    c0, m0, _ = _update_np(cams["home"], home, None, *params)
+    c0, m0, _ = update_np(cams["home"], home, None, *params)
     assert (m0 == 3).all()
-    _, M, carried = _update_np(cams["orbit"], blank("orbit", 0), _as_base(cams["home"], home, c0, m0), *params)
+    _, M, carried = update_np(cams["orbit"], blank("orbit", 0), as_base(cams["home"], home, c0, m0), *params)
     empty, held = M == 0, M > 0
     print("scene %d: M == 0 in %.1f %%, M > 0 in %.1f %% of %d" % (scene_id, 100 * empty.mean(), 100 * held.mean(), W * H))
     assert carried == int(held.sum()) and (empty | held).all()

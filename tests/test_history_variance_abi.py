@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT, compact
+from tests.preview_drive import moves
+from tests.preview_model import as_base, guides_np, noise_classes, temporal_noise_np, update_np, window_np
 
 SYMBOLS = ("rtiow_denoise_history_variance", "rtiow_read_history_variance")
 
@@ -88,20 +90,17 @@ def test_noise_kernel_has_no_scratch_and_no_vgpr_spills(metadata):
 
 @pytest.mark.parametrize("scene_id", [1, 3])
 def test_the_budget_frame_holds_measured_and_spatial_pixels(native, oracle, scene_id):
-    """After the move home -> orbit of tests/test_history.py's _moves and the two budget chunks of tests/test_history_variance.py's
+    """After the move home -> orbit of tests/preview_drive.py's moves and the two budget chunks of tests/test_history_variance.py's
     _budget_mix (one sample where the planned history is short of 6, two more where history and count are short of 3, min_samples = 0) at
     least 1 % of the 203 x 117 frame is measured (n >= 2) and at least 1 % takes the spatial estimate with k >= 2.  The GPU tests commit
     the base after an adaptive pattern that leaves every pixel 4 or 8 samples; here the base is given 4 everywhere and 8 everywhere in turn
     (4: every covered pixel gets one sample; 8: none does).  Images of the CPU oracle (squared back to linear), seeds 1227 and 1228, its
     first-hit guides, the default tolerances."""
     from raytracingincuda_amd import api
-    from tests.test_denoise import _guides_np
-    from tests.test_history import _as_base, _moves, _update_np
-    from tests.test_history_variance import _classes, _temporal_noise_np, _window_np
     W, H = 203, 117
     prec, dt = 32, np.float32
     params = (api.HISTORY_DEPTH_TOL, api.HISTORY_NORMAL_COS, api.HISTORY_MAX)
-    cams = _moves(native, prec, W, H)
+    cams = moves(native, prec, W, H)
     scene = compact(native.build_scene(scene_id, prec))
 
     def linear(view, seed, S):
@@ -113,30 +112,30 @@ def test_the_budget_frame_holds_measured_and_spatial_pixels(native, oracle, scen
 
     guides = {}
     for view in ("home", "orbit"):
-        normal, _, depth, _ = _guides_np(native, oracle, prec, scene_id, cams[view], np.arange(H))
+        normal, _, depth, _ = guides_np(native, oracle, prec, scene_id, cams[view], np.arange(H))
         guides[view] = (normal, depth)
     orbit = {1: linear("orbit", 1228, 1), 3: linear("orbit", 1228, 3)}
     for count in (4, 8):
         home = {"c": linear("home", 1227, count), "n": np.full((H, W), count, np.int32), "N": guides["home"][0], "t": guides["home"][1]}
-        c0, m0, _ = _update_np(cams["home"], home, None, *params)
-        base = _as_base(cams["home"], home, c0, m0)
+        c0, m0, _ = update_np(cams["home"], home, None, *params)
+        base = as_base(cams["home"], home, c0, m0)
         zero = {"c": np.zeros((H, W, 3), dt), "n": np.zeros((H, W), np.int32), "N": guides["orbit"][0], "t": guides["orbit"][1]}
-        _, m, _ = _update_np(cams["orbit"], zero, base, *params)              # the plan: the m of the update before any sample
+        _, m, _ = update_np(cams["orbit"], zero, base, *params)              # the plan: the m of the update before any sample
         n = np.zeros((H, W), np.int32)
         n = np.where(n.astype(dt) + m < dt(6.0), n + 1, n)                    # budget chunk: 1 sample, target 6
         n = np.where(n.astype(dt) + m < dt(3.0), n + 2, n)                    # budget chunk: 2 samples, target 3
         assert set(np.unique(n)) <= {0, 1, 3}
         c = np.where((n == 3)[..., None], orbit[3], np.where((n == 1)[..., None], orbit[1], dt(0))).astype(dt)
         cur = {"c": c, "n": n, "N": guides["orbit"][0], "t": guides["orbit"][1]}
-        C, M, _ = _update_np(cams["orbit"], cur, base, *params)
+        C, M, _ = update_np(cams["orbit"], cur, base, *params)
         for radius in (1, 3):
-            spatial, k = _window_np(C, M, radius)
-            got = _classes(n, k)
+            spatial, k = window_np(C, M, radius)
+            got = noise_classes(n, k)
             print("scene %d, base count %d, r = %d: %s of %d" % (scene_id, count, radius, got, W * H))
             assert got["measured"] >= 0.01 * W * H, got
             assert got["spatial with k >= 2"] >= 0.01 * W * H, got
             # the plane of this frame: finite, not negative, and a real estimate in the spatial class
-            V0 = _temporal_noise_np(C, M, n, np.ones((H, W), dt), radius)
+            V0 = temporal_noise_np(C, M, n, np.ones((H, W), dt), radius)
             assert np.isfinite(V0).all() and (V0 >= 0).all()
             assert ((n < 2) & (spatial > 0)).sum() >= 0.01 * W * H
             assert (V0[n >= 2] <= 1).all() and (V0[n >= 2] > 0).all()        # alpha in (0, 1]

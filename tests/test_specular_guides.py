@@ -1,22 +1,20 @@
 """Filter guides that follow mirrors and glass to the first diffuse surface (rtiow_set_guide_mode,
 rtiow_read_filter_guides, guide_chain_kernel).  The chain is defined operation by operation in T with plain * + - / and sqrt, so all
-four planes are checked BIT FOR BIT against a numpy restatement that calls the CPU oracle's hit_world once per bounce level; the three
-filters are checked against the existing numpy filters fed with the filter guides; the first-hit guides, the history and every output
+four planes are checked BIT FOR BIT against tests/preview_model.py's chain_np, which calls the CPU oracle's hit_world once per bounce
+level; the three filters are checked against the model's filters fed with the filter guides; the first-hit guides, the history and every output
 of the default mode keep their bits."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from tests.conftest import compact
 from tests.lattice import lattice_scene
-from tests.test_denoise import _filter_np, _same_bits, _setup
-from tests.test_denoise_variance import _filter_np as _filter_var_np
+from tests.preview_drive import E_BADARG, E_STATE, INF
+from tests.preview_drive import setup as _setup    # not a bare `setup`: older pytests take that name for a module hook
+from tests.preview_model import LATTICE, chain_np, filter_np, same_bits, variance_filter_np
 
 pytestmark = pytest.mark.gpu
 
-E_BADARG, E_STATE = -1, -2
-INF = float("inf")
 FIRST_HIT, SPECULAR = 0, 1
 SIG = (0.5, 0.1, 0.1, 1.0)
 
@@ -26,93 +24,6 @@ def rt(native):
     import torch
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     return native
-
-
-# ---- numpy restatement of section 12
-
-def _dot(a, b):
-    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-
-
-def chain_np(rt, oracle, prec, scene_id, cam, rows, max_bounces, max_fuzz):
-    """(normal', albedo', depth', bounces, facts) as section 12 defines them: hit_world on the CPU oracle once per bounce level for the
-    chains still alive, the rest in T with plain operations.  facts counts what the tests want to have met."""
-    dt = np.float32 if prec == 32 else np.float64
-    sc = lattice_scene(prec) if scene_id == LATTICE else compact(rt.build_scene(scene_id, prec))
-    cr = np.asarray(sc["center_radius"], dt).reshape(-1, 4)
-    af = np.asarray(sc["albedo_fuzz"], dt).reshape(-1, 4)
-    eta = np.asarray(sc["refraction_index"], dt).reshape(-1)
-    with np.errstate(all="ignore"):
-        inv_eta = dt(1) / eta                               # the shade table's (T)1 / eta
-    ty = np.asarray(sc["type"]).reshape(-1)
-    W, R = cam.img_width, len(rows)
-    C = np.array(cam.center[:], dt)
-    p00, du, dv = (np.array(v[:], dt) for v in (cam.pixel00_loc, cam.pixel_delta_u, cam.pixel_delta_v))
-    fi = np.arange(W).astype(dt)[None, :, None]
-    fj = np.asarray(rows).astype(dt)[:, None, None]
-    ps = (p00 + fi * du) + fj * dv
-    D = (ps - C).reshape(-1, 3).copy()
-    n = len(D)
-    O = np.broadcast_to(C, D.shape).copy()
-    A = np.ones((n, 3), dt); Z = np.zeros(n, dt); b = np.zeros(n, np.int32)
-    normal = np.zeros((n, 3), dt); albedo = np.zeros((n, 3), dt); depth = np.zeros(n, dt)
-    alive = np.ones(n, bool)
-    facts = {"tir": 0, "specular_at_cap": 0, "rough_metal_first_hit": 0, "levels": 0}
-    with np.errstate(all="ignore"):
-        while alive.any():
-            facts["levels"] += 1
-            assert facts["levels"] <= max_bounces + 1
-            idx = np.flatnonzero(alive)
-            t, k = oracle.hit_world(prec, cr, np.concatenate([O[idx], D[idx]], axis=1))
-            miss = k < 0
-            mi = idx[miss]
-            later = mi[b[mi] > 0]
-            albedo[later] = A[later]; depth[later] = Z[later]
-            alive[mi] = False
-            hi, t, k = idx[~miss], t[~miss], k[~miss]
-            Dh = D[hi]
-            P = O[hi] + t[:, None] * Dh
-            inv_r = dt(1) / cr[k, 3]
-            out = (P - cr[k, :3]) * inv_r[:, None]
-            front = _dot(Dh, out) < 0
-            N = np.where(front[:, None], out, -out)
-            glass, metal = ty[k] == 2, ty[k] == 1
-            specular = glass | (metal & (af[k, 3].astype(np.float64) <= max_fuzz))
-            An = np.where(glass[:, None], A[hi], A[hi] * af[k, :3])
-            Zn = Z[hi] + t
-            end = ~specular | (b[hi] == max_bounces)
-            facts["specular_at_cap"] += int((specular & end).sum())
-            facts["rough_metal_first_hit"] += int((metal & ~specular & (b[hi] == 0)).sum())
-            e = hi[end]
-            normal[e] = N[end]; albedo[e] = An[end]; depth[e] = Zn[end]
-            alive[e] = False
-            go = ~end
-            ci, Dc, Nc, g = hi[go], Dh[go], N[go], glass[go]
-            A[ci] = An[go]; Z[ci] = Zn[go]; O[ci] = P[go]; b[ci] += 1
-            # metal
-            c2 = dt(2) * _dot(Dc, Nc)
-            Dm = Dc - c2[:, None] * Nc
-            # dielectric
-            ln = np.sqrt(_dot(Dc, Dc))
-            il = dt(1) / ln
-            u = Dc * il[:, None]
-            m = -_dot(u, Nc)
-            ct = np.where(m < 1, m, dt(1))
-            st = np.sqrt(dt(1) - ct * ct)
-            ri = np.where(front[go], inv_eta[k[go]], eta[k[go]])
-            tir = ri * st > 1
-            facts["tir"] += int((tir & g).sum())
-            c2 = dt(2) * -ct
-            refl = u - c2[:, None] * Nc
-            perp = ri[:, None] * (u + ct[:, None] * Nc)
-            kk = -np.sqrt(np.abs(dt(1) - _dot(perp, perp)))
-            refr = perp + kk[:, None] * Nc
-            r = np.where(tir[:, None], refl, refr)
-            Dg = r * ln[:, None]
-            D[ci] = np.where(g[:, None], Dg, Dm)
-    for a in (normal, albedo, depth, A, Z, O, D):
-        assert a.dtype == dt
-    return normal.reshape(R, W, 3), albedo.reshape(R, W, 3), depth.reshape(R, W), b.reshape(R, W), facts
 
 
 # ---- 1. the definition, bit for bit
@@ -131,7 +42,6 @@ def _reference(rt, oracle, prec, scene_id, W, H, max_bounces, max_fuzz):
     return _references[key]
 
 
-LATTICE = "lattice"       # tests/lattice.py instead of a built-in scene: refraction indices other than 1.5 (below 1 and exactly 1 among them), hollow spheres
 CASES = [(3, 67, 41, 1, INF), (3, 67, 41, 2, INF), (3, 67, 41, 8, INF), (1, 96, 54, 8, INF), (3, 67, 41, 8, 0.25), (LATTICE, 67, 41, 8, INF)]
 
 
@@ -160,9 +70,9 @@ def test_filter_guides_are_the_definition(rt, oracle, prec, case):
             n, a, z, b = r.filter_guides()
         where = (prec, case, source)
         assert b.dtype == np.int32 and np.array_equal(b, wb), (where, int((b != wb).sum()))
-        assert _same_bits(z, wz), (where, int((z != wz).sum()))
-        assert _same_bits(n, wn), (where, int((n != wn).any(-1).sum()))
-        assert _same_bits(a, wa), (where, int((a != wa).any(-1).sum()))
+        assert same_bits(z, wz), (where, int((z != wz).sum()))
+        assert same_bits(n, wn), (where, int((n != wn).any(-1).sum()))
+        assert same_bits(a, wa), (where, int((a != wa).any(-1).sum()))
 
 
 # ---- 2. shards
@@ -182,7 +92,7 @@ def test_shards_hold_their_rows(rt, prec):
         first = r.guides()
     assert 0 < len(rows) < H and (whole[3][rows] >= 1).any()
     for got, want in zip(part, whole):
-        assert _same_bits(got, np.ascontiguousarray(want[rows])), prec
+        assert same_bits(got, np.ascontiguousarray(want[rows])), prec
     assert first[2].shape == (len(rows), W)
 
 
@@ -196,16 +106,16 @@ def test_first_hit_guides_keep_their_bits(rt, prec):
         first = r.guides()
         fn, fa, fz, fb = r.filter_guides()               # FIRST_HIT: the first-hit planes, bounces 0
         for got, want in zip((fn, fa, fz), first):
-            assert _same_bits(got, want), prec
+            assert same_bits(got, want), prec
         assert fb.dtype == np.int32 and not fb.any()
         r.set_guide_mode(SPECULAR, 8, INF)
         for got, want in zip(r.guides(), first):
-            assert _same_bits(got, want), prec
+            assert same_bits(got, want), prec
         sn, sa, sz, sb = r.filter_guides()
-        assert sb.any() and not _same_bits(sz, fz)
+        assert sb.any() and not same_bits(sz, fz)
         # a pixel whose first hit is not specular has the first-hit guides in both sets
         same = sb == 0
-        assert same.any() and _same_bits(sz[same], fz[same]) and _same_bits(sn[same], fn[same]) and _same_bits(sa[same], fa[same])
+        assert same.any() and same_bits(sz[same], fz[same]) and same_bits(sn[same], fn[same]) and same_bits(sa[same], fa[same])
 
 
 # ---- 4. the filters read the filter guides
@@ -224,12 +134,12 @@ def test_the_filters_read_the_filter_guides(rt, prec):
         r.set_guide_mode(SPECULAR, 8, INF)
         n, a, z, b = r.filter_guides()
         got = r.denoise(levels, *SIG)
-        assert _same_bits(got, _filter_np(lin, n, a, z, levels, *SIG)), prec
-        assert not _same_bits(got, first_out)             # fails without the feature
-        assert _same_bits(r.history()[0], rgb)            # the temporal image survived the switch
+        assert same_bits(got, filter_np(lin, n, a, z, levels, *SIG)), prec
+        assert not same_bits(got, first_out)             # fails without the feature
+        assert same_bits(r.history()[0], rgb)            # the temporal image survived the switch
         got = r.denoise_history(levels, *SIG)
-        assert _same_bits(got, _filter_np(rgb, n, a, z, levels, *SIG)), prec
-        assert not _same_bits(got, first_hist)
+        assert same_bits(got, filter_np(rgb, n, a, z, levels, *SIG)), prec
+        assert not same_bits(got, first_hist)
     sv = (4.5,) + SIG[1:]
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 3, W, H, B=10)
@@ -239,8 +149,8 @@ def test_the_filters_read_the_filter_guides(rt, prec):
         r.set_guide_mode(SPECULAR, 8, INF)
         n, a, z, b = r.filter_guides()
         got = r.denoise_variance(levels, *sv)
-        assert _same_bits(got, _filter_var_np(lin, var, n, a, z, levels, *sv)), prec
-        assert not _same_bits(got, first_out)
+        assert same_bits(got, variance_filter_np(lin, var, n, a, z, levels, *sv)), prec
+        assert not same_bits(got, first_out)
 
 
 # ---- 5. the default behaviour is preserved
@@ -283,9 +193,9 @@ def test_the_default_mode_and_the_history_keep_their_bits(rt, prec):
     want = runs["never"]
     assert want["reprojected"] > 0
     for key in ("denoise", "history", "length", "denoise_history", "history2", "length2"):
-        assert _same_bits(runs["and_back"][key], want[key]), (prec, key)
+        assert same_bits(runs["and_back"][key], want[key]), (prec, key)
     for key in ("denoise", "history", "length", "denoise_history", "history2", "length2"):      # history does not depend on the mode
-        assert _same_bits(runs["commit"][key], want[key]), (prec, key)
+        assert same_bits(runs["commit"][key], want[key]), (prec, key)
     assert runs["commit"]["reprojected"] == want["reprojected"] == runs["and_back"]["reprojected"]
 
 
@@ -334,4 +244,4 @@ def test_states_and_error_codes(rt):
         r.set_scene(rt.build_scene(3, 32))
         again = r.filter_guides()
         for got, want in zip(again, kept):
-            assert _same_bits(got, want)
+            assert same_bits(got, want)
