@@ -1,10 +1,11 @@
 // handle.h -- rtiow_handle_s, the device buffers it owns (DeviceBuffer) and the small helpers every host file uses (error text, frame size,
-// shard rows, operand-range checks, make_params)
+// shard rows, operand-range checks, make_params); what of the preview chain is current is preview_state.h's
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "../device/params.h"
 #include "order_key.h"
 #include "launch_plan.h"
+#include "preview_state.h"
 
 // A device allocation owned by the handle or by one call: freed when it goes out of scope.  ensure() grows it to at least `bytes`
 // and never shrinks it; the old allocation is freed before the new one is made, so its contents are lost.
@@ -36,7 +37,7 @@ class DeviceBuffer {
     size_t bytes_ = 0;
 };
 
-enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // rtiow_handle_s::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive / _budget
+static_assert(PREVIEW_E_BADARG == RTIOW_E_BADARG && PREVIEW_E_STATE == RTIOW_E_STATE, "preview_state.h refuses in the C-ABI's codes");
 
 struct rtiow_handle_s {
     int device = 0;
@@ -60,16 +61,16 @@ struct rtiow_handle_s {
     GridParams grid{};                            // offsets are relative to the blob until layout_lds places it in LDS
     int grid_cells_bytes = 0, grid_aos_bytes = 0, grid_direct_bytes = 0, grid_ids_bytes = 0;
     int grid_direct = 0, grid_registered = 0;
-    // camera
-    bool have_camera = false;
+    // what of the preview chain is current: every rule that reads or writes it is in preview_state.h
+    PreviewState preview;
+    // camera (preview.have_camera)
     rtiow_camera_f32 cam32{};
     rtiow_camera_f64 cam64{};
-    // shard
-    int rank = 0, nranks = 1, strip_rows = 8;
+    // shard (preview.nranks)
+    int rank = 0, strip_rows = 8;
     int local_rows = 0;
     // rng
     DeviceBuffer<uint32_t> rng;
-    bool rng_ready = false;
     DeviceBuffer<uint32_t> rng_low_table;         // J^lo * s0 for lo < 2^XW_LOW_BITS (xw_low_table_kernel), per rtiow_init_rng
     DeviceBuffer<uint32_t> jump;
     int jump_count = 0;                           // matrices of `jump` that are filled: enough for the bits of the largest pixel index so far
@@ -89,35 +90,30 @@ struct rtiow_handle_s {
     DeviceBuffer<> staged;                        // SCHED_SORTED: finished pixels in slot order (place_pixels_kernel writes the image)
     DeviceBuffer<unsigned> sort_scratch;
     // SCHED_SORTED: the order a two-phase render left in `order` / `slot_of` is carried to the next renders of the same frame, which then
-    // launch once from sample 0 (order_key.h).  Cleared by whatever changes the cost map (scene, camera, shard: invalidate_frame) or
+    // launch once from sample 0 (order_key.h).  Cleared by whatever changes the cost map (scene, camera, shard) or
     // overwrites the two buffers (counting runs, rtiow_accumulate, rtiow_accumulate_adaptive); launch_render compares the key itself.
     CarriedOrder carried;
     OrderRecord order_rec;                        // what `order` holds now (launch_plan.h: plan_ranking_record, plan_adaptive_record)
     bool order_reuse = true;                      // RTIOW_ORDER_REUSE=0 at rtiow_create: every sorted render ranks again (A/B runs, studies)
-    // progressive rendering (rtiow_accumulate): samples accumulated since the last reset, the per-pixel MidState records of the last chunk
-    // (two buffers, ping-pong: acc_mid[acc_cur] holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)
-    int acc_samples = 0;
+    // progressive rendering (rtiow_accumulate): the per-pixel MidState records of the last chunk (two buffers, ping-pong: acc_mid[acc_cur]
+    // holds them) and the segments each pixel ran in that chunk (the next chunk's ranking)
     int acc_cur = 0;
     DeviceBuffer<> acc_mid[2];
     DeviceBuffer<uint32_t> acc_cost;
-    // adaptive progressive rendering (rtiow_accumulate_adaptive): the mode the first chunk after a reset fixed (ACC_MODE_*), the
-    // per-pixel count and relative error the last adaptive chunk left, and {active pixels, largest count} of that chunk
-    int acc_mode = 0;
+    // adaptive progressive rendering (rtiow_accumulate_adaptive): the per-pixel count and relative error the last adaptive chunk left,
+    // and {active pixels, largest count} of that chunk
     DeviceBuffer<int32_t> adapt_counts;
     DeviceBuffer<float> adapt_err;
     DeviceBuffer<unsigned> adapt_ctr;
     // denoised previews (rtiow_render_guides / rtiow_read_linear / rtiow_denoise), all allocated at first use: the guides ({normal, depth}
-    // and {albedo, 0}, 4 T per pixel each; guides_ok: they belong to the current scene, camera and shard), the linear image, the filter's
-    // two ping-pong colour buffers and its gamma-encoded output (denoised_ok: rtiow_denoise has filled it since the last set_*)
+    // and {albedo, 0}, 4 T per pixel each), the linear image, the filter's two ping-pong colour buffers and its gamma-encoded output
     DeviceBuffer<> guide_nd, guide_alb;
-    bool guides_ok = false;
     DeviceBuffer<> linear;
     DeviceBuffer<> dn_tmp[2];
     DeviceBuffer<> denoised;
-    bool denoised_ok = false;
     // filter guides (rtiow_set_guide_mode): what the three filters steer by.  RTIOW_GUIDES_FIRST_HIT: guide_nd / guide_alb themselves.
     // RTIOW_GUIDES_SPECULAR: the specular chain's {normal', depth'} and {albedo', (T)bounces}, 4 T per pixel each, allocated at first use
-    // and written wherever the first-hit guides are (guides_ok covers both sets).  The knob survives set_scene / _camera / _shard.
+    // and written wherever the first-hit guides are.  The knob survives set_scene / _camera / _shard.
     int guide_mode = RTIOW_GUIDES_FIRST_HIT;
     int guide_max_bounces = 0;
     double guide_max_fuzz = 0;
@@ -127,29 +123,20 @@ struct rtiow_handle_s {
     DeviceBuffer<> variance;
     DeviceBuffer<> dn_var[2];
     // temporal history (rtiow_history_*), allocated at first use.  The base: what rtiow_history_commit kept of an earlier camera --
-    // {H.rgb, M} and {normal', depth'}, 4 T per pixel each, and that camera (hist_base_ok: there is one; it survives rtiow_set_camera,
-    // rtiow_accumulate_reset and rtiow_init_rng, and is emptied by rtiow_history_reset, rtiow_set_scene and rtiow_set_shard).  The
-    // temporal image of the current camera: {C.rgb, M}, 4 T per pixel, and its colour alone as the 3-T plane the filter reads
-    // (hist_ok: rtiow_history_update has written them since the last set_* / reset / commit).  hist_ctr: the reprojected-pixel count.
+    // {H.rgb, M} and {normal', depth'}, 4 T per pixel each, and that camera.  The temporal image of the current camera: {C.rgb, M},
+    // 4 T per pixel, and its colour alone as the 3-T plane the filter reads.  hist_ctr: the reprojected-pixel count and, behind it, the
+    // count of those the clamp changed.
     DeviceBuffer<> hist_base_hm, hist_base_nd;
-    bool hist_base_ok = false;
     rtiow_camera_f32 hist_cam32{};
     rtiow_camera_f64 hist_cam64{};
     DeviceBuffer<> hist_cm, hist_rgb;
-    bool hist_ok = false;
     DeviceBuffer<unsigned> hist_ctr;
     // variance-guided filtering of the temporal image (rtiow_denoise_history_variance), allocated at first use: its level-0 variance
-    // plane V^0, 1 T per pixel, which the filter's ping-pong leaves alone (hist_var_ok: the call has written it for the temporal image
-    // the handle holds -- it goes stale with hist_ok and with every update).  acc_gen counts the chunks and resets of the accumulation;
-    // hist_gen is its value at the update that wrote the temporal image, whose alpha = n / Mout holds only while the two agree.
+    // plane V^0, 1 T per pixel, which the filter's ping-pong leaves alone
     DeviceBuffer<> hist_var;
-    bool hist_var_ok = false;
-    uint64_t acc_gen = 0, hist_gen = 0;
     // history-guided sample budgets (rtiow_history_plan / rtiow_accumulate_budget), allocated at first use: the plan, i.e. the history
-    // length m every pixel of the current camera will carry, 1 T per pixel (plan_ok: rtiow_history_plan has written it since the last
-    // set_* / history reset / commit -- it goes stale with the temporal image), and its count of pixels with m > 0
+    // length m every pixel of the current camera will carry, 1 T per pixel, and its count of pixels with m > 0
     DeviceBuffer<> plan_m;
-    bool plan_ok = false;
     DeviceBuffer<unsigned> plan_ctr;
     int waves_per_simd = 0;
     int num_cus = 256;
@@ -177,6 +164,8 @@ int fail(rtiow_handle_s* h, hipError_t e, const char* file, int line) {
     return (int)e;
 }
 int fail_arg(rtiow_handle_s* h, int code, const char* msg) { if (h) h->err = msg; return code; }
+// A precondition or argument check of preview_state.h: return its refusal, the text left for rtiow_last_error_string.
+#define PREVIEW_TRY(h, check) do { Refusal r_ = (check); if (r_.code) { (h)->err = std::move(r_.text); return r_.code; } } while (0)
 
 #define HIP_TRY(h, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail((h), e_, __FILE__, __LINE__); } while (0)
 
@@ -277,7 +266,7 @@ RenderParams<T> make_params(const rtiow_handle_s* h) {
     p.n = h->n; p.n_padded = h->n_padded;
     p.geom_a = h->geom_a.as<const T>(); p.screen.shade_tbl = h->shade_tbl.as<const T>();
     p.cold.rng = h->rng; p.cold.fb = (T*)h->fb;
-    p.cold.local_rows = h->local_rows; p.cold.rank = h->rank; p.cold.nranks = h->nranks; p.cold.strip_rows = h->strip_rows;
+    p.cold.local_rows = h->local_rows; p.cold.rank = h->rank; p.cold.nranks = h->preview.nranks; p.cold.strip_rows = h->strip_rows;
     p.cold.s_begin = 0; p.s_end = p.cold.S; p.cold.rng_in = h->rng; p.cold.solo_lanes = 1;
     return p;
 }

@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection; launch_history_clip: the same with the neighbourhood clamp; launch_history_plan: its history length alone
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -48,7 +48,7 @@ constexpr bool STAGED_STORES = true;
 // What the plan (launch_plan.h) is made for: the frame and shard of L's parameters, the device, the knobs.
 template <class T>
 LaunchPlan new_plan(const rtiow_handle_s* h, const RenderParams<T>& p, bool counting = false, bool staged_stores = false) {
-    return LaunchPlan{PlanFrame{p.cold.W, h->local_rows, h->rank, h->nranks, h->strip_rows, p.cold.S, p.B, h->precision, h->schedule, h->scene_source,
+    return LaunchPlan{PlanFrame{p.cold.W, h->local_rows, h->rank, h->preview.nranks, h->strip_rows, p.cold.S, p.B, h->precision, h->schedule, h->scene_source,
                                 h->num_cus, h->waves_per_simd, counting, staged_stores}};
 }
 
@@ -362,7 +362,7 @@ int launch_scatter_probe(rtiow_handle_s* h, int form, int n, const T* in_r, cons
 }
 #endif
 
-// One chunk of progressive rendering (rtiow_accumulate): samples [h->acc_samples, h->acc_samples + samples) of every local pixel through
+// One chunk of progressive rendering (rtiow_accumulate): samples [acc_samples, acc_samples + samples) of every local pixel through
 // render_accumulate_kernel, always with the persistent hand-out.  The first chunk after a reset starts from the RNG states of rtiow_init_rng
 // in tile order; under RTIOW_SCHED_SORTED every later chunk ranks the pixels heavy-first by the segments each ran in the previous chunk
 // (same limits as launch_render).  No solo waves, no staged stores: the preview is stored at its pixel.  timed: the start event goes
@@ -375,7 +375,7 @@ int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
     int rc = persistent_setup(h, L, timed, true, [](auto src, auto bounded) { return render_accumulate_kernel<T, src, bounded>; });
     if (rc) return rc;
     if ((rc = size_persistent<T>(h, L, P, plan_tile_slots(p.cold.W, h->local_rows)))) return rc;
-    const int n = h->acc_samples;
+    const int n = h->preview.acc_samples;
     plan_chunk(P, n == 0);
 
     // The state records ping-pong: the chunk reads acc_mid[acc_cur] and writes the other buffer.
@@ -436,7 +436,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
     h->carried.clear();                                  // the active list overwrites h->order: launch_render ranks again
     h->order_rec = OrderRecord{};
     HIP_TRY(h, h->order.ensure((size_t)plan_pools(npix) * POOL * sizeof(int)));    // every pixel may be active
-    const bool first = h->acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
+    const bool first = h->preview.acc_mode != ACC_MODE_ADAPTIVE;  // first chunk after a reset: every pixel at n = 0 from rng_in
     const int in = h->acc_cur, out = first ? 0 : 1 - in;
     if (!first) p.cold.mid_in = h->acc_mid[in];
     p.cold.mid_out = h->acc_mid[out];
@@ -507,15 +507,18 @@ int launch_guides(rtiow_handle_s* h) {
                            h->chain_nd.as<T>(), h->chain_alb.as<T>());
         HIP_TRY(h, hipGetLastError());
     }
-    h->guides_ok = true;
+    on_guides_rendered(h->preview);
     return 0;
 }
+
+// The grid of the kernels that give every 16 x 16 pixels of the local frame a workgroup (the filters, the history, the plan).
+inline dim3 frame_grid(int W, int rows) { return dim3((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16)); }
 
 // The accumulation's current records and counts: plain mode one count for all (counts = nullptr), adaptive mode the per-pixel array.
 inline void accumulation_source(const rtiow_handle_s* h, const unsigned char*& mid, const int32_t*& counts, int& n_uniform) {
     mid = h->acc_mid[h->acc_cur];
-    counts = h->acc_mode == ACC_MODE_ADAPTIVE ? h->adapt_counts : nullptr;
-    n_uniform = h->acc_mode == ACC_MODE_ADAPTIVE ? 0 : h->acc_samples;
+    counts = h->preview.acc_mode == ACC_MODE_ADAPTIVE ? h->adapt_counts : nullptr;
+    n_uniform = h->preview.acc_mode == ACC_MODE_ADAPTIVE ? 0 : h->preview.acc_samples;
 }
 
 // The linear image of the accumulation into h->linear (rtiow_read_linear).  The caller has checked that a chunk has run.
@@ -543,7 +546,7 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool fro
     for (int b = 0; b < 2 && b < levels - 1; ++b) HIP_TRY(h, h->dn_tmp[b].ensure(npix * 3 * sizeof(T)));
     const unsigned char* mid; const int32_t* counts; int n_uniform;
     accumulation_source(h, mid, counts, n_uniform);
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    const dim3 grid = frame_grid(W, rows);
     for (int k = 0; k < levels; ++k) {
         FilterWeights<T> fw;
         fw.ic = (T)(inv2[0] * std::ldexp(1.0, 2 * k));
@@ -556,7 +559,7 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool fro
                            counts, n_uniform, cin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
-    h->denoised_ok = true;
+    on_denoised(h->preview);
     return 0;
 }
 
@@ -594,39 +597,16 @@ HistoryParams<T> history_params(const rtiow_handle_s* h, double depth_tol, doubl
     hp.dv = {c.pixel_delta_v[0], c.pixel_delta_v[1], c.pixel_delta_v[2]};
     hp.depth_tol = (T)depth_tol; hp.normal_cos = (T)normal_cos; hp.max_history = (T)max_history;
     const auto& b = [&]() -> const auto& { if constexpr (sizeof(T) == 4) return h->hist_cam32; else return h->hist_cam64; }();
-    hp.have_base = h->hist_base_ok && b.img_width == W && b.img_height == rows && history_constants<T>(b, hp) ? 1 : 0;
+    hp.have_base = h->preview.hist_base_ok && b.img_width == W && b.img_height == rows && history_constants<T>(b, hp) ? 1 : 0;
     return hp;
 }
 
-// history_reproject_kernel over the current accumulation and the base into h->hist_cm / h->hist_rgb (rtiow_history_update); the count of
-// pixels that carried history goes to h->hist_ctr.  The caller has checked state and arguments and made the guides current.
+// history_reproject_kernel over the current accumulation and the base into h->hist_cm / h->hist_rgb (rtiow_history_update), or --
+// clip_radius > 0 -- history_clip_kernel, the same with the neighbourhood clamp (rtiow_history_update_clipped), which writes the same two
+// images.  h->hist_ctr holds two words: the pixels that carried history and those of them the clamp changed (0 without a clamp).  The caller
+// has checked state and arguments -- clip_radius in 1..CLIP_MAX_RADIUS, which the kernel's LDS tile is sized for -- and made the guides current.
 template <class T>
-int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
-    const int W = img_w(h), rows = h->local_rows;
-    const size_t npix = (size_t)W * rows;
-    HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
-    HIP_TRY(h, h->hist_rgb.ensure(npix * 3 * sizeof(T)));
-    HIP_TRY(h, h->hist_ctr.ensure(sizeof(unsigned)));
-    const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
-    const unsigned char* mid; const int32_t* counts; int n_uniform;
-    accumulation_source(h, mid, counts, n_uniform);
-    HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, sizeof(unsigned), h->stream));
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(history_reproject_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, mid, counts, n_uniform,
-                       h->guide_nd.as<const Vec4<T>>(), h->hist_base_hm.as<const Vec4<T>>(), h->hist_base_nd.as<const Vec4<T>>(),
-                       h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
-    HIP_TRY(h, hipGetLastError());
-    h->hist_ok = true;
-    h->hist_var_ok = false;                              // V^0 was of the image this one replaces
-    h->hist_gen = h->acc_gen;
-    return 0;
-}
-
-// launch_history with the neighbourhood clamp (rtiow_history_update_clipped): history_clip_kernel writes the same two images; h->hist_ctr
-// holds two words, the pixels that carried history and those of them the clamp changed.  The caller has checked clip_radius in
-// 1..CLIP_MAX_RADIUS, which the kernel's LDS tile is sized for.
-template <class T>
-int launch_history_clip(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma) {
+int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history, int clip_radius = 0, double clip_gamma = 0) {
     const int W = img_w(h), rows = h->local_rows;
     const size_t npix = (size_t)W * rows;
     HIP_TRY(h, h->hist_cm.ensure(npix * 4 * sizeof(T)));
@@ -636,14 +616,15 @@ int launch_history_clip(rtiow_handle_s* h, double depth_tol, double normal_cos, 
     const unsigned char* mid; const int32_t* counts; int n_uniform;
     accumulation_source(h, mid, counts, n_uniform);
     HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, 2 * sizeof(unsigned), h->stream));
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(history_clip_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, clip_radius, (T)clip_gamma, mid, counts, n_uniform,
-                       h->guide_nd.as<const Vec4<T>>(), h->hist_base_hm.as<const Vec4<T>>(), h->hist_base_nd.as<const Vec4<T>>(),
-                       h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    const auto guide = h->guide_nd.as<const Vec4<T>>(), base_hm = h->hist_base_hm.as<const Vec4<T>>(), base_nd = h->hist_base_nd.as<const Vec4<T>>();
+    if (clip_radius > 0)
+        hipLaunchKernelGGL(history_clip_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, clip_radius, (T)clip_gamma, mid, counts,
+                           n_uniform, guide, base_hm, base_nd, h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    else
+        hipLaunchKernelGGL(history_reproject_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, mid, counts, n_uniform,
+                           guide, base_hm, base_nd, h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     HIP_TRY(h, hipGetLastError());
-    h->hist_ok = true;
-    h->hist_var_ok = false;                              // V^0 was of the image this one replaces
-    h->hist_gen = h->acc_gen;
+    on_history_updated(h->preview);
     return 0;
 }
 
@@ -659,8 +640,7 @@ int launch_feedback(rtiow_handle_s* h, const double inv2[4], double feedback) {
     HIP_TRY(h, h->hist_base_hm.ensure(npix * 4 * sizeof(T)));
     FilterWeights<T> fw;
     fw.ic = (T)inv2[0]; fw.in = (T)inv2[1]; fw.ia = (T)inv2[2]; fw.iz = (T)inv2[3];
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(feedback_filter_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, fw, feedback == 1.0 ? 0 : 1, (T)feedback,
+    hipLaunchKernelGGL(feedback_filter_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, fw, feedback == 1.0 ? 0 : 1, (T)feedback,
                        h->hist_cm.as<const Vec4<T>>(), filter_nd(h).as<const Vec4<T>>(), filter_alb(h).as<const Vec4<T>>(),
                        h->hist_base_hm.as<Vec4<T>>());
     HIP_TRY(h, hipGetLastError());
@@ -678,11 +658,10 @@ int launch_history_plan(rtiow_handle_s* h, double depth_tol, double normal_cos, 
     HIP_TRY(h, h->plan_ctr.ensure(sizeof(unsigned)));
     const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
     HIP_TRY(h, hipMemsetAsync(h->plan_ctr, 0, sizeof(unsigned), h->stream));
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(history_length_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
+    hipLaunchKernelGGL(history_length_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
                        h->hist_base_hm.as<const T>(), h->hist_base_nd.as<const Vec4<T>>(), h->plan_m.as<T>(), (unsigned*)h->plan_ctr);
     HIP_TRY(h, hipGetLastError());
-    h->plan_ok = true;
+    on_plan_written(h->preview);
     return 0;
 }
 
@@ -705,12 +684,11 @@ template <class T>
 int launch_temporal_noise(rtiow_handle_s* h, int variance_radius) {
     const int W = img_w(h), rows = h->local_rows;
     HIP_TRY(h, h->hist_var.ensure((size_t)W * rows * sizeof(T)));
-    const int32_t* counts = h->acc_mode == ACC_MODE_ADAPTIVE ? (const int32_t*)h->adapt_counts : nullptr;
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(temporal_noise_kernel<T>, grid, dim3(256), 0, h->stream, FrameShape{W, rows}, variance_radius, h->hist_cm.as<const Vec4<T>>(),
+    const int32_t* counts = h->preview.acc_mode == ACC_MODE_ADAPTIVE ? (const int32_t*)h->adapt_counts : nullptr;
+    hipLaunchKernelGGL(temporal_noise_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, variance_radius, h->hist_cm.as<const Vec4<T>>(),
                        (const unsigned char*)h->acc_mid[h->acc_cur], counts, h->hist_var.as<T>());
     HIP_TRY(h, hipGetLastError());
-    h->hist_var_ok = true;
+    on_temporal_variance_written(h->preview);
     return 0;
 }
 
@@ -743,7 +721,7 @@ int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance
     fw.eps = (T)1e-8;
     fw.in = (T)inv2g[0]; fw.ia = (T)inv2g[1]; fw.iz = (T)inv2g[2];
     const unsigned char* mid = h->acc_mid[h->acc_cur];
-    const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
+    const dim3 grid = frame_grid(W, rows);
     // bit k: level k (step 1 << k, k < 3) stages its taps in LDS (variance_tile_kernel)
     const int tile_levels = tuned("RTIOW_TUNE_VARIANCE_TILE", sizeof(T) == 4 ? VARIANCE_TILE_LEVELS_F32 : VARIANCE_TILE_LEVELS_F64);
     for (int k = 0; k < levels; ++k) {
@@ -761,7 +739,7 @@ int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance
                            (const int32_t*)h->adapt_counts, cin, vin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, vout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
-    h->denoised_ok = true;
+    on_denoised(h->preview);
     return 0;
 }
 

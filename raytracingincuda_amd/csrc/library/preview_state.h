@@ -1,0 +1,133 @@
+// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 16): what the handle holds that is current
+// (PreviewState), what every event makes current or stale (on_*: one function per event, each stating everything that event touches),
+// what a call needs (need_*: a predicate that carries its refusal) and the argument checks the calls share (check_*).
+// rtiow_hip.hip and launch.h ask here and write none of these fields themselves; nothing here touches the device.
+// Plain C++ (no HIP): also built on its own by tests/native/preview_state_main.cpp.
+#pragma once
+#include <cstdint>
+#include <string>
+
+constexpr int PREVIEW_E_BADARG = -1, PREVIEW_E_STATE = -2;   // RTIOW_E_BADARG, RTIOW_E_STATE (include/rtiow.h); handle.h asserts them equal
+enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // PreviewState::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive / _budget
+
+struct PreviewState {
+    bool scene = false;                           // rtiow_set_scene has uploaded one (the handle's n != 0); a scene never goes away again
+    bool have_camera = false;
+    int nranks = 1;                               // rtiow_set_shard: the filters and the history refuse nranks > 1
+    bool rng_ready = false;
+    // progressive rendering: the samples rtiow_accumulate has accumulated since the last reset, and the mode the first chunk after a
+    // reset fixed (ACC_MODE_*: rtiow_accumulate or rtiow_accumulate_adaptive)
+    int acc_samples = 0, acc_mode = ACC_MODE_NONE;
+    // denoised previews: guides_ok: the guides belong to the current scene, camera and shard (with RTIOW_GUIDES_SPECULAR it covers the
+    // chain's set too); denoised_ok: rtiow_denoise has filled the denoised image since the last set_*
+    bool guides_ok = false, denoised_ok = false;
+    // temporal history.  hist_base_ok: there is a base, what rtiow_history_commit kept of an earlier camera; it survives rtiow_set_camera,
+    // rtiow_accumulate_reset and rtiow_init_rng, and is emptied by rtiow_history_reset, rtiow_set_scene and rtiow_set_shard.
+    // hist_ok: rtiow_history_update has written the temporal image of the current camera since the last set_* / reset / commit.
+    bool hist_base_ok = false, hist_ok = false;
+    // variance-guided filtering of the temporal image.  hist_var_ok: rtiow_denoise_history_variance has written the plane V^0 for the
+    // temporal image the handle holds -- it goes stale with hist_ok and with every update.  acc_gen counts the chunks and resets of the
+    // accumulation; hist_gen is its value at the update that wrote the temporal image, whose alpha = n / Mout holds only while the two agree.
+    bool hist_var_ok = false;
+    uint64_t acc_gen = 0, hist_gen = 0;
+    // history-guided sample budgets.  plan_ok: rtiow_history_plan has written the plan since the last set_* / history reset / commit --
+    // it goes stale with the temporal image
+    bool plan_ok = false;
+};
+
+// ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
+// Every reset of the accumulation bumps acc_gen, as every chunk does (need_same_accumulation compares it with the update's).
+inline void on_accumulation_reset(PreviewState& s) { s.acc_samples = 0; s.acc_mode = ACC_MODE_NONE; ++s.acc_gen; }
+// A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
+inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.denoised_ok = false; }
+// What a new scene, camera or shard has in common: the accumulation, the guides and the denoised image, the temporal image and the
+// history plan are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is of the old frame too.)
+inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; }
+// rtiow_set_scene, before the upload: also the history base goes, which a new camera keeps.  The RNG states stay.
+inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; }
+inline void on_scene_uploaded(PreviewState& s) { s.scene = true; }
+// rtiow_set_camera: a bad image size takes the camera away and leaves everything else; a good one -- the very camera the handle
+// already has is no exception -- also asks for new RNG states.  The base survives.
+inline void on_set_camera(PreviewState& s, bool good_size) { s.have_camera = good_size; if (good_size) { on_frame_changed(s); s.rng_ready = false; } }
+inline void on_set_shard(PreviewState& s, int nranks) { s.nranks = nranks; on_frame_changed(s); s.rng_ready = false; s.hist_base_ok = false; }
+// rtiow_init_rng resets the accumulation where it starts (on_accumulation_reset) and ends here.
+inline void on_rng_initialised(PreviewState& s) { s.rng_ready = true; }
+// A chunk of either kind, before its launch; then the chunk itself: a plain one counts its samples, the first of a kind fixes the mode.
+inline void on_chunk_begin(PreviewState& s) { ++s.acc_gen; }
+inline void on_plain_chunk(PreviewState& s, int samples) { s.acc_samples += samples; s.acc_mode = ACC_MODE_PLAIN; }
+inline void on_adaptive_chunk(PreviewState& s) { s.acc_mode = ACC_MODE_ADAPTIVE; }
+inline void on_guides_rendered(PreviewState& s) { s.guides_ok = true; }
+inline void on_denoised(PreviewState& s) { s.denoised_ok = true; }
+// rtiow_history_update / _clipped: V^0 was of the image this one replaces.
+inline void on_history_updated(PreviewState& s) { s.hist_ok = true; s.hist_var_ok = false; s.hist_gen = s.acc_gen; }
+inline void on_plan_written(PreviewState& s) { s.plan_ok = true; }
+inline void on_temporal_variance_written(PreviewState& s) { s.hist_var_ok = true; }
+inline void on_history_reset(PreviewState& s) { s.hist_base_ok = false; s.hist_ok = false; s.plan_ok = false; }
+// Both commits: the temporal image and the guides became the base by changing owners, so what they leave behind is stale.
+inline void on_commit(PreviewState& s) { s.hist_base_ok = true; s.hist_ok = false; s.plan_ok = false; s.guides_ok = false; }
+
+// ---- refusals: the code a call returns and the text it leaves in rtiow_last_error_string, `call` first.  code 0: not refused.
+struct Refusal {
+    int code = 0;
+    std::string text;
+};
+inline Refusal refuse_unless(bool ok, int code, const char* call, const std::string& text) { return ok ? Refusal{} : Refusal{code, call + text}; }
+
+// ---- preconditions.  ASKS_SCENE: the call also asks for a scene, under the same text.  A chunk needs one (need_scene) and a scene never
+// goes away, so acc_mode != ACC_MODE_NONE and hist_ok each imply it; the calls differ in whether they ask all the same, and keep to that.
+enum Asks { ASKS_CAMERA, ASKS_SCENE };
+inline bool frame_set(const PreviewState& s, Asks asks) { return s.have_camera && (asks == ASKS_CAMERA || s.scene); }
+inline Refusal need_scene(const PreviewState& s, const char* call) { return refuse_unless(frame_set(s, ASKS_SCENE), PREVIEW_E_STATE, call, " before rtiow_set_scene/rtiow_set_camera"); }
+inline Refusal need_rng(const PreviewState& s, const char* call) { return refuse_unless(s.rng_ready, PREVIEW_E_STATE, call, " before rtiow_init_rng"); }
+// neighbours: the wording of the calls that filter or reproject (the others read or forget what those wrote).
+inline Refusal need_unsharded(const PreviewState& s, const char* call, bool neighbours) {
+    return refuse_unless(s.nranks <= 1, PREVIEW_E_STATE, call, neighbours ? ": not on a sharded handle (the strips of a shard are not image neighbours)" : ": not on a sharded handle");
+}
+inline Refusal need_chunk(const PreviewState& s, const char* call, Asks asks) {
+    return refuse_unless(frame_set(s, asks) && s.acc_mode != ACC_MODE_NONE, PREVIEW_E_STATE, call, ": no chunk since the last reset");
+}
+inline Refusal need_adaptive_chunk(const PreviewState& s, const char* call, Asks asks) {
+    return refuse_unless(frame_set(s, asks) && s.acc_mode == ACC_MODE_ADAPTIVE, PREVIEW_E_STATE, call, ": no adaptive chunk since the last reset (plain chunks keep no second moment)");
+}
+// A chunk of one kind refuses an accumulation of the other (`other`: ACC_MODE_PLAIN or ACC_MODE_ADAPTIVE).
+inline Refusal need_no_chunk_of(const PreviewState& s, const char* call, int other) {
+    return refuse_unless(s.acc_mode != other, PREVIEW_E_STATE, call, std::string(" after ") + (other == ACC_MODE_PLAIN ? "rtiow_accumulate" : "rtiow_accumulate_adaptive") + ": reset the accumulation first");
+}
+inline Refusal need_guides(const PreviewState& s, const char* call) {
+    return refuse_unless(s.have_camera && s.guides_ok, PREVIEW_E_STATE, call, ": no guides for the current scene, camera and shard (rtiow_render_guides)");
+}
+inline Refusal need_denoised(const PreviewState& s, const char* call) { return refuse_unless(s.have_camera && s.denoised_ok, PREVIEW_E_STATE, call, " before rtiow_denoise"); }
+inline Refusal need_temporal_image(const PreviewState& s, const char* call, Asks asks) {
+    return refuse_unless(frame_set(s, asks) && s.hist_ok, PREVIEW_E_STATE, call, ": no temporal image for the current camera (rtiow_history_update)");
+}
+// The accumulation is still the one the update read.
+inline Refusal need_same_accumulation(const PreviewState& s, const char* call) {
+    return refuse_unless(s.hist_gen == s.acc_gen, PREVIEW_E_STATE, call, ": a chunk or a reset since the update that wrote the temporal image (update again)");
+}
+inline Refusal need_temporal_variance(const PreviewState& s, const char* call) {
+    return refuse_unless(s.have_camera && s.hist_ok && s.hist_var_ok, PREVIEW_E_STATE, call, ": no variance plane for the temporal image (rtiow_denoise_history_variance)");
+}
+inline Refusal need_base(const PreviewState& s, const char* call) { return refuse_unless(s.hist_base_ok, PREVIEW_E_STATE, call, ": no history base (rtiow_history_commit)"); }
+inline Refusal need_plan(const PreviewState& s, const char* call) {
+    return refuse_unless(s.have_camera && s.plan_ok, PREVIEW_E_STATE, call, ": no history plan for the current camera (rtiow_history_plan)");
+}
+
+// ---- argument checks
+// The filters: levels in 1..8, then sigma[4] (colour or variance, normal, albedo, depth) each > 0; inv2[k] = 1 / sigma[k]^2.  A call
+// without levels (rtiow_history_commit_filtered) passes 1.
+inline Refusal check_filter(const char* call, int levels, const double (&sigma)[4], double (&inv2)[4]) {
+    if (levels < 1 || levels > 8) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": levels must be 1..8"};
+    for (int k = 0; k < 4; ++k) {
+        if (!(sigma[k] > 0)) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": every sigma must be > 0 (+inf turns its term off)"};
+        inv2[k] = 1.0 / (sigma[k] * sigma[k]);
+    }
+    return Refusal{};
+}
+inline Refusal check_history_tolerances(const char* call, double depth_tol, double normal_cos, double max_history) {
+    return refuse_unless(depth_tol >= 0 && normal_cos >= -1 && normal_cos <= 1 && max_history > 0, PREVIEW_E_BADARG, call,
+                         ": need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
+}
+// clip_radius and variance_radius (`name`) in 1..max_radius, which the kernel's LDS tile is sized for; rest: what else the text asks for.
+inline Refusal check_radius(const char* call, const char* name, int radius, int max_radius, bool rest_ok = true, const char* rest = "") {
+    return refuse_unless(radius >= 1 && radius <= max_radius && rest_ok, PREVIEW_E_BADARG, call, std::string(": need ") + name + " in 1.." + std::to_string(max_radius) + rest);
+}

@@ -45,6 +45,7 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
     HIP_TRY(h, hipMemcpy(h->geom_a, ga.data(), sizeof(T) * 4 * mp, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->shade_tbl, st.data(), sizeof(T) * 12 * m, hipMemcpyHostToDevice));
     h->n = m; h->n_padded = mp;
+    on_scene_uploaded(h->preview);
     h->stats.num_spheres = m;
     h->stats.scene_prepare_ms = 0;
     return 0;

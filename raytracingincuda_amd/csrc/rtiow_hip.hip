@@ -122,32 +122,6 @@ static void release_stream(int device, hipStream_t s) {
     g_idle_streams.emplace_back(device, s);
 }
 
-// Preconditions of the calls that render; `call` names the caller in the message.
-int need_scene(rtiow_handle_s* h, const char* call) {
-    if (h->have_camera && h->n != 0) return 0;
-    return fail_arg(h, RTIOW_E_STATE, (std::string(call) + " before rtiow_set_scene/rtiow_set_camera").c_str());
-}
-int need_rng(rtiow_handle_s* h, const char* call) {
-    if (h->rng_ready) return 0;
-    return fail_arg(h, RTIOW_E_STATE, (std::string(call) + " before rtiow_init_rng").c_str());
-}
-
-// What a change of state invalidates: the accumulation; with a new scene, camera or shard also the guides and the denoised image,
-// the temporal image and the history plan, the carried hand-out order (its cost map is of the old frame) and (clear_rng: camera, shard) the RNG states;
-// (clear_base: scene, shard) the history base, which a new camera keeps.
-// acc_gen: every chunk and every reset of the accumulation bumps it (rtiow_denoise_history_variance compares it with the update's).
-void reset_accumulation(rtiow_handle_s* h) { h->acc_samples = 0; h->acc_mode = ACC_MODE_NONE; ++h->acc_gen; }
-// A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
-void invalidate_guides(rtiow_handle_s* h) { h->guides_ok = false; h->denoised_ok = false; }
-void invalidate_frame(rtiow_handle_s* h, bool clear_rng, bool clear_base) {
-    reset_accumulation(h);
-    invalidate_guides(h);
-    h->hist_ok = false; h->plan_ok = false;
-    h->carried.clear();
-    if (clear_rng) h->rng_ready = false;
-    if (clear_base) h->hist_base_ok = false;
-}
-
 // The times a render call on a shard without rows reports.
 void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
 
@@ -259,7 +233,8 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (!h) return RTIOW_E_BADARG;
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
-    invalidate_frame(h, false, true);
+    on_set_scene(h->preview);
+    h->carried.clear();                                  // its cost map is of the old frame (so too after a new camera or shard)
     return by_precision(h, [&](auto t) {
         using T = decltype(t);
         return upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid);
@@ -269,50 +244,50 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
 int rtiow_set_camera(rtiow_handle h, const void* camera) {
     if (!h || !camera) return RTIOW_E_BADARG;
     // the very camera the handle already has: the same frame, the carried order stays (everything else is reset as for any camera)
-    const bool same_camera = h->have_camera && std::memcmp(h->precision == 32 ? (const void*)&h->cam32 : (const void*)&h->cam64, camera,
+    const bool same_camera = h->preview.have_camera && std::memcmp(h->precision == 32 ? (const void*)&h->cam32 : (const void*)&h->cam64, camera,
                                                            h->precision == 32 ? sizeof h->cam32 : sizeof h->cam64) == 0;
-    const CarriedOrder carried = h->carried;
     int W, H, S;
     if (h->precision == 32) { h->cam32 = *(const rtiow_camera_f32*)camera; W = h->cam32.img_width; H = h->cam32.img_height; S = h->cam32.samples_per_pixel; }
     else { h->cam64 = *(const rtiow_camera_f64*)camera; W = h->cam64.img_width; H = h->cam64.img_height; S = h->cam64.samples_per_pixel; }
-    if (W <= 0 || H <= 0 || S < 0 || (int64_t)W * H > 0x7fffffffLL) { h->have_camera = false; return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_camera: bad image size"); }
-    h->have_camera = true;
-    h->local_rows = compute_local_rows(H, h->rank, h->nranks, h->strip_rows);
+    const bool good_size = W > 0 && H > 0 && S >= 0 && (int64_t)W * H <= 0x7fffffffLL;
+    on_set_camera(h->preview, good_size);
+    if (!good_size) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_camera: bad image size");
+    h->local_rows = compute_local_rows(H, h->rank, h->preview.nranks, h->strip_rows);
     h->stats.local_rows = h->local_rows;
-    invalidate_frame(h, true, false);
-    if (same_camera) h->carried = carried;
+    if (!same_camera) h->carried.clear();
     return 0;
 }
 
 int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     if (!h) return RTIOW_E_BADARG;
     if (nranks < 1 || rank < 0 || rank >= nranks || strip_rows < 1) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_shard: bad rank/nranks/strip_rows");
-    h->rank = rank; h->nranks = nranks; h->strip_rows = strip_rows;
-    if (h->have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
-    invalidate_frame(h, true, true);
+    h->rank = rank; h->strip_rows = strip_rows;
+    if (h->preview.have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
+    on_set_shard(h->preview, nranks);
+    h->carried.clear();
     return 0;
 }
 
 int rtiow_local_rows(rtiow_handle h, int* rows) {
     if (!h || !rows) return RTIOW_E_BADARG;
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_local_rows before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_local_rows before rtiow_set_camera");
     *rows = h->local_rows;
     return 0;
 }
 
 int rtiow_local_row_map(rtiow_handle h, int32_t* rows_out) {
     if (!h || !rows_out) return RTIOW_E_BADARG;
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_local_row_map before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_local_row_map before rtiow_set_camera");
     for (int jl = 0; jl < h->local_rows; ++jl)
-        rows_out[jl] = ((jl / h->strip_rows) * h->nranks + h->rank) * h->strip_rows + (jl % h->strip_rows);
+        rows_out[jl] = ((jl / h->strip_rows) * h->preview.nranks + h->rank) * h->strip_rows + (jl % h->strip_rows);
     return 0;
 }
 
 int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
     if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_init_rng before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_init_rng before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
-    reset_accumulation(h);
+    on_accumulation_reset(h->preview);
     const int W = img_w(h), H = img_h(h);
     int index_bits = 1;                                      // bits of the largest GLOBAL pixel index W*H-1
     while (index_bits < XW_JUMPS && ((uint64_t)W * (uint64_t)H - 1) >> index_bits) ++index_bits;
@@ -339,7 +314,7 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
         hipLaunchKernelGGL(xw_low_table_kernel, dim3((1u << XW_LOW_BITS) / 256), dim3(256), 0, h->stream, h->rng_low_table, h->jump, s0, s1, s2, s3, s4);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(rng_init_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->rng, h->jump, (const uint32_t*)h->rng_low_table, d0,
-                           W, H, h->local_rows, h->rank, h->nranks, h->strip_rows);
+                           W, H, h->local_rows, h->rank, h->preview.nranks, h->strip_rows);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
         HIP_TRY(h, hipEventSynchronize(h->ev1));
@@ -347,7 +322,7 @@ int rtiow_init_rng(rtiow_handle h, uint64_t seed) {
         HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
         h->stats.rng_init_ms = ms;
     }
-    h->rng_ready = true;
+    on_rng_initialised(h->preview);
     return 0;
 }
 
@@ -355,8 +330,8 @@ namespace {
 // First half of rtiow_render: everything up to and including the stop event, nothing that blocks
 // the host (main.cu:334-339 without the synchronisation).
 static int render_begin(rtiow_handle_s* h, int T, bool timed) {
-    if (int rc = need_scene(h, "rtiow_render")) return rc;
-    if (int rc = need_rng(h, "rtiow_render")) return rc;
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_render"));
+    PREVIEW_TRY(h, need_rng(h->preview, "rtiow_render"));
     if (T < 0 || T > 32) return fail_arg(h, RTIOW_E_BADARG, "rtiow_render: threads_per_block_row must be 0..32");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
@@ -434,29 +409,28 @@ int rtiow_render_wait(rtiow_handle h, float* kernel_ms) {
 
 int rtiow_accumulate_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
-    reset_accumulation(h);
+    on_accumulation_reset(h->preview);
     return 0;
 }
 
 int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     (void)threads_per_block_row;                         // chunks always run through the persistent hand-out
-    if (int rc = need_scene(h, "rtiow_accumulate")) return rc;
-    if (int rc = need_rng(h, "rtiow_accumulate")) return rc;
-    if (samples <= 0 || samples > 0x7fffffff - h->acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
-    if (h->acc_mode == ACC_MODE_ADAPTIVE) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate after rtiow_accumulate_adaptive: reset the accumulation first");
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_accumulate"));
+    PREVIEW_TRY(h, need_rng(h->preview, "rtiow_accumulate"));
+    if (samples <= 0 || samples > 0x7fffffff - h->preview.acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
+    PREVIEW_TRY(h, need_no_chunk_of(h->preview, "rtiow_accumulate", ACC_MODE_ADAPTIVE));
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
     if (kernel_ms) *kernel_ms = 0;
-    ++h->acc_gen;
-    if (h->local_rows == 0) { zero_times(h); h->acc_samples += samples; h->acc_mode = ACC_MODE_PLAIN; return 0; }
+    on_chunk_begin(h->preview);
+    if (h->local_rows == 0) { zero_times(h); on_plain_chunk(h->preview, samples); return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
     if ((rc = by_precision(h, [&](auto t) { return launch_accumulate<decltype(t)>(h, samples, timed); }))) return rc;
-    h->acc_samples += samples;
-    h->acc_mode = ACC_MODE_PLAIN;
+    on_plain_chunk(h->preview, samples);
     h->stats.prepass_ms = 0; h->stats.place_ms = 0;
     if (timed) {                                         // the start event: launch_accumulate, behind its allocations
         if ((rc = timed_end(h, kernel_ms))) return rc;
@@ -467,7 +441,7 @@ int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, flo
 
 int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
     if (!h || !samples) return RTIOW_E_BADARG;
-    if (h->acc_mode == ACC_MODE_ADAPTIVE) {             // the largest per-pixel count, kept on the device by adaptive_finish_kernel
+    if (h->preview.acc_mode == ACC_MODE_ADAPTIVE) {     // the largest per-pixel count, kept on the device by adaptive_finish_kernel
         unsigned mx = 0;
         if (h->local_rows > 0) {
             HIP_TRY(h, hipSetDevice(h->device));
@@ -477,25 +451,36 @@ int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
         *samples = (int)mx;
         return 0;
     }
-    *samples = h->acc_samples;
+    *samples = h->preview.acc_samples;
     return 0;
 }
 
 namespace {
-// What rtiow_accumulate_adaptive and rtiow_accumulate_budget share once their arguments and states are checked: the chunk and its times.
-int adaptive_chunk(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule rule, int max_samples, float* kernel_ms, int* active_pixels) {
+// What rtiow_accumulate_adaptive and rtiow_accumulate_budget (`call`) share: the checks (rule_ok, rule_text: the rule's own argument), the chunk and its times.
+int adaptive_chunk(rtiow_handle_s* h, const char* call, int samples, int min_samples, AdaptiveRule rule, bool rule_ok, const char* rule_text,
+                   int max_samples, float* kernel_ms, int* active_pixels) {
+    if (active_pixels) *active_pixels = 0;
+    if (kernel_ms) *kernel_ms = 0;
+    PREVIEW_TRY(h, need_scene(h->preview, call));
+    PREVIEW_TRY(h, need_rng(h->preview, call));
+    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !rule_ok)
+        return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": need samples > 0, 0 <= min_samples <= max_samples, " + rule_text).c_str());
+    if (!plan_order_fits(img_w(h), h->local_rows))
+        return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": frames wider than 65535 or with more than 32767 local rows are not supported").c_str());
+    PREVIEW_TRY(h, need_no_chunk_of(h->preview, call, ACC_MODE_PLAIN));
+    if (rule.budget) PREVIEW_TRY(h, need_plan(h->preview, call));
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
     h->render_pending = false;                           // the chunk reuses the events of rtiow_render_async
-    ++h->acc_gen;
-    if (h->local_rows == 0) { zero_times(h); h->stats.primary_rays = 0; h->acc_mode = ACC_MODE_ADAPTIVE; return 0; }
+    on_chunk_begin(h->preview);
+    if (h->local_rows == 0) { zero_times(h); h->stats.primary_rays = 0; on_adaptive_chunk(h->preview); return 0; }
     const bool timed = kernel_ms != nullptr;
     if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
     int active = 0;
     rc = by_precision(h, [&](auto t) { return launch_adaptive<decltype(t)>(h, samples, min_samples, rule, max_samples, timed, active); });
     if (rc) return rc;
-    h->acc_mode = ACC_MODE_ADAPTIVE;
+    on_adaptive_chunk(h->preview);
     if (active_pixels) *active_pixels = active;
     h->stats.prepass_ms = 0; h->stats.place_ms = 0;
     if (timed) {
@@ -513,38 +498,23 @@ int adaptive_chunk(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule
 
 int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels) {
     if (!h) return RTIOW_E_BADARG;
-    if (active_pixels) *active_pixels = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    if (int rc = need_scene(h, "rtiow_accumulate_adaptive")) return rc;
-    if (int rc = need_rng(h, "rtiow_accumulate_adaptive")) return rc;
-    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(rel_error >= 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: need samples > 0, 0 <= min_samples <= max_samples, rel_error >= 0");
-    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_adaptive: frames wider than 65535 or with more than 32767 local rows are not supported");
-    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_adaptive after rtiow_accumulate: reset the accumulation first");
-    return adaptive_chunk(h, samples, min_samples, AdaptiveRule{false, rel_error, 0.0}, max_samples, kernel_ms, active_pixels);
+    return adaptive_chunk(h, "rtiow_accumulate_adaptive", samples, min_samples, AdaptiveRule{false, rel_error, 0.0}, rel_error >= 0, "rel_error >= 0",
+                          max_samples, kernel_ms, active_pixels);
 }
 
 // ---- History-guided sample budgets
 int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels) {
     if (!h) return RTIOW_E_BADARG;
-    if (active_pixels) *active_pixels = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    if (int rc = need_scene(h, "rtiow_accumulate_budget")) return rc;
-    if (int rc = need_rng(h, "rtiow_accumulate_budget")) return rc;
-    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !(target > 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_budget: need samples > 0, 0 <= min_samples <= max_samples, target > 0 (+inf: everybody)");
-    if (!plan_order_fits(img_w(h), h->local_rows)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate_budget: frames wider than 65535 or with more than 32767 local rows are not supported");
-    if (h->acc_mode == ACC_MODE_PLAIN) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_budget after rtiow_accumulate: reset the accumulation first");
-    if (!h->plan_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_accumulate_budget: no history plan for the current camera (rtiow_history_plan)");
-    return adaptive_chunk(h, samples, min_samples, AdaptiveRule{true, 0.0, target}, max_samples, kernel_ms, active_pixels);
+    return adaptive_chunk(h, "rtiow_accumulate_budget", samples, min_samples, AdaptiveRule{true, 0.0, target}, target > 0, "target > 0 (+inf: everybody)",
+                          max_samples, kernel_ms, active_pixels);
 }
 
 int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_adaptive_state before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_adaptive_state before rtiow_set_camera");
     const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_adaptive_state: npix must be local_rows x width");
-    if (h->acc_mode != ACC_MODE_ADAPTIVE || want == 0) {  // no adaptive chunk since the reset: n = 0, err = +inf
+    if (h->preview.acc_mode != ACC_MODE_ADAPTIVE || want == 0) {  // no adaptive chunk since the reset: n = 0, err = +inf
         for (size_t k = 0; k < want; ++k) { if (counts) counts[k] = 0; if (rel_err) rel_err[k] = HUGE_VALF; }
         return 0;
     }
@@ -560,18 +530,52 @@ namespace {
 int render_guides(rtiow_handle_s* h) {
     return by_precision(h, [&](auto t) { return launch_guides<decltype(t)>(h); });
 }
-// D2H copy of `bytes` from a device buffer on the handle's stream, then wait.
+// D2H copy of `bytes` from a device buffer on the handle's stream, then wait.  A NULL host wanted the call's checks only.
 int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
-    if (!bytes) return 0;
+    if (!bytes || !host) return 0;
+    HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+// What the calls that filter, reproject or plan share once they have checked their arguments and the state: the pass, enqueued by
+// pass(T()) in the handle's precision, between the events of kernel_ms and behind guides that are current (extern "C++": a template).
+extern "C++" template <class Pass>
+int run_pass(rtiow_handle_s* h, float* kernel_ms, Pass pass) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if (!h->preview.guides_ok && (rc = render_guides(h))) return rc;
+    if ((rc = by_precision(h, pass))) return rc;
+    return timed_end(h, kernel_ms);
+}
+// The one or two counters a pass left on the device (hist_ctr, plan_ctr) for whichever of them the caller asked for.
+int read_counters(rtiow_handle_s* h, const unsigned* dev, uint64_t* first, uint64_t* second = nullptr) {
+    if (!first && !second) return 0;
+    unsigned count[2] = {0, 0};
+    if (int rc = copy_out(h, count, dev, (second ? 2 : 1) * sizeof(unsigned))) return rc;
+    if (first) *first = count[0];
+    if (second) *second = count[1];
+    return 0;
+}
+// `want` pixels of 4 T each on the device -> a plane of their first three T and a plane of their fourth (NULL: not wanted): {n.xyz, depth}
+// and {albedo.rgb, x} of the guides, {H.rgb, M} of the base, {C.rgb, M} of the temporal image.
+int read_planes(rtiow_handle_s* h, const void* dev, size_t want, void* first3, void* fourth) {
+    if (!first3 && !fourth) return 0;
+    const size_t es = elem_size(h);
+    std::vector<unsigned char> host(want * 4 * es);
+    if (int rc = copy_out(h, host.data(), dev, host.size())) return rc;
+    for (size_t k = 0; k < want; ++k) {
+        if (first3) std::memcpy((unsigned char*)first3 + 3 * k * es, host.data() + 4 * k * es, 3 * es);
+        if (fourth) std::memcpy((unsigned char*)fourth + k * es, host.data() + (4 * k + 3) * es, es);
+    }
     return 0;
 }
 }  // namespace
 
 int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_linear: no chunk since the last reset");
+    PREVIEW_TRY(h, need_chunk(h->preview, "rtiow_read_linear", ASKS_CAMERA));
     const size_t need = image_bytes(h);
     if (bytes != need || (need && !host_rgb)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_linear: bytes must be local_rows x width x 3 x sizeof(T)");
     if (need == 0) return 0;
@@ -583,9 +587,9 @@ int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes) {
 int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    if (int rc = need_scene(h, "rtiow_render_guides")) return rc;
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_render_guides"));
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->local_rows == 0) { h->guides_ok = true; return 0; }
+    if (h->local_rows == 0) { on_guides_rendered(h->preview); return 0; }
     int rc = timed_begin(h, kernel_ms);
     if (rc) return rc;
     if ((rc = render_guides(h))) return rc;
@@ -597,28 +601,19 @@ namespace {
 // rtiow_read_filter_guides (`call`); bounces: (int)x of the filter guides, 0 when they are the first-hit buffers (from_chain false).
 int read_guide_planes(rtiow_handle_s* h, const char* call, const void* dev_nd, const void* dev_alb, bool from_chain, void* normal, void* albedo,
                       void* depth, int32_t* bounces, size_t npix) {
-    if (!h->have_camera || !h->guides_ok)
-        return fail_arg(h, RTIOW_E_STATE, (std::string(call) + ": no guides for the current scene, camera and shard (rtiow_render_guides)").c_str());
-    const size_t want = local_pixels(h);
+    PREVIEW_TRY(h, need_guides(h->preview, call));
+    const size_t want = local_pixels(h), es = elem_size(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": npix must be local_rows x width").c_str());
-    if (want == 0 || (!normal && !albedo && !depth && !bounces)) return 0;
-    if (bounces && !from_chain) std::memset(bounces, 0, want * sizeof(int32_t));
-    const bool need_alb = albedo || (bounces && from_chain);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t es = elem_size(h);
-    std::vector<unsigned char> nd(normal || depth ? want * 4 * es : 0), alb(need_alb ? want * 4 * es : 0);
-    if (normal || depth) HIP_TRY(h, hipMemcpyAsync(nd.data(), dev_nd, nd.size(), hipMemcpyDeviceToHost, h->stream));
-    if (need_alb) HIP_TRY(h, hipMemcpyAsync(alb.data(), dev_alb, alb.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (size_t k = 0; k < want; ++k) {                  // {n.xyz, depth} and {albedo.rgb, x} -> planes
-        if (normal) std::memcpy((unsigned char*)normal + 3 * k * es, nd.data() + 4 * k * es, 3 * es);
-        if (depth) std::memcpy((unsigned char*)depth + k * es, nd.data() + (4 * k + 3) * es, es);
-        if (albedo) std::memcpy((unsigned char*)albedo + 3 * k * es, alb.data() + 4 * k * es, 3 * es);
-        if (bounces && from_chain) {
-            const unsigned char* x = alb.data() + (4 * k + 3) * es;
-            if (es == 4) { float v; std::memcpy(&v, x, 4); bounces[k] = (int32_t)v; }
-            else { double v; std::memcpy(&v, x, 8); bounces[k] = (int32_t)v; }
-        }
+    if (int rc = read_planes(h, dev_nd, want, normal, depth)) return rc;
+    if (!bounces || !from_chain) {
+        if (bounces) std::memset(bounces, 0, want * sizeof(int32_t));
+        return read_planes(h, dev_alb, want, albedo, nullptr);
+    }
+    std::vector<unsigned char> x(want * es);
+    if (int rc = read_planes(h, dev_alb, want, albedo, x.data())) return rc;
+    for (size_t k = 0; k < want; ++k) {
+        if (es == 4) { float v; std::memcpy(&v, x.data() + k * es, 4); bounces[k] = (int32_t)v; }
+        else { double v; std::memcpy(&v, x.data() + k * es, 8); bounces[k] = (int32_t)v; }
     }
     return 0;
 }
@@ -636,7 +631,7 @@ int rtiow_set_guide_mode(rtiow_handle h, int mode, int max_bounces, double max_f
     if (mode == RTIOW_GUIDES_FIRST_HIT) {                // the arguments are ignored
         if (h->guide_mode == RTIOW_GUIDES_FIRST_HIT) return 0;
         h->guide_mode = RTIOW_GUIDES_FIRST_HIT;
-        invalidate_guides(h);
+        on_guide_mode_changed(h->preview);
         HIP_TRY(h, hipSetDevice(h->device));             // the first-hit buffers are the filter guides again: no second pair is kept
         HIP_TRY(h, h->chain_nd.reset());
         HIP_TRY(h, h->chain_alb.reset());
@@ -646,7 +641,7 @@ int rtiow_set_guide_mode(rtiow_handle h, int mode, int max_bounces, double max_f
         return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_guide_mode: need max_bounces in 1..16 and max_fuzz >= 0 (+inf: every metal is a mirror)");
     if (h->guide_mode == mode && h->guide_max_bounces == max_bounces && h->guide_max_fuzz == max_fuzz) return 0;
     h->guide_mode = mode; h->guide_max_bounces = max_bounces; h->guide_max_fuzz = max_fuzz;
-    invalidate_guides(h);
+    on_guide_mode_changed(h->preview);
     return 0;
 }
 
@@ -659,33 +654,24 @@ int rtiow_read_filter_guides(rtiow_handle h, void* normal, void* albedo, void* d
 int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
-    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise: levels must be 1..8");
-    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise: every sigma must be > 0 (+inf turns its term off)");
-    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise: no chunk since the last reset");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise: not on a sharded handle (the strips of a shard are not image neighbours)");
     double inv2[4];
-    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2); }))) return rc;
-    return timed_end(h, kernel_ms);
+    PREVIEW_TRY(h, check_filter("rtiow_denoise", levels, {sigma_color, sigma_normal, sigma_albedo, sigma_depth}, inv2));
+    PREVIEW_TRY(h, need_chunk(h->preview, "rtiow_denoise", ASKS_SCENE));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_denoise", true));
+    return run_pass(h, kernel_ms, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2); });
 }
 
 int rtiow_read_denoised(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_denoised before rtiow_denoise");
+    PREVIEW_TRY(h, need_denoised(h->preview, "rtiow_read_denoised"));
     const size_t need = image_bytes(h);
     if (bytes != need || !host_rgb) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_denoised: bytes must be local_rows x width x 3 x sizeof(T)");
-    HIP_TRY(h, hipSetDevice(h->device));
     return copy_out(h, host_rgb, h->denoised, need);
 }
 
 int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
     if (!h || !device_ptr || !bytes) return RTIOW_E_BADARG;
-    if (!h->have_camera || !h->denoised_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoised_device_ptr before rtiow_denoise");
+    PREVIEW_TRY(h, need_denoised(h->preview, "rtiow_denoised_device_ptr"));
     *device_ptr = h->denoised;
     *bytes = image_bytes(h);
     return 0;
@@ -694,7 +680,7 @@ int rtiow_denoised_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) 
 // ---- Variance-guided denoising
 int rtiow_read_variance(rtiow_handle h, void* host_var, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (!h->have_camera || h->acc_mode != ACC_MODE_ADAPTIVE) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_variance: no adaptive chunk since the last reset (plain chunks keep no second moment)");
+    PREVIEW_TRY(h, need_adaptive_chunk(h->preview, "rtiow_read_variance", ASKS_CAMERA));
     const size_t want = local_pixels(h);
     if (npix != want || (want && !host_var)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_variance: npix must be local_rows x width");
     if (want == 0) return 0;
@@ -706,27 +692,18 @@ int rtiow_read_variance(rtiow_handle h, void* host_var, size_t npix) {
 int rtiow_denoise_variance(rtiow_handle h, int levels, double sigma_variance, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    const double sig[4] = {sigma_variance, sigma_normal, sigma_albedo, sigma_depth};
-    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_variance: levels must be 1..8");
-    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_variance: every sigma must be > 0 (+inf turns its term off)");
-    if (!h->have_camera || h->n == 0 || h->acc_mode != ACC_MODE_ADAPTIVE)
-        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_variance: no adaptive chunk since the last reset (plain chunks keep no second moment)");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_variance: not on a sharded handle (the strips of a shard are not image neighbours)");
-    double inv2g[3];
-    for (int k = 0; k < 3; ++k) inv2g[k] = 1.0 / (sig[k + 1] * sig[k + 1]);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2g); }))) return rc;
-    return timed_end(h, kernel_ms);
+    double inv2[4];                                      // [1..3]: the guides' terms; the variance term takes sigma_variance itself
+    PREVIEW_TRY(h, check_filter("rtiow_denoise_variance", levels, {sigma_variance, sigma_normal, sigma_albedo, sigma_depth}, inv2));
+    PREVIEW_TRY(h, need_adaptive_chunk(h->preview, "rtiow_denoise_variance", ASKS_SCENE));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_denoise_variance", true));
+    return run_pass(h, kernel_ms, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2 + 1); });
 }
 
 // ---- Temporal history
 int rtiow_history_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_reset: not on a sharded handle");
-    h->hist_base_ok = false; h->hist_ok = false; h->plan_ok = false;
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_reset", false));
+    on_history_reset(h->preview);
     return 0;
 }
 
@@ -734,22 +711,11 @@ int rtiow_history_update(rtiow_handle h, double depth_tol, double normal_cos, do
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
     if (reprojected_pixels) *reprojected_pixels = 0;
-    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
-    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update: no chunk since the last reset");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update: not on a sharded handle (the strips of a shard are not image neighbours)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_history<decltype(t)>(h, depth_tol, normal_cos, max_history); }))) return rc;
-    if ((rc = timed_end(h, kernel_ms))) return rc;
-    if (reprojected_pixels) {
-        unsigned count = 0;
-        if ((rc = copy_out(h, &count, h->hist_ctr, sizeof count))) return rc;
-        *reprojected_pixels = count;
-    }
-    return 0;
+    PREVIEW_TRY(h, check_history_tolerances("rtiow_history_update", depth_tol, normal_cos, max_history));
+    PREVIEW_TRY(h, need_chunk(h->preview, "rtiow_history_update", ASKS_SCENE));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_update", true));
+    if (int rc = run_pass(h, kernel_ms, [&](auto t) { return launch_history<decltype(t)>(h, depth_tol, normal_cos, max_history); })) return rc;
+    return read_counters(h, h->hist_ctr, reprojected_pixels);
 }
 
 int rtiow_history_update_clipped(rtiow_handle h, double depth_tol, double normal_cos, double max_history, int clip_radius, double clip_gamma,
@@ -758,71 +724,50 @@ int rtiow_history_update_clipped(rtiow_handle h, double depth_tol, double normal
     if (kernel_ms) *kernel_ms = 0;
     if (reprojected_pixels) *reprojected_pixels = 0;
     if (clipped_pixels) *clipped_pixels = 0;
-    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update_clipped: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
-    if (clip_radius < 1 || clip_radius > CLIP_MAX_RADIUS || !(clip_gamma >= 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_update_clipped: need clip_radius in 1..3, clip_gamma >= 0 (+inf: no clamp)");
-    if (!h->have_camera || h->n == 0 || h->acc_mode == ACC_MODE_NONE) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update_clipped: no chunk since the last reset");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_update_clipped: not on a sharded handle (the strips of a shard are not image neighbours)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_history_clip<decltype(t)>(h, depth_tol, normal_cos, max_history, clip_radius, clip_gamma); }))) return rc;
-    if ((rc = timed_end(h, kernel_ms))) return rc;
-    if (reprojected_pixels || clipped_pixels) {
-        unsigned count[2] = {0, 0};
-        if ((rc = copy_out(h, count, h->hist_ctr, sizeof count))) return rc;
-        if (reprojected_pixels) *reprojected_pixels = count[0];
-        if (clipped_pixels) *clipped_pixels = count[1];
-    }
-    return 0;
+    PREVIEW_TRY(h, check_history_tolerances("rtiow_history_update_clipped", depth_tol, normal_cos, max_history));
+    PREVIEW_TRY(h, check_radius("rtiow_history_update_clipped", "clip_radius", clip_radius, CLIP_MAX_RADIUS, clip_gamma >= 0, ", clip_gamma >= 0 (+inf: no clamp)"));
+    PREVIEW_TRY(h, need_chunk(h->preview, "rtiow_history_update_clipped", ASKS_SCENE));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_update_clipped", true));
+    if (int rc = run_pass(h, kernel_ms, [&](auto t) { return launch_history<decltype(t)>(h, depth_tol, normal_cos, max_history, clip_radius, clip_gamma); })) return rc;
+    return read_counters(h, h->hist_ctr, reprojected_pixels, clipped_pixels);
 }
 
 int rtiow_history_plan(rtiow_handle h, double depth_tol, double normal_cos, double max_history, float* kernel_ms, uint64_t* reprojected_pixels) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
     if (reprojected_pixels) *reprojected_pixels = 0;
-    if (!(depth_tol >= 0) || !(normal_cos >= -1 && normal_cos <= 1) || !(max_history > 0))
-        return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_plan: need depth_tol >= 0, normal_cos in [-1, 1], max_history > 0 (+inf: no cap)");
-    if (!h->have_camera || h->n == 0) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_plan before rtiow_set_scene/rtiow_set_camera");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_plan: not on a sharded handle (the strips of a shard are not image neighbours)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_history_plan<decltype(t)>(h, depth_tol, normal_cos, max_history); }))) return rc;
-    if ((rc = timed_end(h, kernel_ms))) return rc;
-    if (reprojected_pixels) {
-        unsigned count = 0;
-        if ((rc = copy_out(h, &count, h->plan_ctr, sizeof count))) return rc;
-        *reprojected_pixels = count;
-    }
-    return 0;
+    PREVIEW_TRY(h, check_history_tolerances("rtiow_history_plan", depth_tol, normal_cos, max_history));
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_history_plan"));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_plan", true));
+    if (int rc = run_pass(h, kernel_ms, [&](auto t) { return launch_history_plan<decltype(t)>(h, depth_tol, normal_cos, max_history); })) return rc;
+    return read_counters(h, h->plan_ctr, reprojected_pixels);
 }
 
 int rtiow_read_history_plan(rtiow_handle h, void* length, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_plan: not on a sharded handle");
-    if (!h->have_camera || !h->plan_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_plan: no history plan for the current camera (rtiow_history_plan)");
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_read_history_plan", false));
+    PREVIEW_TRY(h, need_plan(h->preview, "rtiow_read_history_plan"));
     const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_plan: npix must be height x width");
-    if (!length) return 0;
-    HIP_TRY(h, hipSetDevice(h->device));
     return copy_out(h, length, h->plan_m, want * elem_size(h));
 }
 
-int rtiow_history_commit(rtiow_handle h) {
-    if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit: not on a sharded handle");
-    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit: no temporal image for the current camera (rtiow_history_update)");
-    // the temporal image and the guides become the base by changing owners (the work that wrote them is ordered on the stream before
-    // whatever reads them next); the buffers they leave behind hold the old base, so both go stale
-    std::swap(h->hist_base_hm, h->hist_cm);
+namespace {
+// What both commits end in.  The guides become the base's by changing owners (the work that wrote them is ordered on the stream before
+// whatever reads them next); the buffer they get in exchange holds the old base's, so they go stale, and so does the temporal image.
+void commit_base(rtiow_handle_s* h) {
     std::swap(h->hist_base_nd, h->guide_nd);
     h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
-    h->hist_base_ok = true;
-    h->hist_ok = false; h->plan_ok = false; h->guides_ok = false;
+    on_commit(h->preview);
+}
+}  // namespace
+
+int rtiow_history_commit(rtiow_handle h) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_commit", false));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_history_commit", ASKS_CAMERA));
+    std::swap(h->hist_base_hm, h->hist_cm);              // the temporal image becomes the base as the guides do: by changing owners
+    commit_base(h);
     return 0;
 }
 
@@ -831,71 +776,39 @@ int rtiow_history_commit_filtered(rtiow_handle h, double sigma_color, double sig
                                   float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
-    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_commit_filtered: every sigma must be > 0 (+inf turns its term off)");
-    if (!(feedback > 0 && feedback <= 1)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_commit_filtered: need feedback in (0, 1]");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit_filtered: not on a sharded handle");
-    if (!h->have_camera || h->n == 0 || !h->hist_ok)
-        return fail_arg(h, RTIOW_E_STATE, "rtiow_history_commit_filtered: no temporal image for the current camera (rtiow_history_update)");
     double inv2[4];
-    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_feedback<decltype(t)>(h, inv2, feedback); }))) return rc;
-    if ((rc = timed_end(h, kernel_ms))) return rc;
-    // the kernel wrote {H', M} into the buffer of the old base, so only the guides change owners; the temporal image stays where it
-    // is and goes stale, as after rtiow_history_commit
-    std::swap(h->hist_base_nd, h->guide_nd);
-    h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
-    h->hist_base_ok = true;
-    h->hist_ok = false; h->plan_ok = false; h->guides_ok = false;
+    PREVIEW_TRY(h, check_filter("rtiow_history_commit_filtered", 1, {sigma_color, sigma_normal, sigma_albedo, sigma_depth}, inv2));
+    if (!(feedback > 0 && feedback <= 1)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_history_commit_filtered: need feedback in (0, 1]");
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_commit_filtered", false));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_history_commit_filtered", ASKS_SCENE));
+    if (int rc = run_pass(h, kernel_ms, [&](auto t) { return launch_feedback<decltype(t)>(h, inv2, feedback); })) return rc;
+    commit_base(h);                                      // the kernel wrote {H', M} into the buffer of the old base: the temporal image stays where it is
     return 0;
 }
 
 int rtiow_read_history_base(rtiow_handle h, void* rgb, void* length, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_base: not on a sharded handle");
-    if (!h->hist_base_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_base: no history base (rtiow_history_commit)");
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_read_history_base", false));
+    PREVIEW_TRY(h, need_base(h->preview, "rtiow_read_history_base"));
     // the base keeps the frame it was committed at (it survives rtiow_set_camera)
     const size_t want = h->precision == 64 ? (size_t)h->hist_cam64.img_width * (size_t)h->hist_cam64.img_height
                                            : (size_t)h->hist_cam32.img_width * (size_t)h->hist_cam32.img_height;
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_base: npix must be height x width of the base's frame");
-    if (!rgb && !length) return 0;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t es = elem_size(h);
-    std::vector<unsigned char> hm(want * 4 * es);
-    if (int rc = copy_out(h, hm.data(), h->hist_base_hm, hm.size())) return rc;
-    for (size_t k = 0; k < want; ++k) {                  // {H.rgb, M} -> planes
-        if (rgb) std::memcpy((unsigned char*)rgb + 3 * k * es, hm.data() + 4 * k * es, 3 * es);
-        if (length) std::memcpy((unsigned char*)length + k * es, hm.data() + (4 * k + 3) * es, es);
-    }
-    return 0;
+    return read_planes(h, h->hist_base_hm, want, rgb, length);
 }
 
 int rtiow_read_history(rtiow_handle h, void* rgb, void* length, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history: not on a sharded handle");
-    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history: no temporal image for the current camera (rtiow_history_update)");
-    const size_t want = local_pixels(h);
-    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history: npix must be height x width");
-    if (!rgb && !length) return 0;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t es = elem_size(h);
-    std::vector<unsigned char> cm(want * 4 * es);
-    if (int rc = copy_out(h, cm.data(), h->hist_cm, cm.size())) return rc;
-    for (size_t k = 0; k < want; ++k) {                  // {C.rgb, M} -> planes
-        if (rgb) std::memcpy((unsigned char*)rgb + 3 * k * es, cm.data() + 4 * k * es, 3 * es);
-        if (length) std::memcpy((unsigned char*)length + k * es, cm.data() + (4 * k + 3) * es, es);
-    }
-    return 0;
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_read_history", false));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_read_history", ASKS_CAMERA));
+    if (npix != local_pixels(h)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history: npix must be height x width");
+    return read_planes(h, h->hist_cm, npix, rgb, length);
 }
 
 int rtiow_history_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
     if (!h || !device_ptr || !bytes) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_device_ptr: not on a sharded handle");
-    if (!h->have_camera || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_history_device_ptr: no temporal image for the current camera (rtiow_history_update)");
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_device_ptr", false));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_history_device_ptr", ASKS_CAMERA));
     *device_ptr = h->hist_cm;
     *bytes = local_pixels(h) * 4 * elem_size(h);
     return 0;
@@ -904,19 +817,11 @@ int rtiow_history_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
 int rtiow_denoise_history(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    const double sig[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_depth};
-    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history: levels must be 1..8");
-    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history: every sigma must be > 0 (+inf turns its term off)");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history: not on a sharded handle (the strips of a shard are not image neighbours)");
-    if (!h->have_camera || h->n == 0 || !h->hist_ok) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history: no temporal image for the current camera (rtiow_history_update)");
     double inv2[4];
-    for (int k = 0; k < 4; ++k) inv2[k] = 1.0 / (sig[k] * sig[k]);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2, true); }))) return rc;
-    return timed_end(h, kernel_ms);
+    PREVIEW_TRY(h, check_filter("rtiow_denoise_history", levels, {sigma_color, sigma_normal, sigma_albedo, sigma_depth}, inv2));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_denoise_history", true));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_denoise_history", ASKS_SCENE));
+    return run_pass(h, kernel_ms, [&](auto t) { return launch_denoise<decltype(t)>(h, levels, inv2, true); });
 }
 
 // ---- Variance-guided filtering of the temporal image
@@ -924,34 +829,21 @@ int rtiow_denoise_history_variance(rtiow_handle h, int levels, double sigma_vari
                                    int variance_radius, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
-    const double sig[4] = {sigma_variance, sigma_normal, sigma_albedo, sigma_depth};
-    if (levels < 1 || levels > 8) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: levels must be 1..8");
-    for (double s : sig) if (!(s > 0)) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: every sigma must be > 0 (+inf turns its term off)");
-    if (variance_radius < 1 || variance_radius > NOISE_MAX_RADIUS) return fail_arg(h, RTIOW_E_BADARG, "rtiow_denoise_history_variance: need variance_radius in 1..3");
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: not on a sharded handle (the strips of a shard are not image neighbours)");
-    if (!h->have_camera || h->n == 0 || !h->hist_ok)
-        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: no temporal image for the current camera (rtiow_history_update)");
-    if (h->hist_gen != h->acc_gen)
-        return fail_arg(h, RTIOW_E_STATE, "rtiow_denoise_history_variance: a chunk or a reset since the update that wrote the temporal image (update again)");
-    double inv2g[3];
-    for (int k = 0; k < 3; ++k) inv2g[k] = 1.0 / (sig[k + 1] * sig[k + 1]);
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if (!h->guides_ok && (rc = render_guides(h))) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2g, true, variance_radius); }))) return rc;
-    return timed_end(h, kernel_ms);
+    double inv2[4];                                      // [1..3]: the guides' terms, as in rtiow_denoise_variance
+    PREVIEW_TRY(h, check_filter("rtiow_denoise_history_variance", levels, {sigma_variance, sigma_normal, sigma_albedo, sigma_depth}, inv2));
+    PREVIEW_TRY(h, check_radius("rtiow_denoise_history_variance", "variance_radius", variance_radius, NOISE_MAX_RADIUS));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_denoise_history_variance", true));
+    PREVIEW_TRY(h, need_temporal_image(h->preview, "rtiow_denoise_history_variance", ASKS_SCENE));
+    PREVIEW_TRY(h, need_same_accumulation(h->preview, "rtiow_denoise_history_variance"));
+    return run_pass(h, kernel_ms, [&](auto t) { return launch_denoise_variance<decltype(t)>(h, levels, sigma_variance, inv2 + 1, true, variance_radius); });
 }
 
 int rtiow_read_history_variance(rtiow_handle h, void* var, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    if (h->nranks > 1) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_variance: not on a sharded handle");
-    if (!h->have_camera || !h->hist_ok || !h->hist_var_ok)
-        return fail_arg(h, RTIOW_E_STATE, "rtiow_read_history_variance: no variance plane for the temporal image (rtiow_denoise_history_variance)");
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_read_history_variance", false));
+    PREVIEW_TRY(h, need_temporal_variance(h->preview, "rtiow_read_history_variance"));
     const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_variance: npix must be height x width");
-    if (!var) return 0;
-    HIP_TRY(h, hipSetDevice(h->device));
     return copy_out(h, var, h->hist_var, want * elem_size(h));
 }
 
@@ -969,8 +861,8 @@ int rtiow_device(rtiow_handle h, int* device) {
 
 int rtiow_count_segments(rtiow_handle h, int threads_per_block_row, uint64_t* segments) {
     if (!h || !segments) return RTIOW_E_BADARG;
-    if (int rc = need_scene(h, "rtiow_count_segments")) return rc;
-    if (int rc = need_rng(h, "rtiow_count_segments")) return rc;
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_count_segments"));
+    PREVIEW_TRY(h, need_rng(h->preview, "rtiow_count_segments"));
     const int T = threads_per_block_row;
     if (T < 0 || T > 32) return fail_arg(h, RTIOW_E_BADARG, "rtiow_count_segments: threads_per_block_row must be 0..32");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1003,7 +895,7 @@ int rtiow_bind_framebuffer(rtiow_handle h, void* device_ptr, size_t bytes) {
 
 int rtiow_framebuffer_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes) {
     if (!h || !device_ptr) return RTIOW_E_BADARG;
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "framebuffer requested before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "framebuffer requested before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_framebuffer(h);
     if (rc) return rc;
@@ -1014,7 +906,7 @@ int rtiow_framebuffer_device_ptr(rtiow_handle h, void** device_ptr, size_t* byte
 
 int rtiow_read_framebuffer(rtiow_handle h, void* host_rgb, size_t bytes) {
     if (!h || !host_rgb) return RTIOW_E_BADARG;
-    if (!h->have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_framebuffer before rtiow_render");
+    if (!h->preview.have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_framebuffer before rtiow_render");
     const size_t need = image_bytes(h);
     if (bytes < need) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_framebuffer: host buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1025,7 +917,7 @@ int rtiow_read_framebuffer(rtiow_handle h, void* host_rgb, size_t bytes) {
 
 int rtiow_read_levels(rtiow_handle h, unsigned char* host_levels, size_t bytes, uint64_t* nan_channels) {
     if (!h || !host_levels || !nan_channels) return RTIOW_E_BADARG;
-    if (!h->have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_levels before rtiow_render");
+    if (!h->preview.have_camera || !h->fb) return fail_arg(h, RTIOW_E_STATE, "rtiow_read_levels before rtiow_render");
     const size_t n = local_pixels(h) * 3;
     if (bytes < n) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_levels: host buffer too small");
     *nan_channels = 0;
@@ -1091,7 +983,7 @@ int rtiow_synchronize(rtiow_handle h) {
 #ifdef RTIOW_DEBUG_API       // test hooks (include/rtiow_debug.h): compiled into lib/librtiow_hip_debug.so only
 int rtiow_debug_read_rng(rtiow_handle h, uint32_t* host_states, size_t count_words) {
     if (!h || !host_states) return RTIOW_E_BADARG;
-    if (!h->rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_rng before rtiow_init_rng");
+    if (!h->preview.rng_ready) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_rng before rtiow_init_rng");
     const size_t npix = local_pixels(h);
     if (count_words < npix * 6) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_rng: buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1138,7 +1030,7 @@ int rtiow_debug_read_order(rtiow_handle h, int32_t* info12, int32_t* order, size
 int rtiow_debug_read_chunk_costs(rtiow_handle h, uint32_t* costs, size_t count) {
     if (!h || !costs) return RTIOW_E_BADARG;
     const size_t npix = local_pixels(h);
-    if (h->acc_mode != ACC_MODE_PLAIN || h->acc_samples <= 0 || !h->acc_cost || npix == 0)
+    if (h->preview.acc_mode != ACC_MODE_PLAIN || h->preview.acc_samples <= 0 || !h->acc_cost || npix == 0)
         return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_read_chunk_costs: no rtiow_accumulate chunk since the last reset");
     if (count < npix) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_read_chunk_costs: buffer too small");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1187,7 +1079,7 @@ int rtiow_debug_pixel_times(rtiow_handle h, int threads_per_block_row, uint32_t*
     return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times: this build was compiled without -DRTIOW_PIXEL_TIMES (scripts/pixel_finish_study.py builds lib/ab/pixel_times.so)");
 #endif
     if (h->schedule == RTIOW_SCHED_STATIC) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times needs a persistent schedule");
-    if (!h->have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times before rtiow_set_camera");
+    if (!h->preview.have_camera) return fail_arg(h, RTIOW_E_STATE, "rtiow_debug_pixel_times before rtiow_set_camera");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t words = local_pixels(h) * 4;
     if (cap_words < words) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_pixel_times: buffer too small");
@@ -1205,7 +1097,7 @@ int rtiow_debug_pixel_times(rtiow_handle h, int threads_per_block_row, uint32_t*
 
 int rtiow_debug_hit_world(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out) {
     if (!h || n <= 0 || !rays || !t_out || !index_out) return RTIOW_E_BADARG;
-    if (int rc = need_scene(h, "rtiow_debug_hit_world")) return rc;
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_debug_hit_world"));
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h);
     DeviceBuffer<> dr, dt;
@@ -1222,7 +1114,7 @@ int rtiow_debug_hit_world(rtiow_handle h, int n, const void* rays, void* t_out, 
 int rtiow_debug_scatter(rtiow_handle h, int form, int n, const void* in_real11, const int32_t* in_int2, const uint32_t* in_state6,
                         void* out_real12, int32_t* out_int4, uint32_t* out_state6, int* rounds_per_trip) {
     if (!h || n <= 0 || !in_real11 || !in_int2 || !in_state6 || !out_real12 || !out_int4 || !out_state6) return RTIOW_E_BADARG;
-    if (int rc = need_scene(h, "rtiow_debug_scatter")) return rc;
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_debug_scatter"));
     if (form < 0 || form > 2) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: form is 0, 1 or 2");
     if (form == 2 && h->precision != 64) return fail_arg(h, RTIOW_E_BADARG, "rtiow_debug_scatter: form 2 (the rotated trip) exists in fp64 only");
     for (int k = 0; k < n; ++k)
