@@ -84,42 +84,127 @@ class GroupStats(ctypes.Structure):
                 ("create_ms", ctypes.c_double), ("peer_links", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
-# Every symbol include/rtiow.h declares (tests check that the built library exports them all).
-HIP_SYMBOLS = [
-    "rtiow_abi_version", "rtiow_build_id", "rtiow_create", "rtiow_destroy", "rtiow_last_error_string", "rtiow_set_stream",
-    "rtiow_set_scene", "rtiow_set_camera", "rtiow_set_shard", "rtiow_local_rows", "rtiow_local_row_map",
-    "rtiow_init_rng", "rtiow_render", "rtiow_count_segments", "rtiow_bind_framebuffer", "rtiow_framebuffer_device_ptr",
-    "rtiow_read_framebuffer", "rtiow_read_levels", "rtiow_set_scene_source", "rtiow_set_schedule", "rtiow_get_stats", "rtiow_synchronize",
-    "rtiow_render_async", "rtiow_render_wait", "rtiow_stream", "rtiow_device",
-    "rtiow_accumulate_reset", "rtiow_accumulate", "rtiow_accumulated_samples", "rtiow_accumulate_adaptive", "rtiow_read_adaptive_state",
-    "rtiow_read_linear", "rtiow_render_guides", "rtiow_read_guides", "rtiow_denoise", "rtiow_read_denoised", "rtiow_denoised_device_ptr",
-    "rtiow_read_variance", "rtiow_denoise_variance",
-    "rtiow_history_reset", "rtiow_history_update", "rtiow_history_commit", "rtiow_read_history", "rtiow_history_device_ptr", "rtiow_denoise_history",
-    "rtiow_set_guide_mode", "rtiow_read_filter_guides",
-    "rtiow_history_plan", "rtiow_read_history_plan", "rtiow_accumulate_budget",
-    "rtiow_history_update_clipped",
-    "rtiow_denoise_history_variance", "rtiow_read_history_variance",
-    "rtiow_history_commit_filtered", "rtiow_read_history_base",
-    "rtiow_group_create", "rtiow_group_create_error", "rtiow_group_destroy", "rtiow_group_last_error_string", "rtiow_group_size", "rtiow_group_member",
-    "rtiow_group_set_scene", "rtiow_group_set_camera", "rtiow_group_set_scene_source", "rtiow_group_set_schedule",
-    "rtiow_group_init_rng", "rtiow_group_render", "rtiow_group_gather", "rtiow_group_framebuffer_device_ptr",
-    "rtiow_group_read_framebuffer", "rtiow_group_get_stats", "rtiow_group_transport_note",
-]
-# include/rtiow_debug.h: exported by lib/librtiow_hip_debug.so (the test build) only
-DEBUG_SYMBOLS = [
-    "rtiow_debug_read_rng", "rtiow_debug_read_costs", "rtiow_debug_timeline", "rtiow_debug_pixel_times", "rtiow_debug_ops", "rtiow_debug_jump_matrices", "rtiow_debug_grid_plan", "rtiow_debug_hit_world", "rtiow_debug_scatter",
-    "rtiow_debug_gather_schedule", "rtiow_debug_read_order", "rtiow_debug_read_chunk_costs", "rtiow_debug_poison_staged",
-]
+# The C types the headers use, by the names the tables below spell them with.
+_int, _dbl, _size, _u64, _str, _vp = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_void_p
+_H = _G = ctypes.c_void_p                                   # rtiow_handle, rtiow_group
+_intp, _i32p, _i64p = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+_u8p, _u16p, _u32p, _u64p = (ctypes.POINTER(t) for t in (ctypes.c_ubyte, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint64))
+_f32p, _f64p, _sizep, _vpp = (ctypes.POINTER(t) for t in (ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p))
+
+# One row per function, in the order of its header: symbol -> argtypes.  The loaders below declare every row on the library they open;
+# tests, probe scripts and the wrappers below all call through these declarations.  Every function returns int but those of RESTYPES.
+HIP_ABI = {                                                 # include/rtiow.h: librtiow_hip.so and the test build
+    "rtiow_abi_version": (),
+    "rtiow_build_id": (),
+    "rtiow_create": (_int, _int, ctypes.POINTER(_H)),
+    "rtiow_destroy": (_H,),
+    "rtiow_last_error_string": (_H,),
+    "rtiow_set_stream": (_H, _vp),
+    "rtiow_set_scene": (_H, _int, _vp, _vp, _vp, _i32p, _i32p),
+    "rtiow_set_camera": (_H, _vp),
+    "rtiow_set_shard": (_H, _int, _int, _int),
+    "rtiow_local_rows": (_H, _intp),
+    "rtiow_local_row_map": (_H, _i32p),
+    "rtiow_init_rng": (_H, _u64),
+    "rtiow_render": (_H, _int, _f32p),
+    "rtiow_render_async": (_H, _int),
+    "rtiow_render_wait": (_H, _f32p),
+    "rtiow_count_segments": (_H, _int, _u64p),
+    "rtiow_accumulate_reset": (_H,),
+    "rtiow_accumulate": (_H, _int, _int, _f32p),
+    "rtiow_accumulated_samples": (_H, _intp),
+    "rtiow_accumulate_adaptive": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_read_adaptive_state": (_H, _i32p, _f32p, _size),
+    "rtiow_read_linear": (_H, _vp, _size),
+    "rtiow_render_guides": (_H, _f32p),
+    "rtiow_read_guides": (_H, _vp, _vp, _vp, _size),
+    "rtiow_denoise": (_H, _int, _dbl, _dbl, _dbl, _dbl, _f32p),
+    "rtiow_read_denoised": (_H, _vp, _size),
+    "rtiow_denoised_device_ptr": (_H, _vpp, _sizep),
+    "rtiow_read_variance": (_H, _vp, _size),
+    "rtiow_denoise_variance": (_H, _int, _dbl, _dbl, _dbl, _dbl, _f32p),
+    "rtiow_history_reset": (_H,),
+    "rtiow_history_update": (_H, _dbl, _dbl, _dbl, _f32p, _u64p),
+    "rtiow_history_commit": (_H,),
+    "rtiow_read_history": (_H, _vp, _vp, _size),
+    "rtiow_history_device_ptr": (_H, _vpp, _sizep),
+    "rtiow_denoise_history": (_H, _int, _dbl, _dbl, _dbl, _dbl, _f32p),
+    "rtiow_set_guide_mode": (_H, _int, _int, _dbl),
+    "rtiow_read_filter_guides": (_H, _vp, _vp, _vp, _i32p, _size),
+    "rtiow_history_plan": (_H, _dbl, _dbl, _dbl, _f32p, _u64p),
+    "rtiow_read_history_plan": (_H, _vp, _size),
+    "rtiow_accumulate_budget": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_history_update_clipped": (_H, _dbl, _dbl, _dbl, _int, _dbl, _f32p, _u64p, _u64p),
+    "rtiow_denoise_history_variance": (_H, _int, _dbl, _dbl, _dbl, _dbl, _int, _f32p),
+    "rtiow_read_history_variance": (_H, _vp, _size),
+    "rtiow_history_commit_filtered": (_H, _dbl, _dbl, _dbl, _dbl, _dbl, _f32p),
+    "rtiow_read_history_base": (_H, _vp, _vp, _size),
+    "rtiow_bind_framebuffer": (_H, _vp, _size),
+    "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
+    "rtiow_read_framebuffer": (_H, _vp, _size),
+    "rtiow_read_levels": (_H, _u8p, _size, _u64p),
+    "rtiow_set_scene_source": (_H, _int),
+    "rtiow_set_schedule": (_H, _int, _int),
+    "rtiow_get_stats": (_H, ctypes.POINTER(Stats)),
+    "rtiow_synchronize": (_H,),
+    "rtiow_stream": (_H, _vpp),
+    "rtiow_device": (_H, _intp),
+    "rtiow_group_create": (_int, _intp, _int, _int, _int, ctypes.POINTER(_G)),
+    "rtiow_group_create_error": (),
+    "rtiow_group_destroy": (_G,),
+    "rtiow_group_last_error_string": (_G,),
+    "rtiow_group_size": (_G,),
+    "rtiow_group_member": (_G, _int, ctypes.POINTER(_H)),
+    "rtiow_group_set_scene": (_G, _int, _vp, _vp, _vp, _i32p, _i32p),
+    "rtiow_group_set_camera": (_G, _vp),
+    "rtiow_group_set_scene_source": (_G, _int),
+    "rtiow_group_set_schedule": (_G, _int, _int),
+    "rtiow_group_init_rng": (_G, _u64),
+    "rtiow_group_render": (_G, _int, _f32p),
+    "rtiow_group_gather": (_G,),
+    "rtiow_group_framebuffer_device_ptr": (_G, _vpp, _sizep),
+    "rtiow_group_read_framebuffer": (_G, _vp, _size),
+    "rtiow_group_get_stats": (_G, ctypes.POINTER(GroupStats)),
+    "rtiow_group_transport_note": (_G,),
+}
+# include/rtiow_debug.h: exported by lib/librtiow_hip_debug.so (the test build) only.  Its two hooks of instrumented builds
+# (rtiow_debug_region_cycles, rtiow_debug_path_stats) are in no library built here and stay out.
+DEBUG_ABI = {
+    "rtiow_debug_read_rng": (_H, _u32p, _size),
+    "rtiow_debug_read_costs": (_H, _u32p, _u32p, _size),
+    "rtiow_debug_read_order": (_H, _i32p, _i32p, _size, _i32p, _u32p, _size),
+    "rtiow_debug_read_chunk_costs": (_H, _u32p, _size),
+    "rtiow_debug_poison_staged": (_H,),
+    "rtiow_debug_timeline": (_H, _int, _u64p, _size, _intp),
+    "rtiow_debug_pixel_times": (_H, _int, _u32p, _size),
+    "rtiow_debug_ops": (_H, _int, _size, _vp, _vp, _vp, _vp),
+    "rtiow_debug_hit_world": (_H, _int, _vp, _vp, _i32p),
+    "rtiow_debug_scatter": (_H, _int, _int, _vp, _i32p, _u32p, _vp, _i32p, _u32p, _intp),
+    "rtiow_debug_jump_matrices": (_u32p, _size, _int),
+    "rtiow_debug_grid_plan": (_int, _f64p, _f64p, _i32p, _f64p, _u16p, _size, _i32p, _size, _f64p),
+    "rtiow_debug_gather_schedule": (_int, _intp, _intp, _int, _int, _int, _int, _i64p, _size, _intp),
+}
+HOST_ABI = {                                                # include/rtiow_host.h: librtiow_host.so
+    "rtiow_host_scene_slots": (_int,),
+    "rtiow_host_build_scene": (_int, _int, _vp, _vp, _vp, _i32p, _i32p),
+    "rtiow_host_camera": (_int, _int, _int, _int, _int, _vp),
+    "rtiow_host_camera_look": (_int, _int, _int, _int, _int, _f64p, _f64p, _f64p, _dbl, _dbl, _dbl, _vp),
+    "rtiow_host_ppm_filename": (_int, _int, _int, _int, _int, _int, _int, _str, _size),
+    "rtiow_host_write_ppm": (_str, _int, _int, _int, _vp),
+    "rtiow_host_format_ppm": (_int, _int, _int, _vp, _str, _size, _sizep),
+    "rtiow_host_write_ppm_binary": (_str, _int, _int, _int, _vp),
+    "rtiow_host_write_ppm_levels": (_str, _int, _int, _u8p, _int),
+    "rtiow_host_levels": (_int, _int, _int, _vp, _u8p),
+    "rtiow_host_shard_rows": (_int, _int, _int, _int, _i32p),
+    "rtiow_host_place_rows": (_int, _int, _int, _int, _int, _int, _vp, _vp),
+}
+RESTYPES = {"rtiow_build_id": _str, "rtiow_last_error_string": _str, "rtiow_group_create_error": _str, "rtiow_group_last_error_string": _str,
+            "rtiow_group_transport_note": _str, "rtiow_host_levels": ctypes.c_longlong}
+HIP_SYMBOLS, DEBUG_SYMBOLS, HOST_SYMBOLS = list(HIP_ABI), list(DEBUG_ABI), list(HOST_ABI)
 ORDER_NONE, ORDER_RENDER, ORDER_ACCUMULATE, ORDER_ADAPTIVE = 0, 1, 2, 3     # rtiow_debug_read_order: info["kind"]
 ORDER_INFO_FIELDS = ("kind", "total_slots", "solo_slots", "total_pools", "pools_per_block", "deal_group", "lane_cap", "blocks", "n_active", "W", "local_rows")
-HOST_SYMBOLS = [
-    "rtiow_host_scene_slots", "rtiow_host_build_scene", "rtiow_host_camera", "rtiow_host_camera_look", "rtiow_host_ppm_filename",
-    "rtiow_host_write_ppm", "rtiow_host_format_ppm", "rtiow_host_write_ppm_binary", "rtiow_host_write_ppm_levels", "rtiow_host_levels", "rtiow_host_shard_rows", "rtiow_host_place_rows",
-]
 
-_hip = None
-_hip_debug = None
-_host = None
+_loaded = {}
 
 
 def lib_paths():
@@ -130,139 +215,31 @@ def lib_paths():
             "host": os.path.join(_LIBDIR, "librtiow_host.so")}
 
 
-def load_host_library():
-    global _host
-    if _host is None:
-        path = lib_paths()["host"]
+def _load(which, *tables):
+    """dlopen lib_paths()[which] once and declare every row of the tables on it.  Raises loudly when it is missing: no fallback."""
+    if which not in _loaded:
+        path = lib_paths()[which]
         if not os.path.exists(path):
             raise RtiowError(-100, "%s not built; run `python -m raytracingincuda_amd.build`" % path)
         lib = ctypes.CDLL(path)
-        vp, i32p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)
-        lib.rtiow_host_scene_slots.argtypes = [ctypes.c_int]
-        lib.rtiow_host_build_scene.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, i32p, i32p]
-        lib.rtiow_host_camera.argtypes = [ctypes.c_int] * 5 + [vp]
-        d3 = ctypes.POINTER(ctypes.c_double)
-        lib.rtiow_host_camera_look.argtypes = [ctypes.c_int] * 5 + [d3, d3, d3] + [ctypes.c_double] * 3 + [vp]
-        lib.rtiow_host_ppm_filename.argtypes = [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_size_t]
-        lib.rtiow_host_write_ppm.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
-        lib.rtiow_host_write_ppm_binary.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
-        lib.rtiow_host_format_ppm.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p,
-                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-        lib.rtiow_host_shard_rows.argtypes = [ctypes.c_int] * 4 + [i32p]
-        lib.rtiow_host_place_rows.argtypes = [ctypes.c_int] * 6 + [vp, vp]
-        _host = lib
-    return _host
+        for table in tables:
+            for symbol, argtypes in table.items():
+                fn = getattr(lib, symbol)
+                fn.argtypes = argtypes
+                if symbol in RESTYPES:
+                    fn.restype = RESTYPES[symbol]
+        _loaded[which] = lib
+    return _loaded[which]
+
+
+def load_host_library():
+    return _load("host", HOST_ABI)
 
 
 def load_hip_library(debug=False):
     """Load librtiow_hip.so -- or, debug=True, the test build librtiow_hip_debug.so, which also exports the hooks of
     include/rtiow_debug.h.  Raises loudly when it is missing: there is no fallback path."""
-    global _hip, _hip_debug
-    if (_hip_debug if debug else _hip) is None:
-        path = lib_paths()["hip_debug" if debug else "hip"]
-        if not os.path.exists(path):
-            raise RtiowError(-100, "%s not built; run `python -m raytracingincuda_amd.build`" % path)
-        lib = ctypes.CDLL(path)
-        vp, H = ctypes.c_void_p, ctypes.c_void_p
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        lib.rtiow_abi_version.argtypes = []
-        lib.rtiow_build_id.argtypes = []
-        lib.rtiow_build_id.restype = ctypes.c_char_p
-        lib.rtiow_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(H)]
-        lib.rtiow_destroy.argtypes = [H]
-        lib.rtiow_last_error_string.argtypes = [H]
-        lib.rtiow_last_error_string.restype = ctypes.c_char_p
-        lib.rtiow_set_stream.argtypes = [H, vp]
-        lib.rtiow_set_scene.argtypes = [H, ctypes.c_int, vp, vp, vp, i32p, i32p]
-        lib.rtiow_set_camera.argtypes = [H, vp]
-        lib.rtiow_set_shard.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        lib.rtiow_local_rows.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_local_row_map.argtypes = [H, i32p]
-        lib.rtiow_init_rng.argtypes = [H, ctypes.c_uint64]
-        lib.rtiow_render.argtypes = [H, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_count_segments.argtypes = [H, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-        lib.rtiow_bind_framebuffer.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_framebuffer_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-        lib.rtiow_read_framebuffer.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_set_scene_source.argtypes = [H, ctypes.c_int]
-        lib.rtiow_set_schedule.argtypes = [H, ctypes.c_int, ctypes.c_int]
-        lib.rtiow_get_stats.argtypes = [H, ctypes.POINTER(Stats)]
-        lib.rtiow_synchronize.argtypes = [H]
-        if debug:
-            lib.rtiow_debug_read_rng.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
-            lib.rtiow_debug_read_costs.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
-            lib.rtiow_debug_read_order.argtypes = [H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
-                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
-            lib.rtiow_debug_read_chunk_costs.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
-            lib.rtiow_debug_poison_staged.argtypes = [H]
-            lib.rtiow_debug_timeline.argtypes = [H, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
-            lib.rtiow_debug_ops.argtypes = [H, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp]
-            lib.rtiow_debug_gather_schedule.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_render_async.argtypes = [H, ctypes.c_int]
-        lib.rtiow_render_wait.argtypes = [H, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_stream.argtypes = [H, ctypes.POINTER(vp)]
-        lib.rtiow_device.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_accumulate_reset.argtypes = [H]
-        lib.rtiow_accumulate.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_accumulated_samples.argtypes = [H, ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_accumulate_adaptive.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
-                                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_read_adaptive_state.argtypes = [H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
-        lib.rtiow_read_linear.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_render_guides.argtypes = [H, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_read_guides.argtypes = [H, vp, vp, vp, ctypes.c_size_t]
-        lib.rtiow_denoise.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_read_denoised.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_denoised_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-        lib.rtiow_read_variance.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_denoise_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_history_reset.argtypes = [H]
-        lib.rtiow_history_update.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
-        lib.rtiow_history_commit.argtypes = [H]
-        lib.rtiow_read_history.argtypes = [H, vp, vp, ctypes.c_size_t]
-        lib.rtiow_history_plan.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
-        lib.rtiow_read_history_plan.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_accumulate_budget.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
-                                                ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
-        lib.rtiow_history_update_clipped.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
-                                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        lib.rtiow_denoise_history_variance.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                                       ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_read_history_variance.argtypes = [H, vp, ctypes.c_size_t]
-        lib.rtiow_history_commit_filtered.argtypes = [H, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                                      ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_read_history_base.argtypes = [H, vp, vp, ctypes.c_size_t]
-        lib.rtiow_history_device_ptr.argtypes = [H, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-        lib.rtiow_denoise_history.argtypes = [H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_set_guide_mode.argtypes = [H, ctypes.c_int, ctypes.c_int, ctypes.c_double]
-        lib.rtiow_read_filter_guides.argtypes = [H, vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t]
-        G = ctypes.c_void_p
-        lib.rtiow_group_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(G)]
-        lib.rtiow_group_create_error.argtypes = []
-        lib.rtiow_group_create_error.restype = ctypes.c_char_p
-        lib.rtiow_group_destroy.argtypes = [G]
-        lib.rtiow_group_last_error_string.argtypes = [G]
-        lib.rtiow_group_last_error_string.restype = ctypes.c_char_p
-        lib.rtiow_group_transport_note.argtypes = [G]
-        lib.rtiow_group_transport_note.restype = ctypes.c_char_p
-        lib.rtiow_group_size.argtypes = [G]
-        lib.rtiow_group_member.argtypes = [G, ctypes.c_int, ctypes.POINTER(H)]
-        lib.rtiow_group_set_scene.argtypes = [G, ctypes.c_int, vp, vp, vp, i32p, i32p]
-        lib.rtiow_group_set_camera.argtypes = [G, vp]
-        lib.rtiow_group_set_scene_source.argtypes = [G, ctypes.c_int]
-        lib.rtiow_group_set_schedule.argtypes = [G, ctypes.c_int, ctypes.c_int]
-        lib.rtiow_group_init_rng.argtypes = [G, ctypes.c_uint64]
-        lib.rtiow_group_render.argtypes = [G, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-        lib.rtiow_group_gather.argtypes = [G]
-        lib.rtiow_group_framebuffer_device_ptr.argtypes = [G, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-        lib.rtiow_group_read_framebuffer.argtypes = [G, vp, ctypes.c_size_t]
-        lib.rtiow_group_get_stats.argtypes = [G, ctypes.POINTER(GroupStats)]
-        if debug:
-            _hip_debug = lib
-        else:
-            _hip = lib
-    return _hip_debug if debug else _hip
+    return _load("hip_debug", HIP_ABI, DEBUG_ABI) if debug else _load("hip", HIP_ABI)
 
 
 def build_id():
@@ -291,8 +268,8 @@ def build_scene(scene_id, precision=32):
     cr = np.zeros((n, 4), dt); af = np.zeros((n, 4), dt); ri = np.zeros(n, dt)
     ty = np.zeros(n, np.int32); va = np.zeros(n, np.int32)
     got = lib.rtiow_host_build_scene(int(scene_id), precision, cr.ctypes.data, af.ctypes.data, ri.ctypes.data,
-                                     ty.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                     va.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+                                     ty.ctypes.data_as(_i32p),
+                                     va.ctypes.data_as(_i32p))
     if got != n:
         raise RtiowError(got, "rtiow_host_build_scene failed")
     return {"scene_id": int(scene_id), "precision": precision, "center_radius": cr, "albedo_fuzz": af,
@@ -380,10 +357,8 @@ def write_ppm(path, rgb, binary=False):
 def levels(rgb):
     """(levels, nan_channels): main.cu:367, 374-376 per channel on the host, uint8 [H, W, 3] (what rtiow_read_levels computes on the device)."""
     rgb = np.ascontiguousarray(rgb)
-    lib = load_host_library()
-    lib.rtiow_host_levels.restype = ctypes.c_longlong
     out = np.empty(rgb.shape, np.uint8)
-    n = lib.rtiow_host_levels(_rgb_precision(rgb), rgb.shape[1], rgb.shape[0], ctypes.c_void_p(rgb.ctypes.data), ctypes.c_void_p(out.ctypes.data))
+    n = load_host_library().rtiow_host_levels(_rgb_precision(rgb), rgb.shape[1], rgb.shape[0], rgb.ctypes.data, out.ctypes.data_as(_u8p))
     if n < 0:
         raise RtiowError(int(n), "rtiow_host_levels: bad arguments")
     return out, int(n)
@@ -392,7 +367,7 @@ def levels(rgb):
 def write_ppm_levels(path, lev, binary=False):
     """The P3 / P6 file from levels (uint8 [H, W, 3]): threaded formatter, every thread writes its own range of the file."""
     lev = np.ascontiguousarray(lev, np.uint8)
-    rc = load_host_library().rtiow_host_write_ppm_levels(os.fsencode(path), lev.shape[1], lev.shape[0], ctypes.c_void_p(lev.ctypes.data), 1 if binary else 0)
+    rc = load_host_library().rtiow_host_write_ppm_levels(os.fsencode(path), lev.shape[1], lev.shape[0], lev.ctypes.data_as(_u8p), 1 if binary else 0)
     if rc:
         raise RtiowError(rc, "Could not open file for writing: %s" % path)
 
@@ -405,7 +380,7 @@ def shard_rows(height, rank, nranks, strip_rows=8):
         raise RtiowError(n, "rtiow_host_shard_rows: bad arguments")
     rows = np.zeros(n, np.int32)
     if n:
-        lib.rtiow_host_shard_rows(height, rank, nranks, strip_rows, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        lib.rtiow_host_shard_rows(height, rank, nranks, strip_rows, rows.ctypes.data_as(_i32p))
     return rows
 
 
@@ -472,6 +447,23 @@ GUIDE_MAX_BOUNCES = 1
 GUIDE_MAX_FUZZ = 0.0
 
 
+def _out(ctype, wanted=True):
+    """(holder, argument) of an optional output parameter: a zeroed ctype and its address, or NULL when the caller does not want it --
+    kernel_ms and the counts a call only knows after waiting (sync=False)."""
+    holder = ctype(0)
+    return holder, (ctypes.byref(holder) if wanted else None)
+
+
+def _set_scene(fn, handle, scene, dt):
+    """rtiow_set_scene / rtiow_group_set_scene: build_scene()'s five tables in the handle's precision ('valid' may be absent)."""
+    cr = np.ascontiguousarray(scene["center_radius"], dt)
+    af = np.ascontiguousarray(scene["albedo_fuzz"], dt)
+    ri = np.ascontiguousarray(scene["refraction_index"], dt)
+    ty = np.ascontiguousarray(scene["type"], np.int32)
+    va = np.ascontiguousarray(scene["valid"], np.int32) if scene.get("valid") is not None else None
+    return fn(handle, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data, ty.ctypes.data_as(_i32p), va.ctypes.data_as(_i32p) if va is not None else None)
+
+
 class Renderer:
     """One GPU's render state behind the C-ABI handle (include/rtiow.h)."""
 
@@ -495,7 +487,7 @@ class Renderer:
         """A view of a handle somebody else owns (a member of a RendererGroup): close() leaves it alone."""
         r = cls.__new__(cls)
         r._lib, r.precision, r.dtype, r._borrowed = lib, precision, _dtype(precision), True
-        r._debug = hasattr(lib, "rtiow_debug_ops") and lib is _hip_debug
+        r._debug = lib is _loaded.get("hip_debug")
         r._h = handle
         r.width, r.height = width, height
         return r
@@ -525,16 +517,18 @@ class Renderer:
     def set_stream(self, hip_stream):
         self._check(self._lib.rtiow_set_stream(self._h, ctypes.c_void_p(int(hip_stream))))
 
+    def _plane(self, *channels, dtype=None):
+        """An uninitialised host array [local_rows, W, *channels] (the handle's precision unless dtype says otherwise) for a read to fill."""
+        return np.empty((self.local_rows, self.width) + channels, dtype or self.dtype)
+
+    def _device_ptr(self, fn):
+        """(device address, bytes) from one of the *_device_ptr calls."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t(0)
+        self._check(fn(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
     def set_scene(self, scene):
-        dt = self.dtype
-        cr = np.ascontiguousarray(scene["center_radius"], dt)
-        af = np.ascontiguousarray(scene["albedo_fuzz"], dt)
-        ri = np.ascontiguousarray(scene["refraction_index"], dt)
-        ty = np.ascontiguousarray(scene["type"], np.int32)
-        va = np.ascontiguousarray(scene["valid"], np.int32) if scene.get("valid") is not None else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._check(self._lib.rtiow_set_scene(self._h, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data,
-                                              ty.ctypes.data_as(i32p), va.ctypes.data_as(i32p) if va is not None else None))
+        self._check(_set_scene(self._lib.rtiow_set_scene, self._h, scene, self.dtype))
 
     def set_camera(self, cam):
         want = CameraF64 if self.precision == 64 else CameraF32
@@ -556,8 +550,7 @@ class Renderer:
         rays = np.ascontiguousarray(rays, dt)
         n = rays.shape[0]
         t = np.zeros(n, dt); idx = np.zeros(n, np.int32)
-        self._lib.rtiow_debug_hit_world.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        self._check(self._lib.rtiow_debug_hit_world(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data))
+        self._check(self._lib.rtiow_debug_hit_world(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data_as(_i32p)))
         return t, idx
 
     def debug_scatter(self, form, O, D, closest, hit, atten, sky_uy, depth, states):
@@ -575,10 +568,8 @@ class Renderer:
         assert st.shape == (n, 6)
         out = np.zeros((n, 12), dt); oi = np.zeros((n, 4), np.int32); os_ = np.zeros((n, 6), np.uint32)
         rounds = ctypes.c_int(0)
-        vp = ctypes.c_void_p
-        self._lib.rtiow_debug_scatter.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
-        self._check(self._lib.rtiow_debug_scatter(self._h, form, n, real.ctypes.data, ints.ctypes.data, st.ctypes.data,
-                                                  out.ctypes.data, oi.ctypes.data, os_.ctypes.data, ctypes.addressof(rounds)))
+        self._check(self._lib.rtiow_debug_scatter(self._h, form, n, real.ctypes.data, ints.ctypes.data_as(_i32p), st.ctypes.data_as(_u32p),
+                                                  out.ctypes.data, oi.ctypes.data_as(_i32p), os_.ctypes.data_as(_u32p), ctypes.byref(rounds)))
         return {"status": oi[:, 0].copy(), "col": out[:, 0:3].copy(), "O": out[:, 3:6].copy(), "D": out[:, 6:9].copy(), "atten": out[:, 9:12].copy(),
                 "depth": oi[:, 1].copy(), "trips": oi[:, 2].copy(), "flags": oi[:, 3].copy(), "states": os_, "rounds_per_trip": rounds.value}
 
@@ -594,7 +585,7 @@ class Renderer:
     def local_row_map(self):
         rows = np.zeros(self.local_rows, np.int32)
         if len(rows):
-            self._check(self._lib.rtiow_local_row_map(self._h, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+            self._check(self._lib.rtiow_local_row_map(self._h, rows.ctypes.data_as(_i32p)))
         return rows
 
     def init_rng(self, seed=1227):
@@ -602,22 +593,16 @@ class Renderer:
 
     def render(self, threads=8, sync=True):
         """render<<<>>> + sync; returns the HIP-event kernel time in ms (None when sync=False)."""
-        if sync:
-            ms = ctypes.c_float(0)
-            self._check(self._lib.rtiow_render(self._h, int(threads), ctypes.byref(ms)))
-            return ms.value
-        self._check(self._lib.rtiow_render(self._h, int(threads), None))
-        return None
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render(self._h, int(threads), ms_out))
+        return ms.value if sync else None
 
     def accumulate(self, samples, threads=0, sync=True):
         """Progressive rendering: add `samples` samples per pixel to the accumulation and write the preview to the framebuffer (bit for bit
         what render() gives with samples_per_pixel = accumulated_samples).  Returns the HIP-event kernel time in ms (None when sync=False)."""
-        if sync:
-            ms = ctypes.c_float(0)
-            self._check(self._lib.rtiow_accumulate(self._h, int(samples), int(threads), ctypes.byref(ms)))
-            return ms.value
-        self._check(self._lib.rtiow_accumulate(self._h, int(samples), int(threads), None))
-        return None
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate(self._h, int(samples), int(threads), ms_out))
+        return ms.value if sync else None
 
     def reset_accumulation(self):
         """The next accumulate() starts a new image from the RNG states of init_rng."""
@@ -635,14 +620,10 @@ class Renderer:
         the framebuffer (bit for bit what render() gives that pixel with samples_per_pixel = its count).  Returns (kernel ms or None when
         sync=False, active pixels); 0 active pixels means converged.  The call blocks once to read the active count back."""
         active = ctypes.c_int(0)
-        if sync:
-            ms = ctypes.c_float(0)
-            self._check(self._lib.rtiow_accumulate_adaptive(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
-                                                            ctypes.byref(ms), ctypes.byref(active)))
-            return ms.value, active.value
+        ms, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_accumulate_adaptive(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
-                                                        None, ctypes.byref(active)))
-        return None, active.value
+                                                        ms_out, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
 
     def accumulate_with_variance(self, samples, sync=True):
         """Uniform sampling that keeps the second moment variance() and denoise_variance() need: an adaptive chunk in which every pixel
@@ -654,40 +635,36 @@ class Renderer:
     def adaptive_state(self):
         """(counts, rel_err): each pixel's sample count (int32) and relative standard error of its mean luminance (float32, +inf below
         two samples), local_rows x width."""
-        rows, w = self.local_rows, self.width
-        counts = np.zeros((rows, w), np.int32)
-        err = np.zeros((rows, w), np.float32)
-        self._check(self._lib.rtiow_read_adaptive_state(self._h, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                        err.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows * w))
+        shape = (self.local_rows, self.width)
+        counts, err = np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+        self._check(self._lib.rtiow_read_adaptive_state(self._h, counts.ctypes.data_as(_i32p), err.ctypes.data_as(_f32p), counts.size))
         return counts, err
 
     def read_linear(self):
         """The linear (pre-gamma) mean colour of the accumulation, [local_rows, W, 3]: acc * ((T)1 / (T)n) per pixel, n its count."""
-        out = np.empty((self.local_rows, self.width, 3), self.dtype)
+        out = self._plane(3)
         self._check(self._lib.rtiow_read_linear(self._h, out.ctypes.data if out.size else None, out.nbytes))
         return out
 
     def render_guides(self, sync=True):
         """First-hit guide buffers for the current camera, scene and shard; returns the kernel ms (None when sync=False)."""
-        if sync:
-            ms = ctypes.c_float(0)
-            self._check(self._lib.rtiow_render_guides(self._h, ctypes.byref(ms)))
-            return ms.value
-        self._check(self._lib.rtiow_render_guides(self._h, None))
-        return None
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_guides(self._h, ms_out))
+        return ms.value if sync else None
+
+    def _read_fresh_guides(self, fn, *args):
+        """fn(h, *args) for the two guide reads; RTIOW_E_STATE (stale or never rendered) renders the guides and reads again."""
+        rc = fn(self._h, *args)
+        if rc == -2:
+            self.render_guides()
+            rc = fn(self._h, *args)
+        self._check(rc)
 
     def guides(self):
         """(normal [rows, W, 3], albedo [rows, W, 3], depth [rows, W]) of the first hit of each pixel's centre ray (zeros on a miss);
         renders them first when they are stale (after set_scene, set_camera or set_shard)."""
-        rows, w = self.local_rows, self.width
-        normal = np.empty((rows, w, 3), self.dtype)
-        albedo = np.empty((rows, w, 3), self.dtype)
-        depth = np.empty((rows, w), self.dtype)
-        rc = self._lib.rtiow_read_guides(self._h, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, rows * w)
-        if rc == -2:                                     # RTIOW_E_STATE: stale or never rendered
-            self.render_guides()
-            rc = self._lib.rtiow_read_guides(self._h, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, rows * w)
-        self._check(rc)
+        normal, albedo, depth = self._plane(3), self._plane(3), self._plane()
+        self._read_fresh_guides(self._lib.rtiow_read_guides, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, depth.size)
         return normal, albedo, depth
 
     def set_guide_mode(self, mode, max_bounces=GUIDE_MAX_BOUNCES, max_fuzz=GUIDE_MAX_FUZZ):
@@ -700,17 +677,9 @@ class Renderer:
     def filter_guides(self):
         """(normal [rows, W, 3], albedo [rows, W, 3], depth [rows, W], bounces [rows, W] int32) of the guides the filters read: guides()
         and zeros in GUIDES_FIRST_HIT mode, the end of each pixel's specular chain in GUIDES_SPECULAR mode.  Renders stale guides first."""
-        rows, w = self.local_rows, self.width
-        normal = np.empty((rows, w, 3), self.dtype)
-        albedo = np.empty((rows, w, 3), self.dtype)
-        depth = np.empty((rows, w), self.dtype)
-        bounces = np.empty((rows, w), np.int32)
-        args = (normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, bounces.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), rows * w)
-        rc = self._lib.rtiow_read_filter_guides(self._h, *args)
-        if rc == -2:                                     # RTIOW_E_STATE: stale or never rendered
-            self.render_guides()
-            rc = self._lib.rtiow_read_filter_guides(self._h, *args)
-        self._check(rc)
+        normal, albedo, depth, bounces = self._plane(3), self._plane(3), self._plane(), self._plane(dtype=np.int32)
+        self._read_fresh_guides(self._lib.rtiow_read_filter_guides, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data,
+                                bounces.ctypes.data_as(_i32p), depth.size)
         return normal, albedo, depth, bounces
 
     def denoise(self, levels=DENOISE_LEVELS, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
@@ -718,20 +687,16 @@ class Renderer:
         """Edge-avoiding a-trous filter of the accumulation: returns the gamma-encoded denoised image
         [rows, W, 3] (sync=True), or None after enqueueing the work (sync=False; read_denoised() / denoised_device_ptr() later).
         The framebuffer and the accumulation are untouched.  sigma = float("inf") turns a term off."""
-        if not sync:
-            self._check(self._lib.rtiow_denoise(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
-                                                float(sigma_depth), None))
-            return None
-        ms = ctypes.c_float(0)
+        _, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_denoise(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
-                                            float(sigma_depth), ctypes.byref(ms)))
-        return self.read_denoised()
+                                            float(sigma_depth), ms_out))
+        return self.read_denoised() if sync else None
 
     def variance(self):
         """The estimated variance of each pixel's mean luminance, [local_rows, W] (0 below two samples), from the second moment an
         adaptive accumulation keeps: adaptive_state()'s rel_err is sqrt(variance) / (mean luminance + 1e-3)."""
-        out = np.empty((self.local_rows, self.width), self.dtype)
-        self._check(self._lib.rtiow_read_variance(self._h, out.ctypes.data if out.size else None, out.shape[0] * out.shape[1]))
+        out = self._plane()
+        self._check(self._lib.rtiow_read_variance(self._h, out.ctypes.data if out.size else None, out.size))
         return out
 
     def denoise_variance(self, levels=DENOISE_LEVELS, sigma_variance=DENOISE_SIGMA_VARIANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
@@ -739,9 +704,9 @@ class Renderer:
         """Variance-guided a-trous filter of an adaptive accumulation: denoise() with the colour edge-stop
         of every pixel set by its measured variance(), sigma_variance standard deviations wide, so it follows the noise as samples
         accumulate.  Needs accumulate_adaptive() or accumulate_with_variance() chunks.  Returns and stores its image like denoise()."""
-        ms = None if not sync else ctypes.c_float(0)
+        _, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_denoise_variance(self._h, int(levels), float(sigma_variance), float(sigma_normal), float(sigma_albedo),
-                                                     float(sigma_depth), ctypes.byref(ms) if sync else None))
+                                                     float(sigma_depth), ms_out))
         return self.read_denoised() if sync else None
 
     def history_reset(self):
@@ -754,12 +719,9 @@ class Renderer:
         onto the same surface: relative depth within depth_tol, normals at least normal_cos apart in cosine; a pixel's history
         length is capped at max_history samples (float("inf"): no cap).  Call it after any chunk: nothing is counted twice.
         Returns the number of pixels that carried history (None when sync=False)."""
-        if not sync:
-            self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), None, None))
-            return None
-        ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
-        self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
-        return int(n.value)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_history_update(self._h, float(depth_tol), float(normal_cos), float(max_history), ms_out, n_out))
+        return int(n.value) if sync else None
 
     def history_update_clipped(self, clip_radius=HISTORY_CLIP_RADIUS, clip_gamma=HISTORY_CLIP_GAMMA, depth_tol=HISTORY_DEPTH_TOL,
                                normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
@@ -768,28 +730,22 @@ class Renderer:
         current frame contradicts -- a reflection reprojected as if painted on its mirror -- is pulled to what the frame sees.  History
         lengths, and so history_plan(), are history_update()'s.  clip_radius 1..3; clip_gamma >= 0 (float("inf"): no clamp).
         Returns (pixels that carried history, those of them the clamp changed), or None when sync=False."""
-        args = (float(depth_tol), float(normal_cos), float(max_history), int(clip_radius), float(clip_gamma))
-        if not sync:
-            self._check(self._lib.rtiow_history_update_clipped(self._h, *args, None, None, None))
-            return None
-        ms, n, k = ctypes.c_float(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._check(self._lib.rtiow_history_update_clipped(self._h, *args, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(k)))
-        return int(n.value), int(k.value)
+        (_, ms_out), (n, n_out), (k, k_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_history_update_clipped(self._h, float(depth_tol), float(normal_cos), float(max_history), int(clip_radius),
+                                                           float(clip_gamma), ms_out, n_out, k_out))
+        return (int(n.value), int(k.value)) if sync else None
 
     def history_plan(self, depth_tol=HISTORY_DEPTH_TOL, normal_cos=HISTORY_NORMAL_COS, max_history=HISTORY_MAX, sync=True):
         """The history length every pixel of the current camera will carry: history_update()'s m for the
         same three arguments, before any sample of the frame is traced.  It needs scene and camera only, is what accumulate_budget()
         samples by, and goes stale with the temporal image.  Returns the number of pixels with m > 0 (None when sync=False)."""
-        if not sync:
-            self._check(self._lib.rtiow_history_plan(self._h, float(depth_tol), float(normal_cos), float(max_history), None, None))
-            return None
-        ms, n = ctypes.c_float(0), ctypes.c_uint64(0)
-        self._check(self._lib.rtiow_history_plan(self._h, float(depth_tol), float(normal_cos), float(max_history), ctypes.byref(ms), ctypes.byref(n)))
-        return int(n.value)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_history_plan(self._h, float(depth_tol), float(normal_cos), float(max_history), ms_out, n_out))
+        return int(n.value) if sync else None
 
     def history_plan_lengths(self):
         """The plan of history_plan(), [H, W]: each pixel's history length m in samples."""
-        length = np.empty((self.local_rows, self.width), self.dtype)
+        length = self._plane()
         self._check(self._lib.rtiow_read_history_plan(self._h, length.ctypes.data, length.size))
         return length
 
@@ -800,9 +756,9 @@ class Renderer:
         history_update with the plan's arguments, history_commit.  Alternates freely with accumulate_adaptive().  Returns (kernel ms or
         None when sync=False, active pixels)."""
         active = ctypes.c_int(0)
-        ms = ctypes.c_float(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_accumulate_budget(self._h, int(samples), int(min_samples), float(target), int(max_samples),
-                                                      ctypes.byref(ms) if sync else None, ctypes.byref(active)))
+                                                      ms_out, ctypes.byref(active)))
         return (ms.value if sync else None), active.value
 
     def history_commit(self):
@@ -817,39 +773,34 @@ class Renderer:
         `feedback` in (0, 1] (1: the filtered colour alone); the lengths are kept, so history_plan() predicts as before.  The filter
         steers by the filter guides of the current guide mode; the base keeps the first-hit guides.  Returns the kernel time in ms
         (None when sync=False)."""
-        ms = ctypes.c_float(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_history_commit_filtered(self._h, float(sigma_color), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
-                                                            float(feedback), ctypes.byref(ms) if sync else None))
+                                                            float(feedback), ms_out))
         return ms.value if sync else None
 
     def history_base(self):
         """(rgb [H, W, 3] linear, length [H, W]) of the base the last history_commit() or history_commit_filtered() left."""
-        rgb = np.empty((self.local_rows, self.width, 3), self.dtype)
-        length = np.empty((self.local_rows, self.width), self.dtype)
+        rgb, length = self._plane(3), self._plane()
         self._check(self._lib.rtiow_read_history_base(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
         return rgb, length
 
     def history(self):
         """(rgb [H, W, 3] linear, length [H, W]) of the temporal image: the blended colour and its history length in samples."""
-        rgb = np.empty((self.local_rows, self.width, 3), self.dtype)
-        length = np.empty((self.local_rows, self.width), self.dtype)
+        rgb, length = self._plane(3), self._plane()
         self._check(self._lib.rtiow_read_history(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
         return rgb, length
 
     def history_device_ptr(self):
         """(device address, bytes) of the temporal image, H x W x 4 T: {C.rgb, M}."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_size_t(0)
-        self._check(self._lib.rtiow_history_device_ptr(self._h, ctypes.byref(p), ctypes.byref(n)))
-        return p.value, n.value
+        return self._device_ptr(self._lib.rtiow_history_device_ptr)
 
     def denoise_history(self, levels=DENOISE_LEVELS, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
                         sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_depth=DENOISE_SIGMA_DEPTH, sync=True):
         """denoise() of the temporal image instead of the accumulation: the same filter, level 0 reading history()'s colour.  Returns
         and stores its image like denoise()."""
-        ms = None if not sync else ctypes.c_float(0)
+        _, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_denoise_history(self._h, int(levels), float(sigma_color), float(sigma_normal), float(sigma_albedo),
-                                                    float(sigma_depth), ctypes.byref(ms) if sync else None))
+                                                    float(sigma_depth), ms_out))
         return self.read_denoised() if sync else None
 
     def denoise_history_variance(self, levels=DENOISE_LEVELS, sigma_variance=HISTORY_SIGMA_VARIANCE, sigma_normal=DENOISE_SIGMA_NORMAL,
@@ -859,28 +810,25 @@ class Renderer:
         the spread of the temporal image's luminance over the (2 variance_radius + 1)^2 pixels around the pixel elsewhere (plain
         chunks: everywhere).  Call it after history_update() or history_update_clipped() and before the next chunk.  variance_radius
         1..3.  Returns and stores its image like denoise()."""
-        ms = None if not sync else ctypes.c_float(0)
+        _, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_denoise_history_variance(self._h, int(levels), float(sigma_variance), float(sigma_normal), float(sigma_albedo),
-                                                             float(sigma_depth), int(variance_radius), ctypes.byref(ms) if sync else None))
+                                                             float(sigma_depth), int(variance_radius), ms_out))
         return self.read_denoised() if sync else None
 
     def history_variance(self):
         """The variance plane [H, W] the last denoise_history_variance() filtered the temporal image by."""
-        out = np.empty((self.local_rows, self.width), self.dtype)
+        out = self._plane()
         self._check(self._lib.rtiow_read_history_variance(self._h, out.ctypes.data, out.size))
         return out
 
     def read_denoised(self):
-        out = np.empty((self.local_rows, self.width, 3), self.dtype)
+        out = self._plane(3)
         self._check(self._lib.rtiow_read_denoised(self._h, out.ctypes.data, out.nbytes))
         return out
 
     def denoised_device_ptr(self):
         """(device address, bytes) of the last denoise() output."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_size_t(0)
-        self._check(self._lib.rtiow_denoised_device_ptr(self._h, ctypes.byref(p), ctypes.byref(n)))
-        return p.value, n.value
+        return self._device_ptr(self._lib.rtiow_denoised_device_ptr)
 
     def count_segments(self, threads=8):
         """Untimed render that also counts path segments (hit_world calls)."""
@@ -892,22 +840,19 @@ class Renderer:
         self._check(self._lib.rtiow_bind_framebuffer(self._h, ctypes.c_void_p(int(device_ptr)), nbytes))
 
     def framebuffer_device_ptr(self):
-        p = ctypes.c_void_p()
-        n = ctypes.c_size_t(0)
-        self._check(self._lib.rtiow_framebuffer_device_ptr(self._h, ctypes.byref(p), ctypes.byref(n)))
-        return p.value, n.value
+        return self._device_ptr(self._lib.rtiow_framebuffer_device_ptr)
 
     def read_framebuffer(self):
-        out = np.empty((self.local_rows, self.width, 3), self.dtype)
+        out = self._plane(3)
         if out.size:
             self._check(self._lib.rtiow_read_framebuffer(self._h, out.ctypes.data, out.nbytes))
         return out
 
     def read_levels(self):
         """(levels uint8 [rows, W, 3], nan_channels): the writer's quantisation done on the device (rtiow_read_levels)."""
-        out = np.empty((self.local_rows, self.width, 3), np.uint8)
+        out = self._plane(3, dtype=np.uint8)
         nans = ctypes.c_uint64(0)
-        self._check(self._lib.rtiow_read_levels(self._h, ctypes.c_void_p(out.ctypes.data), ctypes.c_size_t(out.nbytes), ctypes.byref(nans)))
+        self._check(self._lib.rtiow_read_levels(self._h, out.ctypes.data_as(_u8p), out.nbytes, ctypes.byref(nans)))
         return out, int(nans.value)
 
     def _need_debug(self):
@@ -927,7 +872,7 @@ class Renderer:
         self._need_debug()
         n = self.local_rows * self.width
         out = np.zeros((n, 6), np.uint32)
-        self._check(self._lib.rtiow_debug_read_rng(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), out.size))
+        self._check(self._lib.rtiow_debug_read_rng(self._h, out.ctypes.data_as(_u32p), out.size))
         return out
 
     def debug_read_costs(self):
@@ -935,8 +880,7 @@ class Renderer:
         self._need_debug()
         own = np.zeros((self.local_rows, self.width), np.uint32)
         smoothed = np.zeros_like(own)
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self._lib.rtiow_debug_read_costs(self._h, own.ctypes.data_as(u32p), smoothed.ctypes.data_as(u32p), own.size))
+        self._check(self._lib.rtiow_debug_read_costs(self._h, own.ctypes.data_as(_u32p), smoothed.ctypes.data_as(_u32p), own.size))
         return own, smoothed
 
     def debug_read_order(self):
@@ -945,24 +889,23 @@ class Renderer:
         ranking of a render, else None; keys: uint32 [local_rows, W] for a ranking, None for an adaptive list.  Raises RtiowError
         (RTIOW_E_STATE) when nothing has written an order."""
         self._need_debug()
-        i32p, u32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
         raw = np.zeros(12, np.int32)
-        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(i32p), None, 0, None, None, 0))
+        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(_i32p), None, 0, None, None, 0))
         info = dict(zip(ORDER_INFO_FIELDS, (int(v) for v in raw)))
         shape = (info["local_rows"], info["W"])
         order = np.zeros(max(info["total_slots"], 1), np.int32)
         slot_of = np.zeros(shape, np.int32) if info["kind"] == ORDER_RENDER else None
         keys = np.zeros(shape, np.uint32) if info["kind"] in (ORDER_RENDER, ORDER_ACCUMULATE) else None
-        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(i32p), order.ctypes.data_as(i32p), order.size,
-                                                     slot_of.ctypes.data_as(i32p) if slot_of is not None else None,
-                                                     keys.ctypes.data_as(u32p) if keys is not None else None, shape[0] * shape[1]))
+        self._check(self._lib.rtiow_debug_read_order(self._h, raw.ctypes.data_as(_i32p), order.ctypes.data_as(_i32p), order.size,
+                                                     slot_of.ctypes.data_as(_i32p) if slot_of is not None else None,
+                                                     keys.ctypes.data_as(_u32p) if keys is not None else None, shape[0] * shape[1]))
         return info, order[:info["total_slots"]], slot_of, keys
 
     def debug_read_chunk_costs(self):
         """uint32 [local_rows, W]: the path segments each pixel ran in the last accumulate() chunk (the next chunk's ranking smooths them)."""
         self._need_debug()
         out = np.zeros((self.local_rows, self.width), np.uint32)
-        self._check(self._lib.rtiow_debug_read_chunk_costs(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), out.size))
+        self._check(self._lib.rtiow_debug_read_chunk_costs(self._h, out.ctypes.data_as(_u32p), out.size))
         return out
 
     def debug_poison_staged(self):
@@ -974,14 +917,14 @@ class Renderer:
         self._need_debug()
         out = np.zeros((16384, 8), np.uint64)
         n = ctypes.c_int(0)
-        self._check(self._lib.rtiow_debug_timeline(self._h, int(threads), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out.size, ctypes.byref(n)))
+        self._check(self._lib.rtiow_debug_timeline(self._h, int(threads), out.ctypes.data_as(_u64p), out.size, ctypes.byref(n)))
         return out[: n.value]
 
     def debug_pixel_times(self, threads=0):
         """uint32 [rows, W, 4]: per pixel {taken, finished (100 MHz ticks), segments, wave} in the last launch that rendered it."""
         self._need_debug()
         out = np.zeros((self.local_rows, self.width, 4), np.uint32)
-        self._check(self._lib.rtiow_debug_pixel_times(self._h, int(threads), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.c_size_t(out.size)))
+        self._check(self._lib.rtiow_debug_pixel_times(self._h, int(threads), out.ctypes.data_as(_u32p), out.size))
         return out
 
     def debug_ops(self, op, a, b=None, c=None):
@@ -1073,15 +1016,7 @@ class RendererGroup:
         self.close()
 
     def set_scene(self, scene):
-        dt = self.dtype
-        cr = np.ascontiguousarray(scene["center_radius"], dt)
-        af = np.ascontiguousarray(scene["albedo_fuzz"], dt)
-        ri = np.ascontiguousarray(scene["refraction_index"], dt)
-        ty = np.ascontiguousarray(scene["type"], np.int32)
-        va = np.ascontiguousarray(scene["valid"], np.int32) if scene.get("valid") is not None else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._check(self._lib.rtiow_group_set_scene(self._g, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data,
-                                                    ty.ctypes.data_as(i32p), va.ctypes.data_as(i32p) if va is not None else None))
+        self._check(_set_scene(self._lib.rtiow_group_set_scene, self._g, scene, self.dtype))
 
     def set_camera(self, cam):
         want = CameraF64 if self.precision == 64 else CameraF32

@@ -11,7 +11,7 @@ E_BADARG, E_STATE = -1, -2
 INF = float("inf")
 LOOKFROM = (13.0, 2.0, 3.0)
 SLACK = 1.15                 # the quality tests allow 15 % over the values their probes measured
-# (base view, current view) of every plan of tests/test_history_budget.py; tests/test_history_budget_abi.py counts their classes of pixel
+# (base view, current view) of every plan of tests/test_history_budget.py; tests/test_preview_views.py counts their classes of pixel
 # on the CPU
 BUDGET_PAIRS = (("home", "orbit"), ("home", "dolly"), ("home", "roll"), ("orbit", "home"), ("roll", "home"))
 # The base of those tests is committed after the adaptive pattern of sample(): every pixel 4 or 8 samples.  Caps: below both counts
@@ -47,7 +47,7 @@ def budget_moves(rt, prec, W, H, B=10):
     """The home view and the orbit of moves(), with a dolly and a roll of their own.  moves()'s dolly (4 % towards the scene) and roll
     (vup tilted mostly along the view axis) leave under 1 % of these frames without history; a dolly 4 % AWAY from the scene brings a
     border into view and vup tilted across the view axis rolls the frame by about 6 degrees, which leave 4 to 10 %
-    (tests/test_history_budget_abi.py counts them on the CPU)."""
+    (tests/test_preview_views.py counts them on the CPU)."""
     cams = moves(rt, prec, W, H, B)
     cams["dolly"] = rt.camera_look(prec, W, H, 1, B, lookfrom=tuple(1.04 * v for v in LOOKFROM))
     cams["roll"] = rt.camera_look(prec, W, H, 1, B, vup=(0.0, 1.0, 0.1))

@@ -28,11 +28,10 @@ def _plan(native, cr, centre=None):
     cells = np.zeros(4096 * 4, np.uint16)
     direct = np.zeros(n, np.int32)
     hw = np.zeros(n, np.float64)
-    lib.rtiow_debug_grid_plan.restype = ctypes.c_int
-    lib.rtiow_debug_grid_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    rc = lib.rtiow_debug_grid_plan(n, cr.ctypes.data, centre.ctypes.data, ctypes.addressof(dims), ctypes.addressof(params),
-                                   cells.ctypes.data, cells.size, direct.ctypes.data, direct.size, hw.ctypes.data)
+    f64p = ctypes.POINTER(ctypes.c_double)
+    rc = lib.rtiow_debug_grid_plan(n, cr.ctypes.data_as(f64p), centre.ctypes.data_as(f64p), dims, params,
+                                   cells.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), cells.size,
+                                   direct.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), direct.size, hw.ctypes.data_as(f64p))
     assert rc >= 0
     nx, nz, registered, nd = list(dims)
     keys = ("x0", "z0", "cell", "ylo", "yhi", "rfar", "eps", "cmax")

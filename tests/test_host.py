@@ -92,6 +92,57 @@ def test_host_camera_equals_oracle_bitwise(native, oracle):
         native.camera(32, 0, 10, 1, 1)
 
 
+def test_the_placeable_camera_lives_in_the_host_library(native):
+    from raytracingincuda_amd import api
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rtiow_host.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+rtiow_host_camera_look\s*\(", header)
+    assert "rtiow_host_camera_look" in api.HOST_SYMBOLS
+    hsyms = subprocess.run(["nm", "-D", "--defined-only", native.lib_paths()["host"]], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"\bT rtiow_host_camera_look\b", hsyms)
+    assert callable(native.camera_look)
+
+
+# the reference's placement, main.cu:114-121
+LOOKFROM, LOOKAT, VUP, VFOV, DEFOCUS, FOCUS = (13.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, 0.6, 10.0
+
+
+@pytest.mark.parametrize("prec", [32, 64])
+@pytest.mark.parametrize("size", [(320, 192), (1920, 1080)])
+def test_camera_look_at_the_reference_placement_is_camera(native, prec, size):
+    W, H = size
+    want = native.camera(prec, W, H, 100, 50)
+    got = native.camera_look(prec, W, H, 100, 50, LOOKFROM, LOOKAT, VUP, VFOV, DEFOCUS, FOCUS)
+    assert type(got) is type(want)
+    assert bytes(got) == bytes(want)
+    assert bytes(native.camera_look(prec, W, H, 100, 50)) == bytes(want)          # the defaults are that placement
+
+
+@pytest.mark.parametrize("prec", [32, 64])
+def test_camera_look_moves_the_camera(native, prec):
+    W, H = 320, 192
+    base = native.camera(prec, W, H, 4, 10)
+    moved = native.camera_look(prec, W, H, 4, 10, lookfrom=(12.0, 2.5, 4.0))
+    dt = np.float32 if prec == 32 else np.float64
+    assert list(moved.center) == [dt(12.0), dt(2.5), dt(4.0)]
+    assert list(moved.center) != list(base.center) and list(moved.pixel00_loc) != list(base.pixel00_loc)
+    assert (moved.img_width, moved.img_height, moved.samples_per_pixel, moved.max_depth) == (W, H, 4, 10)
+    # the pixel grid is centred on the view axis: pixel00 + ((W-1)/2) du + ((H-1)/2) dv lies on the line lookfrom -> lookat, focus_dist away
+    p00, du, dv, c = (np.array(v[:], np.float64) for v in (moved.pixel00_loc, moved.pixel_delta_u, moved.pixel_delta_v, moved.center))
+    mid = p00 + (W - 1) / 2 * du + (H - 1) / 2 * dv
+    axis = -c / np.linalg.norm(c)
+    assert np.allclose(mid, c + 10.0 * axis, atol=1e-4 if prec == 32 else 1e-12)
+    # a wider field of view widens the pixel steps; a roll turns them
+    wide = native.camera_look(prec, W, H, 4, 10, vfov=40.0)
+    assert np.linalg.norm(np.array(wide.pixel_delta_u[:])) > 1.9 * np.linalg.norm(np.array(base.pixel_delta_u[:]))
+    rolled = native.camera_look(prec, W, H, 4, 10, vup=(0.2, 1.0, 0.0))
+    assert list(rolled.center) == list(base.center) and list(rolled.pixel_delta_u) != list(base.pixel_delta_u)
+    lib = native.load_host_library()
+    v = (ctypes.c_double * 3)(1, 2, 3)
+    assert lib.rtiow_host_camera_look(prec, W, H, 4, 10, None, v, v, 20.0, 0.6, 10.0, ctypes.addressof(moved)) == -1
+    assert lib.rtiow_host_camera_look(16, W, H, 4, 10, v, v, v, 20.0, 0.6, 10.0, ctypes.addressof(moved)) == -1
+    assert lib.rtiow_host_camera_look(prec, 0, H, 4, 10, v, v, v, 20.0, 0.6, 10.0, ctypes.addressof(moved)) == -1
+
+
 def test_ppm_filename_matches_reference_pattern(native):
     # main.cu:349-358 and GlobalDouble main.cu:351
     assert native.ppm_filename(32, 1, 320, 192, 10, 25, 8) == "global_float_scene1_320x192_10samples_25bounces_8threadsPerBlockRow.ppm"
@@ -202,9 +253,7 @@ def test_cli_unknown_option_aborts_like_uncaught_cxxopts(native):
 def test_committed_jump_constant_equals_the_matrix_power(native):
     """xorwow_jump67.inc (A^(2^67), used to skip 67 of the 98 squarings per process) against the same 32
     jump matrices derived from the one-step matrix A: host arithmetic of librtiow_hip.so, no GPU needed."""
-    import ctypes
-    lib = ctypes.CDLL(native.lib_paths()["hip_debug"])
-    lib.rtiow_debug_jump_matrices.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_int]
+    lib = native.load_hip_library(debug=True)
     n = 32 * 160 * 5
     fast, scratch = (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
     assert lib.rtiow_debug_jump_matrices(fast, n, 0) == 32
