@@ -3,11 +3,11 @@
 // a pixel while its count plus that length is below a target.
 // Part of the single gfx950 translation unit rtiow_hip.hip (included there, in this order; internal linkage).
 //
-// history_length_kernel is the `m` of history_reproject_kernel and nothing else of it: the same operations
-// in the same order in T, plain * + - /, floor and fabs, so that m + (T)n is the Mout rtiow_history_update gives later, bit for bit.
-// The arithmetic is written out here a second time on purpose: history_reproject_kernel stays as it is.
+// history_length_kernel is the `m` of history_reproject_kernel and nothing else of it: both call
+// gather_history (history.h), the one statement of that arithmetic, this kernel with COLOUR == false, so that m + (T)n is the Mout
+// rtiow_history_update gives later, bit for bit.  tests/test_frame_edges.py holds the two to each other on every class of pixel.
 #pragma once
-#include "history.h"            // HistoryParams, Vec4
+#include "history.h"            // HistoryParams, Vec4, gather_history
 #include "adaptive.h"           // FrameShape, tile_slot_pixel, MidState records
 
 namespace {
@@ -24,52 +24,7 @@ __global__ void __launch_bounds__(256) history_length_kernel(FrameShape fr, cons
     bool carried = false;
     if (inside) {
         const size_t lp = (size_t)y * fr.W + x;
-        T m = 0;
-        if (hp.have_base) {
-            const Vec4<T> g = cur_nd[lp];
-            const T fi = (T)x, fj = (T)y;
-            const V3<T> D = {((hp.pixel00.x + fi * hp.du.x) + fj * hp.dv.x) - hp.O.x, ((hp.pixel00.y + fi * hp.du.y) + fj * hp.dv.y) - hp.O.y,
-                             ((hp.pixel00.z + fi * hp.du.z) + fj * hp.dv.z) - hp.O.z};
-            const bool hit = g.w > (T)0;
-            V3<T> d = D;
-            if (hit) d = {(hp.O.x + g.w * D.x) - hp.Ob.x, (hp.O.y + g.w * D.y) - hp.Ob.y, (hp.O.z + g.w * D.z) - hp.Ob.z};
-            const T den = (d.x * hp.w.x + d.y * hp.w.y) + d.z * hp.w.z;
-            if (den > (T)0) {
-                const T s = hp.f / den;
-                const T ex = s * d.x - hp.a.x, ey = s * d.y - hp.a.y, ez = s * d.z - hp.a.z;
-                const T u = ((ex * hp.dub.x + ey * hp.dub.y) + ez * hp.dub.z) * hp.iu;
-                const T v = ((ex * hp.dvb.x + ey * hp.dvb.y) + ez * hp.dvb.z) * hp.iv;
-                const T te = den / hp.f;
-                if (u > (T)-1 && u < (T)fr.W && v > (T)-1 && v < (T)fr.local_rows) {      // false for NaN
-                    const T xf = __builtin_elementwise_floor(u), yf = __builtin_elementwise_floor(v);
-                    const int x0 = (int)xf, y0 = (int)yf;
-                    const T fx = u - xf, fy = v - yf;
-                    const T gx = (T)1 - fx, gy = (T)1 - fy;
-                    const T b[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
-                    const T tol = hp.depth_tol * te;
-                    T sl = 0, sb = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
-                        if (qx < 0 || qx >= fr.W || qy < 0 || qy >= fr.local_rows) continue;
-                        const size_t q = (size_t)qy * fr.W + qx;
-                        const T mq = base_hm[4 * q + 3];
-                        const Vec4<T> gq = base_nd[q];
-                        bool ok = mq > (T)0;
-                        if (hit) {
-                            const T dd = gq.w - te;
-                            const T nn = (g.x * gq.x + g.y * gq.y) + g.z * gq.z;
-                            ok = ok && gq.w > (T)0 && __builtin_elementwise_abs(dd) <= tol && nn >= hp.normal_cos;
-                        } else ok = ok && gq.w == (T)0;
-                        if (!ok) continue;
-                        sl = sl + b[k] * mq;
-                        sb = sb + b[k];
-                    }
-                    if (sb > (T)0) m = sl / sb;
-                }
-            }
-            m = m < hp.max_history ? m : hp.max_history;
-        }
+        const T m = gather_history<T, false>(fr, hp, x, y, lp, cur_nd, reinterpret_cast<const Vec4<T>*>(base_hm), base_nd).m;
         carried = m > (T)0;
         out_m[lp] = m;
     }

@@ -8,7 +8,7 @@
 // fabs and a correctly rounded sqrt: no RT_FMA, madd3 or dot3.  -ffp-contract=off keeps the plain operations unfused, so a numpy
 // restatement gives the same bits.
 #pragma once
-#include "history.h"            // HistoryParams, Vec4, linear_colour, FrameShape
+#include "history.h"            // HistoryParams, Vec4, gather_history, blend_history, linear_colour, FrameShape
 
 namespace {
 
@@ -18,7 +18,7 @@ constexpr int CLIP_TILE_SIDE = 16 + 2 * CLIP_MAX_RADIUS;     // 22: 484 entries 
 // One lane per pixel, 16 x 16 pixels per workgroup, as history_reproject_kernel, whose arguments these are but for r, gamma and the
 // second counter.  The workgroup first decodes the (16 + 2r)^2 records of its pixels and their halo once each into LDS as
 // {c.rgb, counts ? 1 : 0}; lanes outside the frame help fill and meet the barrier.  A lane then sums its window from LDS, gathers
-// the history exactly as section 11 does, clamps it and blends.  ctr[0] counts the pixels with m > 0, ctr[1] those of them whose
+// the history with gather_history (history.h), clamps it and blends with blend_history.  ctr[0] counts the pixels with m > 0, ctr[1] those of them whose
 // history the clamp changed: two ballots and at most two LDS atomics per wave, then one global atomic per counter and workgroup.
 // Every wave of the grid adding to the same word of device memory is what history_reproject_kernel's time is made of (DESIGN.md
 // section 4.13), so the workgroup adds its four waves up first.
@@ -67,54 +67,8 @@ __global__ void __launch_bounds__(256) history_clip_kernel(FrameShape fr, const 
                 qx2 = qx2 + e.x * e.x; qy2 = qy2 + e.y * e.y; qz2 = qz2 + e.z * e.z;
                 kT = kT + e.w;
             }
-        // section 11, as history_reproject_kernel states it
-        T hx = 0, hy = 0, hz = 0, m = 0;
-        if (hp.have_base) {
-            const Vec4<T> g = cur_nd[lp];
-            const T fi = (T)x, fj = (T)y;
-            const V3<T> D = {((hp.pixel00.x + fi * hp.du.x) + fj * hp.dv.x) - hp.O.x, ((hp.pixel00.y + fi * hp.du.y) + fj * hp.dv.y) - hp.O.y,
-                             ((hp.pixel00.z + fi * hp.du.z) + fj * hp.dv.z) - hp.O.z};
-            const bool hit = g.w > (T)0;
-            V3<T> d = D;
-            if (hit) d = {(hp.O.x + g.w * D.x) - hp.Ob.x, (hp.O.y + g.w * D.y) - hp.Ob.y, (hp.O.z + g.w * D.z) - hp.Ob.z};
-            const T den = (d.x * hp.w.x + d.y * hp.w.y) + d.z * hp.w.z;
-            if (den > (T)0) {
-                const T s = hp.f / den;
-                const T ex = s * d.x - hp.a.x, ey = s * d.y - hp.a.y, ez = s * d.z - hp.a.z;
-                const T u = ((ex * hp.dub.x + ey * hp.dub.y) + ez * hp.dub.z) * hp.iu;
-                const T v = ((ex * hp.dvb.x + ey * hp.dvb.y) + ez * hp.dvb.z) * hp.iv;
-                const T te = den / hp.f;
-                if (u > (T)-1 && u < (T)fr.W && v > (T)-1 && v < (T)fr.local_rows) {      // false for NaN
-                    const T xf = __builtin_elementwise_floor(u), yf = __builtin_elementwise_floor(v);
-                    const int x0 = (int)xf, y0 = (int)yf;
-                    const T fx = u - xf, fy = v - yf;
-                    const T gx = (T)1 - fx, gy = (T)1 - fy;
-                    const T b[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
-                    const T tol = hp.depth_tol * te;
-                    T sx = 0, sy = 0, sz = 0, sl = 0, sb = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
-                        if (qx < 0 || qx >= fr.W || qy < 0 || qy >= fr.local_rows) continue;
-                        const size_t q = (size_t)qy * fr.W + qx;
-                        const Vec4<T> hq = base_hm[q], gq = base_nd[q];
-                        bool ok = hq.w > (T)0;
-                        if (hit) {
-                            const T dd = gq.w - te;
-                            const T nn = (g.x * gq.x + g.y * gq.y) + g.z * gq.z;
-                            ok = ok && gq.w > (T)0 && __builtin_elementwise_abs(dd) <= tol && nn >= hp.normal_cos;
-                        } else ok = ok && gq.w == (T)0;
-                        if (!ok) continue;
-                        sx = sx + b[k] * hq.x; sy = sy + b[k] * hq.y; sz = sz + b[k] * hq.z;
-                        sl = sl + b[k] * hq.w;
-                        sb = sb + b[k];
-                    }
-                    if (sb > (T)0) { hx = sx / sb; hy = sy / sb; hz = sz / sb; m = sl / sb; }
-                }
-            }
-            m = m < hp.max_history ? m : hp.max_history;
-        }
-        carried = m > (T)0;
+        Gathered<T> h = gather_history<T, true>(fr, hp, x, y, lp, cur_nd, base_hm, base_nd);       // section 11, history.h's one statement
+        carried = h.m > (T)0;
         // the clamp: lo = mu - gamma sd, hi = mu + gamma sd; a comparison with NaN is false and leaves h alone
         if (carried && kT >= (T)2) {
             const T mux = ax / kT, muy = ay / kT, muz = az / kT;
@@ -122,19 +76,12 @@ __global__ void __launch_bounds__(256) history_clip_kernel(FrameShape fr, const 
             vx = vx > (T)0 ? vx : (T)0; vy = vy > (T)0 ? vy : (T)0; vz = vz > (T)0 ? vz : (T)0;
             const T ex = gamma * Real<T>::sqrt(vx), ey = gamma * Real<T>::sqrt(vy), ez = gamma * Real<T>::sqrt(vz);
             const T lox = mux - ex, hix = mux + ex, loy = muy - ey, hiy = muy + ey, loz = muz - ez, hiz = muz + ez;
-            clipped = hx < lox || hx > hix || hy < loy || hy > hiy || hz < loz || hz > hiz;
-            hx = hx < lox ? lox : (hx > hix ? hix : hx);
-            hy = hy < loy ? loy : (hy > hiy ? hiy : hy);
-            hz = hz < loz ? loz : (hz > hiz ? hiz : hz);
+            clipped = h.hx < lox || h.hx > hix || h.hy < loy || h.hy > hiy || h.hz < loz || h.hz > hiz;
+            h.hx = h.hx < lox ? lox : (h.hx > hix ? hix : h.hx);
+            h.hy = h.hy < loy ? loy : (h.hy > hiy ? hiy : h.hy);
+            h.hz = h.hz < loz ? loz : (h.hz > hiz ? hiz : h.hz);
         }
-        const T nT = (T)n, mout = m + nT;
-        Vec4<T> o = {(T)0, (T)0, (T)0, mout};
-        if (mout > (T)0) {
-            const T alpha = nT / mout;
-            o.x = hx + alpha * (c.x - hx); o.y = hy + alpha * (c.y - hy); o.z = hz + alpha * (c.z - hz);
-        }
-        out_cm[lp] = o;
-        out_rgb[3 * lp] = o.x; out_rgb[3 * lp + 1] = o.y; out_rgb[3 * lp + 2] = o.z;
+        blend_history<T>(h, c, n, lp, out_cm, out_rgb);
     }
     const unsigned long long votes = __ballot(carried), cuts = __ballot(clipped);
     if ((threadIdx.x & 63u) == 0) {

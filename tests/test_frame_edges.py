@@ -3,8 +3,8 @@
 The numpy restatements of tests/preview_model.py are run here on the inputs that tests/test_denoise.py, tests/test_denoise_variance.py
 and tests/test_history.py never feed them: frames of one pixel, one column, one row, below and around an 8 x 8 guide tile, a 16 x 16 filter
 workgroup and the sorted schedule's 4096-pixel threshold (section A); cameras inside a sphere, straight above, grazing, far outside the
-grid, facing the sky, and history across moves that put pixels behind the base camera, off its frame, on its edge and onto other
-surfaces (B); accumulations in which nobody, or everybody exactly once, was sampled (C); frames whose hand-out order does not fit
+grid, facing the sky, and history (the update, the plan and the clipped update, which share one gather) across moves that put pixels
+behind the base camera, off its frame, on its edge and onto other surfaces (B); accumulations in which nobody, or everybody exactly once, was sampled (C); frames whose hand-out order does not fit
 row << 16 | column (D).  Everything is compared BIT FOR BIT.  Section E, not marked gpu, shows on the CPU oracle alone that the cases
 reach what they are for.
 
@@ -28,8 +28,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import compact
-from tests.preview_drive import E_BADARG, E_STATE, INF, begin, check_against_err, check_update, move, orbit, run_mixed, state
-from tests.preview_model import as_base, dot, filter_np, gamma, guides_np, reproject, same_bits, update_np, variance_filter_np, vec
+from tests.preview_drive import E_BADARG, E_STATE, INF, begin, check_against_err, check_clipped, check_update, move, orbit, run_mixed, state
+from tests.preview_model import as_base, dot, filter_np, gamma, guides_np, plan_np, reproject, same_bits, update_np, variance_filter_np, vec
 from tests.test_grid_plan import _plan
 
 SIG = (0.5, 0.1, 0.1, 1.0)                                  # denoise: colour, normal, albedo, depth
@@ -251,11 +251,21 @@ def test_history_across_large_moves(rt, prec, frame, adaptive):
         counts = {}
         for name, kw in MOVES.items():
             cam = rt.camera_look(prec, W, H, 1, B, **kw)
+            where = (prec, frame, adaptive, name)
             move(r, cam, 1228)
+            r.history_plan(*default)                        # before the first sample: the plan needs the guides alone
+            plan = r.history_plan_lengths()
             sample(r)
             cur = state(r, adaptive)
-            check_update(r, cam, cur, base, LOOSE, (prec, frame, adaptive, name, LOOSE))
-            counts[name] = check_update(r, cam, cur, base, default, (prec, frame, adaptive, name))[2]
+            assert same_bits(plan, plan_np(cam, cur["N"], cur["t"], base, default)[0]), where
+            check_update(r, cam, cur, base, LOOSE, where + (LOOSE,))
+            counts[name] = check_update(r, cam, cur, base, default, where)[2]
+            plain_rgb, length = r.history()
+            assert same_bits(cur["n"].astype(r.dtype) + plan, length), where
+            # the three kernels share one gather: the clipped update on the same classes of pixel, and gamma = inf, which clamps nothing
+            check_clipped(r, cam, cur, base, default, 1, rt.api.HISTORY_CLIP_GAMMA, where)
+            want = check_clipped(r, cam, cur, base, default, 1, INF, where + (INF,))
+            assert want["clipped"] == 0 and same_bits(r.history()[0], plain_rgb), where
         assert counts["elsewhere"] == 0 and 0 < counts["opposite"] < counts["orbit25"] < counts["near"], counts
 
 
