@@ -510,6 +510,52 @@ int rtiow_history_commit_filtered(rtiow_handle h, double sigma_color, double sig
                                   float* kernel_ms);
 int rtiow_read_history_base(rtiow_handle h, void* rgb /* npix*3 T, linear */, void* length /* npix T */, size_t npix);
 
+/* ---- Edge resolve: silhouette pixels rebuilt from sub-pixel coverage layers.  The guides are one centre ray
+ * per pixel, while the colour of a silhouette pixel is an area mix of two surfaces: such a pixel looks like neither neighbour and the
+ * filters leave it almost alone.  rtiow_render_coverage finds, per pixel, which first-hit spheres share it and in what proportion;
+ * rtiow_resolve_edges rebuilds each mixed pixel of the denoised image from what the filter produced on the pure pixels of its layers
+ * nearby.  Everything in T, left to right as written, plain * + - /, no fused multiply-add.
+ * Coverage layers.  They depend on scene, camera and shard only, like the guides.  G = subsamples_per_side in {2, 4}, S = G G.  For local
+ * pixel (i, jl) with global row j and sub-sample s = a + G b (b outer): o_a = ((T)a + 0.5) / G - 0.5 and o_b likewise (-+0.25 for G = 2;
+ * -+0.375, -+0.125 for G = 4: exact), fx = (T)i + o_a, fy = (T)j + o_b, D = ((pixel00 + fx du) + fy dv) - O with O the camera centre (no
+ * lens sample), (t, k) = hit_world(O, D), and the normal N facing the ray to the letter of rtiow_render_guides.  A miss: k = -1, N = 0,
+ * t = 0.  k counts the spheres rtiow_set_scene kept (invalid slots are not counted).  c_k = the number of sub-samples with that k.  The
+ * distinct k are ordered by c_k descending, the smaller k first on a tie (the sky, -1, is the smallest).  Layer l in {0, 1} holds id_l,
+ * c_l, n_l = (the sum of N over its sub-samples, from 0 in index order) * ((T)1 / (T)c_l) per component, and z_l the same of t.  One
+ * distinct k: the pixel is PURE, with pid = id_0 and layer 1 = {-2, 0, 0, 0}.  Otherwise it is MIXED; a third surface and beyond is
+ * dropped.
+ * rtiow_render_coverage: RTIOW_E_BADARG unless G is 2 or 4; RTIOW_E_STATE before scene and camera are set.  It works on shards (rows are
+ * global).  The layers go stale with rtiow_set_scene, rtiow_set_camera and rtiow_set_shard and survive chunks, resets,
+ * rtiow_set_guide_mode, rtiow_history_update and both commits: their buffers, allocated at first use, never change owners.  Every call
+ * renders, whatever G the layers have.  kernel_ms == NULL: asynchronous on the handle's stream.
+ * rtiow_read_coverage copies planes: ids and counts npix x 2 int32, normal npix x 2 x 3 T, depth npix x 2 T (any pointer may be NULL).
+ * npix != local_rows x width: RTIOW_E_BADARG; stale layers: RTIOW_E_STATE.
+ * The resolve.  rtiow_resolve_edges rewrites, in place, the mixed pixels of the denoised image -- the buffer of rtiow_read_denoised /
+ * rtiow_denoised_device_ptr, whichever of the four filters wrote it last.  g = that image, gamma-encoded as stored; N_q, Z_q = the
+ * FIRST-HIT guides of pixel q in either guide mode; i_n = (T)(1 / sigma_normal^2) and i_z likewise, computed in double and rounded once,
+ * sigma = +inf turning a term off.  Per mixed pixel p = (x, y), r = radius:
+ *   L_p = g_p g_p per channel.  Taps q = p + (dx, dy), dy then dx in -r..r; a tap counts when q is inside the frame and q is pure.
+ *   For layer l = 0 then 1, from 0 over the taps that count with pid_q == id_l: d = N_q - n_l, en = (d.x d.x + d.y d.y) + d.z d.z,
+ *   dz = Z_q - z_l, e = en i_n + (dz dz) i_z, w = 1 / (1 + e), Sx = Sx + w (g_q g_q) per channel, Wt = Wt + w.
+ *   A layer with Wt > 0 is FOUND: F_l = Sx / Wt, a_l = (T)c_l / (T)S.  R = 0, rest = 1; for each found layer in order R = R + a_l F_l,
+ *   rest = rest - a_l; then R = R + rest L_p.
+ *   n_eff = the count behind the filtered image: n_p of rtiow_read_linear when rtiow_denoise(_variance) wrote it, Mout_p of the temporal
+ *   image when rtiow_denoise_history(_variance) did.  beta = (T)prior / ((T)prior + (T)n_eff) and out = L_p + beta (R - L_p); prior = +inf
+ *   is decided on the host: out = R.  Stored: out > 0 ? sqrt(out) : 0.
+ * A pure pixel keeps its stored bits, and so does a mixed pixel with no found layer.  The kernel reads only pure pixels and its own pixel
+ * and writes only mixed pixels, so in place is race-free and deterministic.  *resolved_pixels (may be NULL) = the pixels rewritten.
+ * Stale layers are rendered first, inside kernel_ms, with the G of the last rtiow_render_coverage, or 4 if there was none; so are stale
+ * guides.  kernel_ms == NULL and resolved_pixels == NULL: asynchronous on the handle's stream.
+ * RTIOW_E_BADARG: radius outside 1..3, a sigma <= 0 or NaN, prior <= 0 or NaN.  RTIOW_E_STATE: no denoised image; an image already
+ * resolved (a second pass would blend twice: filter again); a sharded handle; the temporal image stale when the denoised image came from
+ * it (resolve before rtiow_history_commit); a chunk or a reset of the accumulation since the filter ran.  A failing call leaves the
+ * handle as it was.  The call touches nothing but the denoised buffer: framebuffer, accumulation, counts and errors, guides, temporal
+ * image, base, plan, the bits of the next chunk.  Not available on groups. */
+int rtiow_render_coverage(rtiow_handle h, int subsamples_per_side, float* kernel_ms);
+int rtiow_read_coverage(rtiow_handle h, int32_t* ids /* npix*2 */, int32_t* counts /* npix*2 */, void* normal /* npix*2*3 T */, void* depth /* npix*2 T */,
+                        size_t npix);
+int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double sigma_depth, double prior, float* kernel_ms, uint64_t* resolved_pixels);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -139,6 +139,9 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_read_history_variance": (_H, _vp, _size),
     "rtiow_history_commit_filtered": (_H, _dbl, _dbl, _dbl, _dbl, _dbl, _f32p),
     "rtiow_read_history_base": (_H, _vp, _vp, _size),
+    "rtiow_render_coverage": (_H, _int, _f32p),
+    "rtiow_read_coverage": (_H, _i32p, _i32p, _vp, _vp, _size),
+    "rtiow_resolve_edges": (_H, _int, _dbl, _dbl, _dbl, _f32p, _u64p),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -439,6 +442,16 @@ HISTORY_SIGMA_VARIANCE = 2.0
 # does not pay yet, and history_commit() stays the commit the documents recommend.
 HISTORY_FEEDBACK_SIGMA_COLOR = 0.05
 HISTORY_FEEDBACK = 1.0
+# Renderer.render_coverage / resolve_edges defaults: the best of scripts/edge_resolve_probe.py --sweep, i.e. the smallest worst case over
+# 4, 16 and 64 samples and scenes 1 and 3 of the whole-frame MSE of the resolved denoise() over plain denoise()'s, at 320 x 180 against
+# 1024 samples, first of equals in grid order (profiles/edge_resolve/edge_resolve_probe.json).  At these the
+# ratio is 0.85 to 0.87 at 4 samples, 0.88 to 0.90 at 16 and 0.92 to 0.94 at 64.  The 4 x 4 lattice is better at 4 samples alone (0.82 to
+# 0.84 with the same radius, sigmas and prior) for about three times the render_coverage time.
+COVERAGE_GRID = 2
+EDGE_RADIUS = 1
+EDGE_SIGMA_NORMAL = 0.1
+EDGE_SIGMA_DEPTH = 0.1
+EDGE_PRIOR = 32.0
 # The filter guides' chain (Renderer.set_guide_mode, GUIDES_SPECULAR): the cap on specular bounces and the largest fuzz a metal may have
 # to count as a mirror.  From the sweep of scripts/specular_guides_probe.py (profiles/specular_guides/specular_guides_probe.json; DESIGN.md
 # section 4.11): the setting with the smallest worse-of-two-scenes MSE over the specular pixels at 16 samples.  No setting beat the
@@ -783,6 +796,44 @@ class Renderer:
         rgb, length = self._plane(3), self._plane()
         self._check(self._lib.rtiow_read_history_base(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
         return rgb, length
+
+    def render_coverage(self, subsamples_per_side=COVERAGE_GRID, sync=True):
+        """Sub-pixel coverage layers for the current camera, scene and shard: which first-hit spheres share
+        each pixel, from subsamples_per_side^2 (2 or 4 a side) primary rays on a lattice inside it.  Returns the kernel ms (None when
+        sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_coverage(self._h, int(subsamples_per_side), ms_out))
+        self._coverage_grid = int(subsamples_per_side)
+        return ms.value if sync else None
+
+    def coverage(self):
+        """(ids [rows, W, 2] int32, counts [rows, W, 2] int32, normal [rows, W, 2, 3], depth [rows, W, 2]) of the two coverage layers of
+        each pixel: sphere index (-1: the sky; -2: no second layer, the pixel is pure), sub-samples covered, their mean normal and hit
+        distance.  Renders them first, at the subsamples_per_side of the last render_coverage() (COVERAGE_GRID before any), when they
+        are stale (after set_scene, set_camera or set_shard)."""
+        ids, counts, normal, depth = self._plane(2, dtype=np.int32), self._plane(2, dtype=np.int32), self._plane(2, 3), self._plane(2)
+        args = (ids.ctypes.data_as(_i32p), counts.ctypes.data_as(_i32p), normal.ctypes.data, depth.ctypes.data, ids.size // 2)
+        if self._coverage_is_stale():
+            self.render_coverage(getattr(self, "_coverage_grid", COVERAGE_GRID))
+        self._check(self._lib.rtiow_read_coverage(self._h, *args))
+        return ids, counts, normal, depth
+
+    def _coverage_is_stale(self):
+        return self._lib.rtiow_read_coverage(self._h, None, None, None, None, self.local_rows * self.width) == -2
+
+    def resolve_edges(self, radius=EDGE_RADIUS, sigma_normal=EDGE_SIGMA_NORMAL, sigma_depth=EDGE_SIGMA_DEPTH, prior=EDGE_PRIOR, sync=True):
+        """Rebuild the silhouette pixels of the denoised image in place: every pixel that two first-hit
+        spheres share (render_coverage) becomes the coverage-weighted sum of what the filter produced on the pure pixels of each of its
+        layers within `radius` (1..3), weighted by first-hit normal and depth (float("inf") turns a term off), blended with its own
+        filtered value by prior / (prior + the samples behind it) (float("inf"): the rebuilt colour alone).  Call it once after denoise(),
+        denoise_variance(), denoise_history() or denoise_history_variance() and read the result with read_denoised(); before
+        history_commit() when the filter read the temporal image.  Stale layers are rendered first, at the subsamples_per_side of the
+        last render_coverage() (COVERAGE_GRID before any).  Returns the number of pixels rewritten (None when sync=False)."""
+        if self._coverage_is_stale():
+            self.render_coverage(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_resolve_edges(self._h, int(radius), float(sigma_normal), float(sigma_depth), float(prior), ms_out, n_out))
+        return int(n.value) if sync else None
 
     def history(self):
         """(rgb [H, W, 3] linear, length [H, W]) of the temporal image: the blended colour and its history length in samples."""

@@ -138,6 +138,11 @@ struct rtiow_handle_s {
     // length m every pixel of the current camera will carry, 1 T per pixel, and its count of pixels with m > 0
     DeviceBuffer<> plan_m;
     DeviceBuffer<unsigned> plan_ctr;
+    // edge resolve (rtiow_render_coverage / rtiow_resolve_edges), allocated at first use: the coverage layers of every local pixel --
+    // {id_0, id_1, c_0, c_1} as four int32 and {n_l, z_l}, 4 T, for l = 0, 1 -- and the count of pixels the last resolve rewrote.  The
+    // buffers never change owners.
+    DeviceBuffer<> cov_ic, cov_nz;
+    DeviceBuffer<unsigned> edge_ctr;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "scene_tables.h"
@@ -16,6 +16,7 @@
 #include "../device/history_clip.h"
 #include "../device/history_budget.h"
 #include "../device/temporal_noise.h"
+#include "../device/edge_resolve.h"
 
 namespace {
 
@@ -511,6 +512,26 @@ int launch_guides(rtiow_handle_s* h) {
     return 0;
 }
 
+// The coverage layers of every local pixel (rtiow_render_coverage) into h->cov_ic / h->cov_nz: coverage_kernel on the layout and grid of
+// launch_guides, with `grid` sub-samples per side (2 or 4: the caller has checked).
+template <class T>
+int launch_coverage(rtiow_handle_s* h, int grid) {
+    Launch<T> L{make_params<T>(h)};
+    const int threads = 256;
+    int rc = layout_lds<T>(h, L, threads, false, false);
+    if (rc) return rc;
+    const size_t npix = local_pixels(h);
+    HIP_TRY(h, h->cov_ic.ensure(npix * sizeof(int4)));
+    HIP_TRY(h, h->cov_nz.ensure(npix * 2 * sizeof(Vec4<T>)));
+    const auto k = by_source(L.lds_source, [](auto src) { return coverage_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, L.lds));
+    const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
+    hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, grid, h->cov_ic.as<int4>(), h->cov_nz.as<Vec4<T>>());
+    HIP_TRY(h, hipGetLastError());
+    on_coverage_rendered(h->preview, grid);
+    return 0;
+}
+
 // The grid of the kernels that give every 16 x 16 pixels of the local frame a workgroup (the filters, the history, the plan).
 inline dim3 frame_grid(int W, int rows) { return dim3((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16)); }
 
@@ -559,7 +580,7 @@ int launch_denoise(rtiow_handle_s* h, int levels, const double inv2[4], bool fro
                            counts, n_uniform, cin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
-    on_denoised(h->preview);
+    on_denoised(h->preview, from_history ? DENOISED_FROM_TEMPORAL : DENOISED_FROM_ACCUMULATION);
     return 0;
 }
 
@@ -644,6 +665,28 @@ int launch_feedback(rtiow_handle_s* h, const double inv2[4], double feedback) {
                        h->hist_cm.as<const Vec4<T>>(), filter_nd(h).as<const Vec4<T>>(), filter_alb(h).as<const Vec4<T>>(),
                        h->hist_base_hm.as<Vec4<T>>());
     HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// edge_resolve_kernel over the denoised image, in place (rtiow_resolve_edges): the coverage layers, the FIRST-HIT guides whatever the guide
+// mode, and the count behind the image -- the history length of the temporal image when the filter read that, else the accumulation's
+// counts.  inv2[2] = 1 / sigma^2 of normal and depth (double), rounded to T here; prior = +inf is decided here: the kernel then stores the
+// rebuilt colour itself.  h->edge_ctr holds the number of pixels rewritten.  The caller has checked state and arguments -- radius in
+// 1..EDGE_MAX_RADIUS -- and made the guides and the layers current.
+template <class T>
+int launch_edge_resolve(rtiow_handle_s* h, int radius, const double inv2[2], double prior) {
+    const int W = img_w(h), rows = h->local_rows;
+    HIP_TRY(h, h->edge_ctr.ensure(sizeof(unsigned)));
+    HIP_TRY(h, hipMemsetAsync(h->edge_ctr, 0, sizeof(unsigned), h->stream));
+    const bool temporal = h->preview.denoised_from == DENOISED_FROM_TEMPORAL;
+    const unsigned char* mid; const int32_t* counts; int n_uniform;
+    accumulation_source(h, mid, counts, n_uniform);
+    const int grid = h->preview.coverage_grid;
+    hipLaunchKernelGGL(edge_resolve_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, radius, grid * grid, (T)inv2[0], (T)inv2[1],
+                       (T)prior, std::isinf(prior) ? 1 : 0, h->cov_ic.as<const int4>(), h->cov_nz.as<const Vec4<T>>(), h->guide_nd.as<const Vec4<T>>(),
+                       temporal ? nullptr : counts, n_uniform, temporal ? h->hist_cm.as<const Vec4<T>>() : nullptr, h->denoised.as<T>(), (unsigned*)h->edge_ctr);
+    HIP_TRY(h, hipGetLastError());
+    on_edges_resolved(h->preview);
     return 0;
 }
 
@@ -739,7 +782,7 @@ int launch_denoise_variance(rtiow_handle_s* h, int levels, double sigma_variance
                            (const int32_t*)h->adapt_counts, cin, vin, filter_nd(h).as<const T>(), filter_alb(h).as<const T>(), cout, vout, last ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
     }
-    on_denoised(h->preview);
+    on_denoised(h->preview, from_history ? DENOISED_FROM_TEMPORAL : DENOISED_FROM_ACCUMULATION);
     return 0;
 }
 

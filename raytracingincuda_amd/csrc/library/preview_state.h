@@ -1,4 +1,4 @@
-// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 16): what the handle holds that is current
+// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 17): what the handle holds that is current
 // (PreviewState), what every event makes current or stale (on_*: one function per event, each stating everything that event touches),
 // what a call needs (need_*: a predicate that carries its refusal) and the argument checks the calls share (check_*).
 // rtiow_hip.hip and launch.h ask here and write none of these fields themselves; nothing here touches the device.
@@ -9,6 +9,7 @@
 
 constexpr int PREVIEW_E_BADARG = -1, PREVIEW_E_STATE = -2;   // RTIOW_E_BADARG, RTIOW_E_STATE (include/rtiow.h); handle.h asserts them equal
 enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // PreviewState::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive / _budget
+enum { DENOISED_FROM_ACCUMULATION = 0, DENOISED_FROM_TEMPORAL = 1 };     // PreviewState::denoised_from: rtiow_denoise(_variance), rtiow_denoise_history(_variance)
 
 struct PreviewState {
     bool scene = false;                           // rtiow_set_scene has uploaded one (the handle's n != 0); a scene never goes away again
@@ -33,6 +34,16 @@ struct PreviewState {
     // history-guided sample budgets.  plan_ok: rtiow_history_plan has written the plan since the last set_* / history reset / commit --
     // it goes stale with the temporal image
     bool plan_ok = false;
+    // edge resolve.  coverage_ok: the coverage layers belong to the current scene, camera and shard;
+    // coverage_grid: the sub-samples per side of the last rtiow_render_coverage, 0 before the first (it survives everything).
+    // denoised_from: which image the filter that wrote the denoised image read (DENOISED_FROM_*), and denoised_gen: acc_gen at that
+    // filter -- the counts behind the image are the accumulation's only while the two agree.  resolved: rtiow_resolve_edges has rewritten
+    // the denoised image since that filter.
+    bool coverage_ok = false;
+    int coverage_grid = 0;
+    int denoised_from = DENOISED_FROM_ACCUMULATION;
+    uint64_t denoised_gen = 0;
+    bool resolved = false;
 };
 
 // ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
@@ -41,8 +52,9 @@ inline void on_accumulation_reset(PreviewState& s) { s.acc_samples = 0; s.acc_mo
 // A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
 inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.denoised_ok = false; }
 // What a new scene, camera or shard has in common: the accumulation, the guides and the denoised image, the temporal image and the
-// history plan are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is of the old frame too.)
-inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; }
+// history plan and the coverage layers are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is
+// of the old frame too.)
+inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; s.coverage_ok = false; }
 // rtiow_set_scene, before the upload: also the history base goes, which a new camera keeps.  The RNG states stay.
 inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; }
 inline void on_scene_uploaded(PreviewState& s) { s.scene = true; }
@@ -57,7 +69,10 @@ inline void on_chunk_begin(PreviewState& s) { ++s.acc_gen; }
 inline void on_plain_chunk(PreviewState& s, int samples) { s.acc_samples += samples; s.acc_mode = ACC_MODE_PLAIN; }
 inline void on_adaptive_chunk(PreviewState& s) { s.acc_mode = ACC_MODE_ADAPTIVE; }
 inline void on_guides_rendered(PreviewState& s) { s.guides_ok = true; }
-inline void on_denoised(PreviewState& s) { s.denoised_ok = true; }
+// Any of the four filters: the image is new, so not resolved, and its counts are those of the accumulation as it stands.
+inline void on_denoised(PreviewState& s, int from = DENOISED_FROM_ACCUMULATION) { s.denoised_ok = true; s.denoised_from = from; s.denoised_gen = s.acc_gen; s.resolved = false; }
+inline void on_coverage_rendered(PreviewState& s, int grid) { s.coverage_ok = true; s.coverage_grid = grid; }
+inline void on_edges_resolved(PreviewState& s) { s.resolved = true; }
 // rtiow_history_update / _clipped: V^0 was of the image this one replaces.
 inline void on_history_updated(PreviewState& s) { s.hist_ok = true; s.hist_var_ok = false; s.hist_gen = s.acc_gen; }
 inline void on_plan_written(PreviewState& s) { s.plan_ok = true; }
@@ -111,6 +126,22 @@ inline Refusal need_base(const PreviewState& s, const char* call) { return refus
 inline Refusal need_plan(const PreviewState& s, const char* call) {
     return refuse_unless(s.have_camera && s.plan_ok, PREVIEW_E_STATE, call, ": no history plan for the current camera (rtiow_history_plan)");
 }
+inline Refusal need_coverage(const PreviewState& s, const char* call) {
+    return refuse_unless(s.have_camera && s.coverage_ok, PREVIEW_E_STATE, call, ": no coverage layers for the current scene, camera and shard (rtiow_render_coverage)");
+}
+// rtiow_resolve_edges: the denoised image is a filter's own (a second pass would blend twice), the temporal image it came from is still
+// there to be read for its lengths, and the accumulation still holds the counts the filter saw.
+inline Refusal need_unresolved(const PreviewState& s, const char* call) { return refuse_unless(!s.resolved, PREVIEW_E_STATE, call, ": the denoised image is already resolved (filter again)"); }
+inline Refusal need_denoised_source(const PreviewState& s, const char* call) {
+    return refuse_unless(s.denoised_from != DENOISED_FROM_TEMPORAL || s.hist_ok, PREVIEW_E_STATE, call,
+                         ": the temporal image the denoised image came from is stale (resolve before rtiow_history_commit)");
+}
+inline Refusal need_denoised_accumulation(const PreviewState& s, const char* call) {
+    return refuse_unless(s.denoised_gen == s.acc_gen, PREVIEW_E_STATE, call, ": a chunk or a reset since the filter that wrote the denoised image (filter again)");
+}
+// The grid the layers would be rendered with when they are stale: the last one asked for, else COVERAGE_DEFAULT_GRID.
+constexpr int COVERAGE_DEFAULT_GRID = 4;
+inline int coverage_grid_or_default(const PreviewState& s) { return s.coverage_grid ? s.coverage_grid : COVERAGE_DEFAULT_GRID; }
 
 // ---- argument checks
 // The filters: levels in 1..8, then sigma[4] (colour or variance, normal, albedo, depth) each > 0; inv2[k] = 1 / sigma[k]^2.  A call
@@ -130,4 +161,16 @@ inline Refusal check_history_tolerances(const char* call, double depth_tol, doub
 // clip_radius and variance_radius (`name`) in 1..max_radius, which the kernel's LDS tile is sized for; rest: what else the text asks for.
 inline Refusal check_radius(const char* call, const char* name, int radius, int max_radius, bool rest_ok = true, const char* rest = "") {
     return refuse_unless(radius >= 1 && radius <= max_radius && rest_ok, PREVIEW_E_BADARG, call, std::string(": need ") + name + " in 1.." + std::to_string(max_radius) + rest);
+}
+inline Refusal check_coverage_grid(const char* call, int subsamples_per_side) {
+    return refuse_unless(subsamples_per_side == 2 || subsamples_per_side == 4, PREVIEW_E_BADARG, call, ": subsamples_per_side must be 2 or 4");
+}
+// rtiow_resolve_edges: radius in 1..max_radius, sigma[2] (normal, depth) each > 0 with inv2[k] = 1 / sigma[k]^2, prior > 0.
+inline Refusal check_edge_resolve(const char* call, int radius, int max_radius, const double (&sigma)[2], double prior, double (&inv2)[2]) {
+    if (Refusal r = check_radius(call, "radius", radius, max_radius); r.code) return r;
+    for (int k = 0; k < 2; ++k) {
+        if (!(sigma[k] > 0)) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": every sigma must be > 0 (+inf turns its term off)"};
+        inv2[k] = 1.0 / (sigma[k] * sigma[k]);
+    }
+    return refuse_unless(prior > 0, PREVIEW_E_BADARG, call, ": need prior > 0 (+inf: the rebuilt colour alone)");
 }

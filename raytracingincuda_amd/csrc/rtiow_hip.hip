@@ -69,6 +69,7 @@
 #include "device/history_budget.h"
 #include "device/temporal_noise.h"
 #include "device/guide_chain.h"
+#include "device/edge_resolve.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -845,6 +846,59 @@ int rtiow_read_history_variance(rtiow_handle h, void* var, size_t npix) {
     const size_t want = local_pixels(h);
     if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_history_variance: npix must be height x width");
     return copy_out(h, var, h->hist_var, want * elem_size(h));
+}
+
+// ---- Edge resolve
+int rtiow_render_coverage(rtiow_handle h, int subsamples_per_side, float* kernel_ms) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    PREVIEW_TRY(h, check_coverage_grid("rtiow_render_coverage", subsamples_per_side));
+    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_render_coverage"));
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->local_rows == 0) { on_coverage_rendered(h->preview, subsamples_per_side); return 0; }
+    int rc = timed_begin(h, kernel_ms);
+    if (rc) return rc;
+    if ((rc = by_precision(h, [&](auto t) { return launch_coverage<decltype(t)>(h, subsamples_per_side); }))) return rc;
+    return timed_end(h, kernel_ms);
+}
+
+int rtiow_read_coverage(rtiow_handle h, int32_t* ids, int32_t* counts, void* normal, void* depth, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, need_coverage(h->preview, "rtiow_read_coverage"));
+    const size_t want = local_pixels(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_coverage: npix must be local_rows x width");
+    if (ids || counts) {
+        std::vector<int32_t> host(want * 4);                 // {id_0, id_1, c_0, c_1} per pixel
+        if (int rc = copy_out(h, host.data(), h->cov_ic, host.size() * sizeof(int32_t))) return rc;
+        for (size_t k = 0; k < want; ++k) {
+            if (ids) { ids[2 * k] = host[4 * k]; ids[2 * k + 1] = host[4 * k + 1]; }
+            if (counts) { counts[2 * k] = host[4 * k + 2]; counts[2 * k + 1] = host[4 * k + 3]; }
+        }
+    }
+    return read_planes(h, h->cov_nz, 2 * want, normal, depth);   // {n_l, z_l}: two 4-T vectors per pixel
+}
+
+int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double sigma_depth, double prior, float* kernel_ms, uint64_t* resolved_pixels) {
+    if (!h) return RTIOW_E_BADARG;
+    if (kernel_ms) *kernel_ms = 0;
+    if (resolved_pixels) *resolved_pixels = 0;
+    double inv2[2];
+    PREVIEW_TRY(h, check_edge_resolve("rtiow_resolve_edges", radius, EDGE_MAX_RADIUS, {sigma_normal, sigma_depth}, prior, inv2));
+    PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_resolve_edges", true));
+    PREVIEW_TRY(h, need_denoised(h->preview, "rtiow_resolve_edges"));
+    PREVIEW_TRY(h, need_unresolved(h->preview, "rtiow_resolve_edges"));
+    PREVIEW_TRY(h, need_denoised_source(h->preview, "rtiow_resolve_edges"));
+    PREVIEW_TRY(h, need_denoised_accumulation(h->preview, "rtiow_resolve_edges"));
+    const int grid = coverage_grid_or_default(h->preview);
+    auto pass = [&](auto t) {                                // stale layers first, like run_pass's stale guides: inside kernel_ms
+        using T = decltype(t);
+        if (!h->preview.coverage_ok) {
+            if (int rc = launch_coverage<T>(h, grid)) return rc;
+        }
+        return launch_edge_resolve<T>(h, radius, inv2, prior);
+    };
+    if (int rc = run_pass(h, kernel_ms, pass)) return rc;
+    return read_counters(h, h->edge_ctr, resolved_pixels);
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {
