@@ -556,6 +556,37 @@ int rtiow_read_coverage(rtiow_handle h, int32_t* ids /* npix*2 */, int32_t* coun
                         size_t npix);
 int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double sigma_depth, double prior, float* kernel_ms, uint64_t* resolved_pixels);
 
+/* ---- Lens-sampled filter guides.  The guides above are traced through a pinhole, while the image the filters
+ * work on is rendered through the camera's lens: where the circle of confusion spans pixels the colour is a smooth mix of what the
+ * aperture sees and the guides still show one hard edge.  With this knob on, the FILTER guides -- what rtiow_denoise,
+ * rtiow_denoise_variance, rtiow_denoise_history, rtiow_denoise_history_variance and rtiow_history_commit_filtered steer by and
+ * rtiow_read_filter_guides reads -- are the mean of the guide values over S = G G rays from a fixed lattice of points on the defocus
+ * disk through the pixel centre on the focus plane: the rays rtiow_render draws, without their randomness.
+ * Everything in T, left to right as written, plain * + - / and a correctly rounded sqrt, no fused multiply-add.  Local pixel (i, jl) with
+ * global row j, G = samples_per_side, lens sample s = a + G b (b outer), a, b in 0..G-1:
+ *   o_a = (T)(2a + 1) / (T)G - 1 and o_b likewise (-+0.5 for G = 2; -+0.75, -+0.25 for G = 4: exact).
+ *   kappa = (T)1 for G = 2, (T)0.8944271909999159 for G = 4 (sqrt(0.8): the lattice's second moment per axis is 1/4, the uniform unit
+ *   disk's, and every point lies inside the disk).  lx = kappa o_a, ly = kappa o_b.
+ *   O_s = (O + lx U) + ly V per component, O the camera centre, U, V = defocus_disk_u, defocus_disk_v as the camera struct holds them.
+ *   ps = (pixel00 + (T)i du) + (T)j dv, the ray target of rtiow_render_guides.  D_s = ps - O_s.
+ *   (normal'_s, albedo'_s, depth'_s, b_s) = the chain of rtiow_set_guide_mode's block above started from (O_s, D_s), with the handle's
+ *   max_fuzz and max_bounces in RTIOW_GUIDES_SPECULAR; in RTIOW_GUIDES_FIRST_HIT with max_bounces = 0, i.e. ended at its first hit:
+ *   rtiow_render_guides' values to the letter (normal facing the ray, albedo {r,g,b} or {1,1,1} for a dielectric, depth t, 0 on a miss).
+ *   From 0 in s order, per component: Ns = Ns + normal'_s, As = As + albedo'_s, Zs = Zs + depth'_s.  q = (T)1 / (T)S (exact).
+ *   normal = Ns q, albedo = As q, depth = Zs q, bounces = the largest b_s.  The normal is not renormalised: a blurred normal is shorter,
+ *   and that is the information.  A ray that misses adds zeros.
+ * rtiow_set_guide_lens(h, G): G = 0 (off, the default of a new handle), 2 or 4; anything else, or a NULL handle: RTIOW_E_BADARG.  A knob
+ * like rtiow_set_guide_mode and orthogonal to it: it survives rtiow_set_scene, rtiow_set_camera and rtiow_set_shard; a call that changes
+ * nothing does nothing; one that changes the value makes the guides (both sets) and the denoised image stale and leaves the accumulation
+ * and its count, the history base, the temporal image, the plan and the coverage layers alone.  The lattice takes effect when guides are
+ * rendered -- rtiow_render_guides, and the stale guides a filter, an update or a filtered commit renders first -- and only if
+ * (double)defocus_angle > 0, the test rtiow_render makes before it samples the lens: with a pinhole camera the knob is accepted and
+ * inert, the filter guides are the guide mode's bit for bit and no further kernel runs.  In effect, the lens guides live in the second
+ * pair of buffers in either guide mode (allocated at first use; freed again in RTIOW_GUIDES_FIRST_HIT with the knob back at 0) and
+ * rtiow_read_filter_guides returns them.  The first-hit guides, the reprojection, the plan, the coverage layers, rtiow_resolve_edges, the
+ * accumulation and every output with the knob off are untouched.  Not available on groups. */
+int rtiow_set_guide_lens(rtiow_handle h, int samples_per_side /* 0: off (default), 2 or 4 */);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -142,6 +142,7 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_render_coverage": (_H, _int, _f32p),
     "rtiow_read_coverage": (_H, _i32p, _i32p, _vp, _vp, _size),
     "rtiow_resolve_edges": (_H, _int, _dbl, _dbl, _dbl, _f32p, _u64p),
+    "rtiow_set_guide_lens": (_H, _int),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -458,6 +459,9 @@ EDGE_PRIOR = 32.0
 # first-hit guides on both scenes, which is why GUIDES_FIRST_HIT stays the mode a handle starts in.
 GUIDE_MAX_BOUNCES = 1
 GUIDE_MAX_FUZZ = 0.0
+# Renderer.set_guide_lens: the lens points per side the wrapper turns on.  2 x 2 is the lattice the rule of
+# DESIGN.md section 4.18 is stated for; 4 x 4 traces four times the rays.  A handle starts with the lattice off.
+GUIDE_LENS_GRID = 2
 
 
 def _out(ctype, wanted=True):
@@ -687,9 +691,17 @@ class Renderer:
         guides.  A change makes the guides and the denoised image stale; the knob survives set_scene, set_camera and set_shard."""
         self._check(self._lib.rtiow_set_guide_mode(self._h, int(mode), int(max_bounces), float(max_fuzz)))
 
+    def set_guide_lens(self, samples_per_side=GUIDE_LENS_GRID):
+        """Filter guides as the aperture sees them: the mean of the guide mode's values over a fixed
+        samples_per_side x samples_per_side lattice of points on the camera's defocus disk (2 or 4; 0 turns it off, which is how a handle
+        starts).  Inert with a pinhole camera (defocus_angle <= 0).  The first-hit guides, the history and the coverage layers are
+        untouched.  A change makes the guides and the denoised image stale; the knob survives set_scene, set_camera and set_shard."""
+        self._check(self._lib.rtiow_set_guide_lens(self._h, int(samples_per_side)))
+
     def filter_guides(self):
         """(normal [rows, W, 3], albedo [rows, W, 3], depth [rows, W], bounces [rows, W] int32) of the guides the filters read: guides()
-        and zeros in GUIDES_FIRST_HIT mode, the end of each pixel's specular chain in GUIDES_SPECULAR mode.  Renders stale guides first."""
+        and zeros in GUIDES_FIRST_HIT mode, the end of each pixel's specular chain in GUIDES_SPECULAR mode; with set_guide_lens() in
+        effect their mean over the lens lattice and the largest bounce count.  Renders stale guides first."""
         normal, albedo, depth, bounces = self._plane(3), self._plane(3), self._plane(), self._plane(dtype=np.int32)
         self._read_fresh_guides(self._lib.rtiow_read_filter_guides, normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data,
                                 bounces.ctypes.data_as(_i32p), depth.size)

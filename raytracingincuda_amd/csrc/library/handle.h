@@ -118,6 +118,9 @@ struct rtiow_handle_s {
     int guide_max_bounces = 0;
     double guide_max_fuzz = 0;
     DeviceBuffer<> chain_nd, chain_alb;
+    // lens-sampled filter guides (rtiow_set_guide_lens): lens points per side of the lattice, 0 (off), 2 or 4.  While the lattice is in
+    // effect (lens_in_effect) the second pair of buffers holds the lens guides in either guide mode.  The knob survives set_scene / _camera / _shard.
+    int guide_lens = 0;
     // variance-guided denoising (rtiow_read_variance / rtiow_denoise_variance), allocated at first use: the variance plane of the adaptive
     // accumulation (1 T per pixel, rewritten by every call) and the filter's two ping-pong variance planes
     DeviceBuffer<> variance;
@@ -196,10 +199,16 @@ template <class F>
 auto by_precision(const rtiow_handle_s* h, F f) { return h->precision == 32 ? f(float()) : f(double()); }
 
 size_t local_pixels(const rtiow_handle_s* h) { return (size_t)img_w(h) * h->local_rows; }
+// Is the lens lattice of rtiow_set_guide_lens in effect?  The knob is on and the camera has a lens: the test the render kernels make
+// before they sample it.  A function of the knob and the camera alone, and a change of either makes the guides stale, so current guides
+// were rendered under the answer given here.
+bool lens_in_effect(const rtiow_handle_s* h) { return h->guide_lens > 0 && (h->precision == 64 ? (double)h->cam64.defocus_angle : (double)h->cam32.defocus_angle) > 0; }
+// The filter guides live in the second pair of buffers: the specular chain's, or the lens lattice's in either mode.
+bool filter_guides_in_second_pair(const rtiow_handle_s* h) { return h->guide_mode == RTIOW_GUIDES_SPECULAR || lens_in_effect(h); }
 // The guides the filters read (rtiow_denoise, rtiow_denoise_variance, rtiow_denoise_history): the first-hit buffers themselves, or the
-// specular chain's.  The history launch and the commit's swap use guide_nd whatever the mode.
-const DeviceBuffer<>& filter_nd(const rtiow_handle_s* h) { return h->guide_mode == RTIOW_GUIDES_SPECULAR ? h->chain_nd : h->guide_nd; }
-const DeviceBuffer<>& filter_alb(const rtiow_handle_s* h) { return h->guide_mode == RTIOW_GUIDES_SPECULAR ? h->chain_alb : h->guide_alb; }
+// second pair.  The history launch and the commit's swap use guide_nd whatever the mode.
+const DeviceBuffer<>& filter_nd(const rtiow_handle_s* h) { return filter_guides_in_second_pair(h) ? h->chain_nd : h->guide_nd; }
+const DeviceBuffer<>& filter_alb(const rtiow_handle_s* h) { return filter_guides_in_second_pair(h) ? h->chain_alb : h->guide_alb; }
 size_t image_bytes(const rtiow_handle_s* h) { return local_pixels(h) * 3 * elem_size(h); }          // the local image, 3 T per pixel
 
 int ensure_framebuffer(rtiow_handle_s* h) {

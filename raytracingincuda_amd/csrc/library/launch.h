@@ -11,6 +11,7 @@
 #include "../device/cost_sort.h"
 #include "../device/denoise.h"
 #include "../device/guide_chain.h"
+#include "../device/guide_lens.h"
 #include "../device/denoise_variance.h"
 #include "../device/history.h"
 #include "../device/history_clip.h"
@@ -485,6 +486,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
 // First-hit guides of every local pixel (rtiow_render_guides) into h->guide_nd / h->guide_alb: guide_kernel with the scene staged as
 // the render launches stage it (layout_lds of a non-persistent launch: no drain scratch), one 8x8 tile per wave, four waves a workgroup.
 // RTIOW_GUIDES_SPECULAR: guide_chain_kernel follows on the same layout and grid and writes the filter guides to h->chain_nd / h->chain_alb.
+// With the lens lattice in effect (rtiow_set_guide_lens, lens_in_effect) guide_lens_kernel writes them instead, in either guide mode.
 template <class T>
 int launch_guides(rtiow_handle_s* h) {
     Launch<T> L{make_params<T>(h)};
@@ -499,7 +501,16 @@ int launch_guides(rtiow_handle_s* h) {
     const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_nd.as<T>(), h->guide_alb.as<T>());
     HIP_TRY(h, hipGetLastError());
-    if (h->guide_mode == RTIOW_GUIDES_SPECULAR) {
+    if (lens_in_effect(h)) {
+        HIP_TRY(h, h->chain_nd.ensure(npix * 4 * sizeof(T)));
+        HIP_TRY(h, h->chain_alb.ensure(npix * 4 * sizeof(T)));
+        const auto kl = by_source(L.lds_source, [](auto src) { return guide_lens_kernel<T, src>; });
+        HIP_TRY(h, allow_lds(kl, L.lds));
+        const bool chain = h->guide_mode == RTIOW_GUIDES_SPECULAR;   // RTIOW_GUIDES_FIRST_HIT: every chain ends at its first hit
+        hipLaunchKernelGGL(kl, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_lens, chain ? h->guide_max_bounces : 0,
+                           chain ? h->guide_max_fuzz : 0.0, h->chain_nd.as<T>(), h->chain_alb.as<T>());
+        HIP_TRY(h, hipGetLastError());
+    } else if (h->guide_mode == RTIOW_GUIDES_SPECULAR) {
         HIP_TRY(h, h->chain_nd.ensure(npix * 4 * sizeof(T)));
         HIP_TRY(h, h->chain_alb.ensure(npix * 4 * sizeof(T)));
         const auto kc = by_source(L.lds_source, [](auto src) { return guide_chain_kernel<T, src>; });

@@ -49,7 +49,7 @@ struct PreviewState {
 // ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
 // Every reset of the accumulation bumps acc_gen, as every chunk does (need_same_accumulation compares it with the update's).
 inline void on_accumulation_reset(PreviewState& s) { s.acc_samples = 0; s.acc_mode = ACC_MODE_NONE; ++s.acc_gen; }
-// A new guide mode (rtiow_set_guide_mode) makes the guides and the denoised image stale and nothing else.
+// A new guide mode (rtiow_set_guide_mode) or lens lattice (rtiow_set_guide_lens) makes the guides and the denoised image stale and nothing else.
 inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.denoised_ok = false; }
 // What a new scene, camera or shard has in common: the accumulation, the guides and the denoised image, the temporal image and the
 // history plan and the coverage layers are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is

@@ -633,6 +633,7 @@ int rtiow_set_guide_mode(rtiow_handle h, int mode, int max_bounces, double max_f
         if (h->guide_mode == RTIOW_GUIDES_FIRST_HIT) return 0;
         h->guide_mode = RTIOW_GUIDES_FIRST_HIT;
         on_guide_mode_changed(h->preview);
+        if (h->guide_lens != 0) return 0;                // the lens lattice keeps the second pair
         HIP_TRY(h, hipSetDevice(h->device));             // the first-hit buffers are the filter guides again: no second pair is kept
         HIP_TRY(h, h->chain_nd.reset());
         HIP_TRY(h, h->chain_alb.reset());
@@ -648,8 +649,24 @@ int rtiow_set_guide_mode(rtiow_handle h, int mode, int max_bounces, double max_f
 
 int rtiow_read_filter_guides(rtiow_handle h, void* normal, void* albedo, void* depth, int32_t* bounces, size_t npix) {
     if (!h) return RTIOW_E_BADARG;
-    return read_guide_planes(h, "rtiow_read_filter_guides", filter_nd(h), filter_alb(h), h->guide_mode == RTIOW_GUIDES_SPECULAR, normal, albedo, depth,
+    return read_guide_planes(h, "rtiow_read_filter_guides", filter_nd(h), filter_alb(h), filter_guides_in_second_pair(h), normal, albedo, depth,
                              bounces, npix);
+}
+
+// ---- Lens-sampled filter guides
+int rtiow_set_guide_lens(rtiow_handle h, int samples_per_side) {
+    if (!h) return RTIOW_E_BADARG;
+    if (samples_per_side != 0 && samples_per_side != 2 && samples_per_side != 4)
+        return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_guide_lens: samples_per_side must be 0 (off), 2 or 4");
+    if (h->guide_lens == samples_per_side) return 0;
+    h->guide_lens = samples_per_side;
+    on_guide_mode_changed(h->preview);                   // a new lattice is a new kind of filter guides: the same two things go stale
+    if (samples_per_side == 0 && h->guide_mode == RTIOW_GUIDES_FIRST_HIT) {
+        HIP_TRY(h, hipSetDevice(h->device));             // the first-hit buffers are the filter guides again: no second pair is kept
+        HIP_TRY(h, h->chain_nd.reset());
+        HIP_TRY(h, h->chain_alb.reset());
+    }
+    return 0;
 }
 
 int rtiow_denoise(rtiow_handle h, int levels, double sigma_color, double sigma_normal, double sigma_albedo, double sigma_depth, float* kernel_ms) {
