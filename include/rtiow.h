@@ -587,6 +587,49 @@ int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double 
  * accumulation and every output with the knob off are untouched.  Not available on groups. */
 int rtiow_set_guide_lens(rtiow_handle h, int samples_per_side /* 0: off (default), 2 or 4 */);
 
+/* ---- Scene edits that keep the history: reprojection through sphere motion.  rtiow_set_scene empties the
+ * history base, so a viewer that nudges one sphere restarts every pixel from the noise of its few samples although almost every pixel
+ * still shows the surface it showed a frame ago.  rtiow_edit_scene changes the spheres and keeps the base; the updates then carry the
+ * history of a moved sphere along with it.  The base keeps its format and holds no ids.
+ * The snapshot.  rtiow_history_commit and rtiow_history_commit_filtered also keep, on the host, the tables of the scene current at the
+ * commit: per kept sphere k (invalid slots dropped, numbered as rtiow_read_coverage numbers them) {C'_k, r'_k} and the material record
+ * -- type, the 4 T of albedo_fuzz, refraction_index -- as the bits of T.  It goes wherever the base goes: rtiow_history_reset,
+ * rtiow_set_scene and rtiow_set_shard drop it.
+ * rtiow_edit_scene takes rtiow_set_scene's arguments and is rtiow_set_scene in every respect -- tables uploaded, screen and grid tables
+ * rebuilt at the next render, the accumulation back to 0, guides, coverage layers, plan, temporal image and denoised image stale, the
+ * carried hand-out order dropped, the stats' meaning -- except that the history base and its snapshot survive.  With a base, MOTION IS
+ * IN EFFECT from the call until the next commit (which takes a new snapshot), rtiow_history_reset, rtiow_set_scene or rtiow_set_shard,
+ * whether or not any value changed.  Without a base the call is a rtiow_set_scene of the same shape.  Against the snapshot, bits against
+ * bits: moved_k = any of the 4 T of {C_k, r_k} differs; changed_k = the material record differs.
+ * RTIOW_E_BADARG: a NULL handle (-1 before any device work); a null or empty table; an n other than the current scene's; a `valid` that
+ * keeps other slots than the current scene keeps (kept spheres must correspond index for index); a material type outside 0..2.
+ * RTIOW_E_STATE: no scene yet.  A failing call leaves the handle as it was.  Not available on groups.
+ * The motion plane.  While motion is in effect it is rendered wherever the first-hit guides are (rtiow_render_guides, and the stale guides
+ * a filter, an update, a plan or a filtered commit renders first) and goes stale with them.  Everything in T, left to right as written,
+ * plain * + - /, no fused multiply-add.  For local pixel p: (t, k) = hit_world(O, D) of rtiow_render_guides, the same ray and the same
+ * values as the guides' depth.
+ *   a miss:             id = -1, Q = 0, carry = 1.
+ *   a hit, changed_k:   id = k,  Q = 0, carry = 0: a surface that changed colour or kind carries nothing.
+ *   a hit, not moved_k: id = k,  Q = O + t D per component, carry = 1: the expression the update forms from the depth, so the same bits.
+ *   a hit, moved_k:     id = k,  P = O + t D, o = (P - C_k) * ((T)1 / r_k) per component (the guides' outward), Q = C'_k + r'_k o per
+ *                       component, carry = 1: the point of the sphere's old surface that this point came from, under translation and
+ *                       scaling about the centre.
+ * rtiow_read_scene_motion copies planes: prev_point npix x 3 T (Q), carry and ids npix int32 (any pointer may be NULL).
+ * npix != local_rows x width: RTIOW_E_BADARG.  RTIOW_E_STATE: motion is not in effect, or the plane is stale.  Rows are global, as in
+ * rtiow_read_guides; a base needs an unsharded handle, so a handle of several ranks never has motion in effect.
+ * The gather through motion.  While motion is in effect rtiow_history_update, rtiow_history_update_clipped and rtiow_history_plan are
+ * their definitions above with exactly two changes at a hit pixel: d = Q_p - O' instead of (O + t_p D) - O', and carry_p == 0 means no
+ * taps (m = 0).  Everything after d is unchanged: den, s, u, v, te, the taps and their tests, the cap, the blend, the clip, the
+ * counters.  The normal test needs no change: translation and scaling about the centre keep the normal of corresponding points.  So:
+ * a pixel whose first hit is the sky or a sphere that neither moved nor changed has the plain call's bits; a pixel that now sees what
+ * the moved sphere used to hide fails the depth test against the base and gets m = 0, so rtiow_accumulate_budget samples it; and the
+ * plan still predicts Mout bit for bit.  With motion not in effect every call is what it was, bit for bit.
+ * Out of scope: rotation (meaningless for uniform spheres), added or removed spheres, pixels that only reflect or refract an edited
+ * sphere (the clip bounds them, as it does for camera motion), motion-aware coverage layers and lens guides. */
+int rtiow_edit_scene(rtiow_handle h, int n, const void* center_radius, const void* albedo_fuzz,
+                     const void* refraction_index, const int32_t* type, const int32_t* valid);
+int rtiow_read_scene_motion(rtiow_handle h, void* prev_point /* npix*3 T */, int32_t* carry /* npix */, int32_t* ids /* npix */, size_t npix);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

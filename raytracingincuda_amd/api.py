@@ -143,6 +143,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_read_coverage": (_H, _i32p, _i32p, _vp, _vp, _size),
     "rtiow_resolve_edges": (_H, _int, _dbl, _dbl, _dbl, _f32p, _u64p),
     "rtiow_set_guide_lens": (_H, _int),
+    "rtiow_edit_scene": (_H, _int, _vp, _vp, _vp, _i32p, _i32p),
+    "rtiow_read_scene_motion": (_H, _vp, _i32p, _i32p, _size),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -547,6 +549,13 @@ class Renderer:
     def set_scene(self, scene):
         self._check(_set_scene(self._lib.rtiow_set_scene, self._h, scene, self.dtype))
 
+    def edit_scene(self, scene):
+        """set_scene() that keeps the history base: the same tables with the same number of slots and the
+        same 'valid' pattern, spheres moved, resized or given another material.  With a base, the updates and the plan that follow carry
+        the history of a moved sphere along with it until the next commit.  The loop of an edited frame: edit_scene, set_camera if it
+        moved, init_rng, history_plan, accumulate_budget ..., history_update_clipped, history_commit."""
+        self._check(_set_scene(self._lib.rtiow_edit_scene, self._h, scene, self.dtype))
+
     def set_camera(self, cam):
         want = CameraF64 if self.precision == 64 else CameraF32
         if not isinstance(cam, want):
@@ -808,6 +817,15 @@ class Renderer:
         rgb, length = self._plane(3), self._plane()
         self._check(self._lib.rtiow_read_history_base(self._h, rgb.ctypes.data, length.ctypes.data, length.size))
         return rgb, length
+
+    def scene_motion(self):
+        """(prev_point [rows, W, 3], carry [rows, W] int32, ids [rows, W] int32) of the motion plane while an edit_scene() is in effect:
+        the point of the scene the base was committed under that each pixel's first hit came from, whether that surface carries history
+        (0: its material changed) and the sphere index (-1: the sky).  Renders stale guides, and the plane with them, first."""
+        prev_point, carry, ids = self._plane(3), self._plane(dtype=np.int32), self._plane(dtype=np.int32)
+        self._read_fresh_guides(self._lib.rtiow_read_scene_motion, prev_point.ctypes.data, carry.ctypes.data_as(_i32p), ids.ctypes.data_as(_i32p),
+                                ids.size)
+        return prev_point, carry, ids
 
     def render_coverage(self, subsamples_per_side=COVERAGE_GRID, sync=True):
         """Sub-pixel coverage layers for the current camera, scene and shard: which first-hit spheres share

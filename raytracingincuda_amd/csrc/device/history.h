@@ -30,22 +30,36 @@ template <class T> using Vec4 = T __attribute__((ext_vector_type(4)));
 // vector per pixel each, so a tap is two vector loads (neighbouring pixels gather neighbouring taps: L2 serves them).  COLOUR == false
 // gathers the length alone: a tap then loads M, the last of the four T of {H.rgb, M}, and the colour sums and quotients are not formed;
 // what is left is operation for operation the `m` of COLOUR == true.  fr and hp by value: they stay the kernel's wave-uniform constants.
+// MOTION == true (device/scene_motion.h) is the gather through an edited scene, with exactly two changes at a
+// hit pixel: d = Q_p - O' with {Q_p, carry_p} = motion[lp], the motion plane's point of the old surface, instead of (O + t_p D) - O'; and
+// carry_p == 0 (a surface that changed colour or kind) takes no taps, m = 0.  Everything after d is shared.  Where the first hit is the
+// sky or a sphere that neither moved nor changed, Q_p has the bits of O + t_p D and carry_p is 1: the bits of MOTION == false.  A pixel
+// that now sees what a moved sphere used to hide fails the depth test against the base as any disocclusion does.  The normal test needs no
+// change: translation and scaling about the centre keep the normal of corresponding points.  MOTION == false never reads `motion`, and
+// its instantiations compile to the code they had before the parameter existed.
 template <class T> struct Gathered { T hx = 0, hy = 0, hz = 0, m = 0; };
 
-template <class T, bool COLOUR>
+template <class T, bool COLOUR, bool MOTION = false>
 __device__ __forceinline__ Gathered<T> gather_history(FrameShape fr, HistoryParams<T> hp, int x, int y, size_t lp, const Vec4<T>* cur_nd,
-                                                      const Vec4<T>* base_hm, const Vec4<T>* base_nd) {
+                                                      const Vec4<T>* base_hm, const Vec4<T>* base_nd, const Vec4<T>* motion = nullptr) {
     Gathered<T> h;
     if (!hp.have_base) return h;
     const Vec4<T> g = cur_nd[lp];
+    Vec4<T> mq = {(T)0, (T)0, (T)0, (T)1};
+    if constexpr (MOTION) mq = motion[lp];
     const T fi = (T)x, fj = (T)y;
     const V3<T> D = {((hp.pixel00.x + fi * hp.du.x) + fj * hp.dv.x) - hp.O.x, ((hp.pixel00.y + fi * hp.du.y) + fj * hp.dv.y) - hp.O.y,
                      ((hp.pixel00.z + fi * hp.du.z) + fj * hp.dv.z) - hp.O.z};
     const bool hit = g.w > (T)0;
     V3<T> d = D;
-    if (hit) d = {(hp.O.x + g.w * D.x) - hp.Ob.x, (hp.O.y + g.w * D.y) - hp.Ob.y, (hp.O.z + g.w * D.z) - hp.Ob.z};
+    if (hit) {
+        if constexpr (MOTION) d = {mq.x - hp.Ob.x, mq.y - hp.Ob.y, mq.z - hp.Ob.z};
+        else d = {(hp.O.x + g.w * D.x) - hp.Ob.x, (hp.O.y + g.w * D.y) - hp.Ob.y, (hp.O.z + g.w * D.z) - hp.Ob.z};
+    }
     const T den = (d.x * hp.w.x + d.y * hp.w.y) + d.z * hp.w.z;
-    if (den > (T)0) {
+    bool taps = den > (T)0;
+    if constexpr (MOTION) taps = taps && !(hit && mq.w == (T)0);
+    if (taps) {
         const T s = hp.f / den;
         const T ex = s * d.x - hp.a.x, ey = s * d.y - hp.a.y, ez = s * d.z - hp.a.z;
         const T u = ((ex * hp.dub.x + ey * hp.dub.y) + ez * hp.dub.z) * hp.iu;

@@ -146,6 +146,16 @@ struct rtiow_handle_s {
     // buffers never change owners.
     DeviceBuffer<> cov_ic, cov_nz;
     DeviceBuffer<unsigned> edge_ctr;
+    // scene edits that keep the history (rtiow_edit_scene).  On the host, as the bits of T and per kept sphere: the tables of the current
+    // scene (scene_geom: {C, r}, 4 T; scene_mat: type as int32, then the 4 T of albedo_fuzz and refraction_index), written by every
+    // upload, and the snapshot of them both commits take (snap_geom, snap_mat), which goes wherever the base goes.  scene_slots and
+    // scene_kept: the n and the kept pattern of the last upload, which an edit must repeat.  On the device, allocated at first use: the
+    // per-sphere table of the motion plane ({C', r'} and the MOTION_* flags, written by rtiow_edit_scene) and the plane itself ({Q, carry}
+    // as 4 T and the id per local pixel, written wherever the guides are while motion is in effect).
+    std::vector<unsigned char> scene_geom, scene_mat, snap_geom, snap_mat, scene_kept;
+    int scene_slots = 0;
+    DeviceBuffer<> motion_snap, motion_qc;
+    DeviceBuffer<int32_t> motion_flags, motion_ids;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

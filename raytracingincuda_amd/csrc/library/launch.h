@@ -487,6 +487,8 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
 // the render launches stage it (layout_lds of a non-persistent launch: no drain scratch), one 8x8 tile per wave, four waves a workgroup.
 // RTIOW_GUIDES_SPECULAR: guide_chain_kernel follows on the same layout and grid and writes the filter guides to h->chain_nd / h->chain_alb.
 // With the lens lattice in effect (rtiow_set_guide_lens, lens_in_effect) guide_lens_kernel writes them instead, in either guide mode.
+// While motion is in effect (rtiow_edit_scene on a handle with a base) surface_motion_kernel follows on the same layout and grid and writes
+// the motion plane to h->motion_qc / h->motion_ids, sized by the current frame; the table it reads is rtiow_edit_scene's.
 template <class T>
 int launch_guides(rtiow_handle_s* h) {
     Launch<T> L{make_params<T>(h)};
@@ -517,6 +519,15 @@ int launch_guides(rtiow_handle_s* h) {
         HIP_TRY(h, allow_lds(kc, L.lds));
         hipLaunchKernelGGL(kc, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_max_bounces, h->guide_max_fuzz,
                            h->chain_nd.as<T>(), h->chain_alb.as<T>());
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (motion_in_effect(h->preview)) {
+        HIP_TRY(h, h->motion_qc.ensure(npix * sizeof(Vec4<T>)));
+        HIP_TRY(h, h->motion_ids.ensure(npix * sizeof(int32_t)));
+        const auto km = by_source(L.lds_source, [](auto src) { return surface_motion_kernel<T, src>; });
+        HIP_TRY(h, allow_lds(km, L.lds));
+        hipLaunchKernelGGL(km, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->motion_snap.as<const Vec4<T>>(),
+                           (const int32_t*)h->motion_flags, h->motion_qc.as<Vec4<T>>(), (int32_t*)h->motion_ids);
         HIP_TRY(h, hipGetLastError());
     }
     on_guides_rendered(h->preview);
@@ -637,6 +648,7 @@ HistoryParams<T> history_params(const rtiow_handle_s* h, double depth_tol, doubl
 // clip_radius > 0 -- history_clip_kernel, the same with the neighbourhood clamp (rtiow_history_update_clipped), which writes the same two
 // images.  h->hist_ctr holds two words: the pixels that carried history and those of them the clamp changed (0 without a clamp).  The caller
 // has checked state and arguments -- clip_radius in 1..CLIP_MAX_RADIUS, which the kernel's LDS tile is sized for -- and made the guides current.
+// While motion is in effect the guides came with the motion plane, and motion_reproject_kernel / motion_clip_kernel gather through it.
 template <class T>
 int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history, int clip_radius = 0, double clip_gamma = 0) {
     const int W = img_w(h), rows = h->local_rows;
@@ -649,7 +661,14 @@ int launch_history(rtiow_handle_s* h, double depth_tol, double normal_cos, doubl
     accumulation_source(h, mid, counts, n_uniform);
     HIP_TRY(h, hipMemsetAsync(h->hist_ctr, 0, 2 * sizeof(unsigned), h->stream));
     const auto guide = h->guide_nd.as<const Vec4<T>>(), base_hm = h->hist_base_hm.as<const Vec4<T>>(), base_nd = h->hist_base_nd.as<const Vec4<T>>();
-    if (clip_radius > 0)
+    const auto motion = h->motion_qc.as<const Vec4<T>>();
+    if (motion_in_effect(h->preview) && clip_radius > 0)
+        hipLaunchKernelGGL(motion_clip_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, clip_radius, (T)clip_gamma, mid, counts,
+                           n_uniform, guide, base_hm, base_nd, motion, h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    else if (motion_in_effect(h->preview))
+        hipLaunchKernelGGL(motion_reproject_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, mid, counts, n_uniform,
+                           guide, base_hm, base_nd, motion, h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
+    else if (clip_radius > 0)
         hipLaunchKernelGGL(history_clip_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, clip_radius, (T)clip_gamma, mid, counts,
                            n_uniform, guide, base_hm, base_nd, h->hist_cm.as<Vec4<T>>(), h->hist_rgb.as<T>(), (unsigned*)h->hist_ctr);
     else
@@ -703,7 +722,7 @@ int launch_edge_resolve(rtiow_handle_s* h, int radius, const double inv2[2], dou
 
 // history_length_kernel over the current guides and the base into h->plan_m (rtiow_history_plan): the m of launch_history for the same
 // tolerances, before any sample of the frame; the count of pixels with m > 0 goes to h->plan_ctr.  The caller has checked state and
-// arguments and made the guides current.
+// arguments and made the guides current.  While motion is in effect: motion_length_kernel, through the motion plane.
 template <class T>
 int launch_history_plan(rtiow_handle_s* h, double depth_tol, double normal_cos, double max_history) {
     const int W = img_w(h), rows = h->local_rows;
@@ -712,8 +731,13 @@ int launch_history_plan(rtiow_handle_s* h, double depth_tol, double normal_cos, 
     HIP_TRY(h, h->plan_ctr.ensure(sizeof(unsigned)));
     const HistoryParams<T> hp = history_params<T>(h, depth_tol, normal_cos, max_history);
     HIP_TRY(h, hipMemsetAsync(h->plan_ctr, 0, sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(history_length_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
-                       h->hist_base_hm.as<const T>(), h->hist_base_nd.as<const Vec4<T>>(), h->plan_m.as<T>(), (unsigned*)h->plan_ctr);
+    if (motion_in_effect(h->preview))
+        hipLaunchKernelGGL(motion_length_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
+                           h->hist_base_hm.as<const T>(), h->hist_base_nd.as<const Vec4<T>>(), h->motion_qc.as<const Vec4<T>>(), h->plan_m.as<T>(),
+                           (unsigned*)h->plan_ctr);
+    else
+        hipLaunchKernelGGL(history_length_kernel<T>, frame_grid(W, rows), dim3(256), 0, h->stream, FrameShape{W, rows}, hp, h->guide_nd.as<const Vec4<T>>(),
+                           h->hist_base_hm.as<const T>(), h->hist_base_nd.as<const Vec4<T>>(), h->plan_m.as<T>(), (unsigned*)h->plan_ctr);
     HIP_TRY(h, hipGetLastError());
     on_plan_written(h->preview);
     return 0;

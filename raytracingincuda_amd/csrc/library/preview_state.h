@@ -1,4 +1,4 @@
-// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 17): what the handle holds that is current
+// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 19): what the handle holds that is current
 // (PreviewState), what every event makes current or stale (on_*: one function per event, each stating everything that event touches),
 // what a call needs (need_*: a predicate that carries its refusal) and the argument checks the calls share (check_*).
 // rtiow_hip.hip and launch.h ask here and write none of these fields themselves; nothing here touches the device.
@@ -44,31 +44,38 @@ struct PreviewState {
     int denoised_from = DENOISED_FROM_ACCUMULATION;
     uint64_t denoised_gen = 0;
     bool resolved = false;
+    // scene edits that keep the history.  scene_edited: rtiow_edit_scene has changed the scene since the commit
+    // that made the base -- motion is in effect; it is cleared wherever the base is made or emptied.  motion_ok: the motion plane belongs to
+    // the current scene, camera and shard; it is written wherever the guides are while motion is in effect and goes stale with them.
+    bool scene_edited = false, motion_ok = false;
 };
 
 // ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
 // Every reset of the accumulation bumps acc_gen, as every chunk does (need_same_accumulation compares it with the update's).
 inline void on_accumulation_reset(PreviewState& s) { s.acc_samples = 0; s.acc_mode = ACC_MODE_NONE; ++s.acc_gen; }
 // A new guide mode (rtiow_set_guide_mode) or lens lattice (rtiow_set_guide_lens) makes the guides and the denoised image stale and nothing else.
-inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.denoised_ok = false; }
+inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.motion_ok = false; s.denoised_ok = false; }
 // What a new scene, camera or shard has in common: the accumulation, the guides and the denoised image, the temporal image and the
 // history plan and the coverage layers are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is
 // of the old frame too.)
 inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; s.coverage_ok = false; }
 // rtiow_set_scene, before the upload: also the history base goes, which a new camera keeps.  The RNG states stay.
-inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; }
+inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; s.scene_edited = false; }
+// rtiow_edit_scene, before the upload: rtiow_set_scene's event without emptying the base; with a base, motion is in effect from here on.
+inline void on_scene_edited(PreviewState& s) { on_frame_changed(s); s.scene_edited = s.hist_base_ok; }
 inline void on_scene_uploaded(PreviewState& s) { s.scene = true; }
 // rtiow_set_camera: a bad image size takes the camera away and leaves everything else; a good one -- the very camera the handle
 // already has is no exception -- also asks for new RNG states.  The base survives.
 inline void on_set_camera(PreviewState& s, bool good_size) { s.have_camera = good_size; if (good_size) { on_frame_changed(s); s.rng_ready = false; } }
-inline void on_set_shard(PreviewState& s, int nranks) { s.nranks = nranks; on_frame_changed(s); s.rng_ready = false; s.hist_base_ok = false; }
+inline void on_set_shard(PreviewState& s, int nranks) { s.nranks = nranks; on_frame_changed(s); s.rng_ready = false; s.hist_base_ok = false; s.scene_edited = false; }
 // rtiow_init_rng resets the accumulation where it starts (on_accumulation_reset) and ends here.
 inline void on_rng_initialised(PreviewState& s) { s.rng_ready = true; }
 // A chunk of either kind, before its launch; then the chunk itself: a plain one counts its samples, the first of a kind fixes the mode.
 inline void on_chunk_begin(PreviewState& s) { ++s.acc_gen; }
 inline void on_plain_chunk(PreviewState& s, int samples) { s.acc_samples += samples; s.acc_mode = ACC_MODE_PLAIN; }
 inline void on_adaptive_chunk(PreviewState& s) { s.acc_mode = ACC_MODE_ADAPTIVE; }
-inline void on_guides_rendered(PreviewState& s) { s.guides_ok = true; }
+// The motion plane is rendered with the guides while motion is in effect, and only then.
+inline void on_guides_rendered(PreviewState& s) { s.guides_ok = true; s.motion_ok = s.scene_edited; }
 // Any of the four filters: the image is new, so not resolved, and its counts are those of the accumulation as it stands.
 inline void on_denoised(PreviewState& s, int from = DENOISED_FROM_ACCUMULATION) { s.denoised_ok = true; s.denoised_from = from; s.denoised_gen = s.acc_gen; s.resolved = false; }
 inline void on_coverage_rendered(PreviewState& s, int grid) { s.coverage_ok = true; s.coverage_grid = grid; }
@@ -77,9 +84,10 @@ inline void on_edges_resolved(PreviewState& s) { s.resolved = true; }
 inline void on_history_updated(PreviewState& s) { s.hist_ok = true; s.hist_var_ok = false; s.hist_gen = s.acc_gen; }
 inline void on_plan_written(PreviewState& s) { s.plan_ok = true; }
 inline void on_temporal_variance_written(PreviewState& s) { s.hist_var_ok = true; }
-inline void on_history_reset(PreviewState& s) { s.hist_base_ok = false; s.hist_ok = false; s.plan_ok = false; }
+inline void on_history_reset(PreviewState& s) { s.hist_base_ok = false; s.hist_ok = false; s.plan_ok = false; s.scene_edited = false; s.motion_ok = false; }
 // Both commits: the temporal image and the guides became the base by changing owners, so what they leave behind is stale.
-inline void on_commit(PreviewState& s) { s.hist_base_ok = true; s.hist_ok = false; s.plan_ok = false; s.guides_ok = false; }
+// The base is of the scene as it stands now: motion is off until the next rtiow_edit_scene.
+inline void on_commit(PreviewState& s) { s.hist_base_ok = true; s.hist_ok = false; s.plan_ok = false; s.guides_ok = false; s.scene_edited = false; s.motion_ok = false; }
 
 // ---- refusals: the code a call returns and the text it leaves in rtiow_last_error_string, `call` first.  code 0: not refused.
 struct Refusal {
@@ -139,6 +147,15 @@ inline Refusal need_denoised_source(const PreviewState& s, const char* call) {
 inline Refusal need_denoised_accumulation(const PreviewState& s, const char* call) {
     return refuse_unless(s.denoised_gen == s.acc_gen, PREVIEW_E_STATE, call, ": a chunk or a reset since the filter that wrote the denoised image (filter again)");
 }
+// Motion is in effect: from an rtiow_edit_scene on a handle with a base until the next commit, history reset, set_scene or set_shard.
+inline bool motion_in_effect(const PreviewState& s) { return s.hist_base_ok && s.scene_edited; }
+// rtiow_edit_scene: a scene to edit.  (Its argument checks compare with the tables the handle holds: check_scene_edit.)
+inline Refusal need_scene_to_edit(const PreviewState& s, const char* call) { return refuse_unless(s.scene, PREVIEW_E_STATE, call, " before rtiow_set_scene"); }
+// rtiow_read_scene_motion: motion in effect and the plane of the current scene, camera and shard.
+inline Refusal need_motion(const PreviewState& s, const char* call) {
+    if (Refusal r = refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)"); r.code) return r;
+    return refuse_unless(s.have_camera && s.guides_ok && s.motion_ok, PREVIEW_E_STATE, call, ": no motion plane for the current scene, camera and shard (rtiow_render_guides)");
+}
 // The grid the layers would be rendered with when they are stale: the last one asked for, else COVERAGE_DEFAULT_GRID.
 constexpr int COVERAGE_DEFAULT_GRID = 4;
 inline int coverage_grid_or_default(const PreviewState& s) { return s.coverage_grid ? s.coverage_grid : COVERAGE_DEFAULT_GRID; }
@@ -164,6 +181,16 @@ inline Refusal check_radius(const char* call, const char* name, int radius, int 
 }
 inline Refusal check_coverage_grid(const char* call, int subsamples_per_side) {
     return refuse_unless(subsamples_per_side == 2 || subsamples_per_side == 4, PREVIEW_E_BADARG, call, ": subsamples_per_side must be 2 or 4");
+}
+// rtiow_edit_scene, in the order it asks: the tables are there (check_scene_tables, rtiow_set_scene's own refusal); a scene to edit
+// (need_scene_to_edit); n is the current scene's and `valid` keeps the slots the current scene keeps (kept[i] != 0; valid == nullptr
+// keeps every slot), so that kept spheres correspond index for index (check_scene_edit).
+inline Refusal check_scene_tables(const char* call, bool tables, int n) { return refuse_unless(tables && n > 0, PREVIEW_E_BADARG, call, ": null or empty table"); }
+inline Refusal check_scene_edit(const char* call, int n, const int32_t* valid, int current_n, const unsigned char* kept) {
+    if (n != current_n) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": n must be the current scene's (rtiow_set_scene changes the shape)"};
+    for (int i = 0; i < n; ++i)
+        if ((!valid || valid[i] != 0) != (kept[i] != 0)) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": valid must keep the slots the current scene keeps"};
+    return Refusal{};
 }
 // rtiow_resolve_edges: radius in 1..max_radius, sigma[2] (normal, depth) each > 0 with inv2[k] = 1 / sigma[k]^2, prior > 0.
 inline Refusal check_edge_resolve(const char* call, int radius, int max_radius, const double (&sigma)[2], double prior, double (&inv2)[2]) {

@@ -45,9 +45,41 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
     HIP_TRY(h, hipMemcpy(h->geom_a, ga.data(), sizeof(T) * 4 * mp, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->shade_tbl, st.data(), sizeof(T) * 12 * m, hipMemcpyHostToDevice));
     h->n = m; h->n_padded = mp;
+    // what rtiow_edit_scene compares and the commits snapshot: the kept spheres' tables as the bits of T, and the kept pattern
+    h->scene_slots = n;
+    h->scene_kept.assign((size_t)n, 0);
+    h->scene_geom.clear(); h->scene_mat.clear();
+    for (int i = 0; i < n; ++i) {
+        if (valid && !valid[i]) continue;
+        h->scene_kept[i] = 1;
+        auto bytes = [](std::vector<unsigned char>& to, const void* from, size_t count) { to.insert(to.end(), (const unsigned char*)from, (const unsigned char*)from + count); };
+        bytes(h->scene_geom, cr + 4 * i, 4 * sizeof(T));
+        bytes(h->scene_mat, type + i, sizeof(int32_t));
+        bytes(h->scene_mat, af + 4 * i, 4 * sizeof(T));
+        bytes(h->scene_mat, ri + i, sizeof(T));
+    }
     on_scene_uploaded(h->preview);
     h->stats.num_spheres = m;
     h->stats.scene_prepare_ms = 0;
+    return 0;
+}
+
+// The per-sphere table of the motion plane (surface_motion_kernel) after an rtiow_edit_scene on a handle with a base: {C'_k, r'_k} of the
+// snapshot, and MOTION_MOVED / MOTION_CHANGED from comparing the current tables with the snapshot, bits against bits.  The caller has
+// checked that the edit kept the shape, so both hold h->n spheres.  The copies are synchronous: the vectors are gone on return.
+template <class T>
+int upload_motion_table(rtiow_handle_s* h) {
+    const size_t m = (size_t)h->n, gs = 4 * sizeof(T), ms = sizeof(int32_t) + 5 * sizeof(T);
+    std::vector<int32_t> flags(m, 0);
+    for (size_t k = 0; k < m; ++k) {
+        if (std::memcmp(h->scene_geom.data() + k * gs, h->snap_geom.data() + k * gs, gs) != 0) flags[k] |= MOTION_MOVED;
+        if (std::memcmp(h->scene_mat.data() + k * ms, h->snap_mat.data() + k * ms, ms) != 0) flags[k] |= MOTION_CHANGED;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));         // a plane of the previous edit may still be reading the table
+    HIP_TRY(h, h->motion_snap.ensure(m * gs));
+    HIP_TRY(h, h->motion_flags.ensure(m * sizeof(int32_t)));
+    HIP_TRY(h, hipMemcpy(h->motion_snap, h->snap_geom.data(), m * gs, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->motion_flags, flags.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
     return 0;
 }
 

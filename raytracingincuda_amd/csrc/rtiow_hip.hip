@@ -70,6 +70,7 @@
 #include "device/temporal_noise.h"
 #include "device/guide_chain.h"
 #include "device/edge_resolve.h"
+#include "device/scene_motion.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -122,6 +123,9 @@ static void release_stream(int device, hipStream_t s) {
     std::lock_guard<std::mutex> lock(g_idle_streams_mu);
     g_idle_streams.emplace_back(device, s);
 }
+
+// The snapshot of the scene the base was committed under goes wherever the base goes (rtiow_history_reset, rtiow_set_scene, rtiow_set_shard).
+void drop_snapshot(rtiow_handle_s* h) { h->snap_geom.clear(); h->snap_mat.clear(); }
 
 // The times a render call on a shard without rows reports.
 void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
@@ -235,10 +239,30 @@ int rtiow_set_scene(rtiow_handle h, int n, const void* center_radius, const void
     if (n <= 0 || !center_radius || !albedo_fuzz || !refraction_index || !type) return fail_arg(h, RTIOW_E_BADARG, "rtiow_set_scene: null or empty table");
     HIP_TRY(h, hipSetDevice(h->device));
     on_set_scene(h->preview);
+    drop_snapshot(h);
     h->carried.clear();                                  // its cost map is of the old frame (so too after a new camera or shard)
     return by_precision(h, [&](auto t) {
         using T = decltype(t);
         return upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid);
+    });
+}
+
+// ---- Scene edits that keep the history
+int rtiow_edit_scene(rtiow_handle h, int n, const void* center_radius, const void* albedo_fuzz,
+                     const void* refraction_index, const int32_t* type, const int32_t* valid) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, check_scene_tables("rtiow_edit_scene", center_radius && albedo_fuzz && refraction_index && type, n));
+    PREVIEW_TRY(h, need_scene_to_edit(h->preview, "rtiow_edit_scene"));
+    PREVIEW_TRY(h, check_scene_edit("rtiow_edit_scene", n, valid, h->scene_slots, h->scene_kept.data()));
+    for (int i = 0; i < n; ++i)                          // upload_scene's own refusal, asked before anything is touched
+        if (h->scene_kept[i] && (type[i] < 0 || type[i] > 2)) return fail_arg(h, RTIOW_E_BADARG, "material type out of range");
+    HIP_TRY(h, hipSetDevice(h->device));
+    on_scene_edited(h->preview);
+    h->carried.clear();                                  // its cost map is of the old frame
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid)) return rc;
+        return motion_in_effect(h->preview) ? upload_motion_table<T>(h) : 0;
     });
 }
 
@@ -265,6 +289,7 @@ int rtiow_set_shard(rtiow_handle h, int rank, int nranks, int strip_rows) {
     h->rank = rank; h->strip_rows = strip_rows;
     if (h->preview.have_camera) { h->local_rows = compute_local_rows(img_h(h), rank, nranks, strip_rows); h->stats.local_rows = h->local_rows; }
     on_set_shard(h->preview, nranks);
+    drop_snapshot(h);
     h->carried.clear();
     return 0;
 }
@@ -722,6 +747,7 @@ int rtiow_history_reset(rtiow_handle h) {
     if (!h) return RTIOW_E_BADARG;
     PREVIEW_TRY(h, need_unsharded(h->preview, "rtiow_history_reset", false));
     on_history_reset(h->preview);
+    drop_snapshot(h);
     return 0;
 }
 
@@ -773,9 +799,11 @@ int rtiow_read_history_plan(rtiow_handle h, void* length, size_t npix) {
 namespace {
 // What both commits end in.  The guides become the base's by changing owners (the work that wrote them is ordered on the stream before
 // whatever reads them next); the buffer they get in exchange holds the old base's, so they go stale, and so does the temporal image.
+// The scene current at the commit is kept beside them, on the host: what a later rtiow_edit_scene compares with.
 void commit_base(rtiow_handle_s* h) {
     std::swap(h->hist_base_nd, h->guide_nd);
     h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
+    h->snap_geom = h->scene_geom; h->snap_mat = h->scene_mat;
     on_commit(h->preview);
 }
 }  // namespace
@@ -916,6 +944,23 @@ int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double 
     };
     if (int rc = run_pass(h, kernel_ms, pass)) return rc;
     return read_counters(h, h->edge_ctr, resolved_pixels);
+}
+
+// ---- The motion plane of an edited scene
+int rtiow_read_scene_motion(rtiow_handle h, void* prev_point, int32_t* carry, int32_t* ids, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, need_motion(h->preview, "rtiow_read_scene_motion"));
+    const size_t want = local_pixels(h), es = elem_size(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_scene_motion: npix must be local_rows x width");
+    if (carry) {
+        std::vector<unsigned char> c(want * es);
+        if (int rc = read_planes(h, h->motion_qc, want, prev_point, c.data())) return rc;
+        for (size_t k = 0; k < want; ++k) {
+            if (es == 4) { float v; std::memcpy(&v, c.data() + k * es, 4); carry[k] = (int32_t)v; }
+            else { double v; std::memcpy(&v, c.data() + k * es, 8); carry[k] = (int32_t)v; }
+        }
+    } else if (int rc = read_planes(h, h->motion_qc, want, prev_point, nullptr)) return rc;
+    return copy_out(h, ids, h->motion_ids, want * sizeof(int32_t));
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {
