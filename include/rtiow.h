@@ -624,11 +624,43 @@ int rtiow_set_guide_lens(rtiow_handle h, int samples_per_side /* 0: off (default
  * a pixel whose first hit is the sky or a sphere that neither moved nor changed has the plain call's bits; a pixel that now sees what
  * the moved sphere used to hide fails the depth test against the base and gets m = 0, so rtiow_accumulate_budget samples it; and the
  * plan still predicts Mout bit for bit.  With motion not in effect every call is what it was, bit for bit.
- * Out of scope: rotation (meaningless for uniform spheres), added or removed spheres, pixels that only reflect or refract an edited
- * sphere (the clip bounds them, as it does for camera motion), motion-aware coverage layers and lens guides. */
+ * Out of scope: rotation (meaningless for uniform spheres), added or removed spheres, motion-aware coverage layers and lens guides.
+ * Pixels that only reflect, refract or are shadowed by an edited sphere: rtiow_set_edit_influence, below. */
 int rtiow_edit_scene(rtiow_handle h, int n, const void* center_radius, const void* albedo_fuzz,
                      const void* refraction_index, const int32_t* type, const int32_t* valid);
 int rtiow_read_scene_motion(rtiow_handle h, void* prev_point /* npix*3 T */, int32_t* carry /* npix */, int32_t* ids /* npix */, size_t npix);
+
+/* ---- Edit influence: shorten the history where a scene edit changes the light.  The motion plane looks at
+ * a pixel's first hit only.  The ground under a moved sphere, a neighbour that took its colour bleed, a mirror that shows it: their first
+ * hit was not edited, they pass every test of the gather and carry a full-length history of the wrong light.  The sky is the only light,
+ * so the irradiance at a point changes by at most the share of its surroundings that the edited spheres occupy, before and after the edit.
+ * rtiow_set_edit_influence records kappa: 0 is off (a handle's default; every call is then what it was, bit for bit), kappa > 0 is on,
+ * +inf drops the history wherever there is any influence at all.  NaN or negative: RTIOW_E_BADARG; a NULL handle: -1.  Allowed in every
+ * state, on shards too; the value survives set_scene / _camera / _shard.  Another value than the handle has makes the motion plane, the
+ * guides it is rendered with, the plan, the temporal image and the denoised image stale; the same value changes nothing.
+ * The edit list.  rtiow_edit_scene with motion in effect keeps, through the kept spheres in ascending k: moved_k (with or without
+ * changed_k): two entries, {C'_k, r'_k} of the snapshot, then {C_k, r_k} of the current scene; changed_k only: one entry, {C_k, r_k};
+ * neither: none.  Each entry has the owner k.
+ * The influence plane.  While motion is in effect and kappa > 0 it is written wherever the motion plane is.  Everything in T, left to
+ * right as written, plain * + - / and sqrt, no fused multiply-add.  For local pixel p with guides' depth t_p, motion plane carry_p, id k_p:
+ *   a miss (depth == 0) or carry_p == 0:  lambda_p = 0
+ *   otherwise:  P = O + t_p D per component (as rtiow_history_update forms it), s = 0, and for every entry e in list order with
+ *               owner_e != k_p:  v = C_e - P, d2 = (v.x v.x + v.y v.y) + v.z v.z, q = (r_e r_e) / d2,
+ *                                omega = q >= 1 ? 1 : 1 - sqrt(1 - q)  (NaN compares false),  s = s + omega;
+ *               lambda_p = s > 0 ? min(1, kappa s) : 0, with kappa rounded once to T.
+ *   fade_p = carry_p == 0 ? 0 : 1 - lambda_p replaces carry_p in the motion plane.
+ * omega is twice the share of the full sphere of directions around P that the entry occupies.  A pixel's own sphere is skipped (its
+ * history is the motion plane's business), sky pixels never fade, an empty list gives lambda = 0 everywhere.
+ * The gathers.  rtiow_history_update, rtiow_history_update_clipped and rtiow_history_plan through the motion plane gain one operation
+ * after the cap: m = m * fade_p.  fade_p == 0 takes no taps, as carry_p == 0 does.  The plan still predicts Mout - n bit for bit, so
+ * rtiow_accumulate_budget samples the faded pixels more, and the clipped update clamps what is left.  rtiow_read_scene_motion answers
+ * carry as (fourth component != 0).
+ * rtiow_read_edit_influence copies lambda, npix T.  npix != local_rows x width: RTIOW_E_BADARG.  RTIOW_E_STATE: motion is not in effect,
+ * kappa == 0 (no plane is made then), or the plane is stale (rtiow_render_guides).  Rows are global, as in rtiow_read_scene_motion.
+ * Out of scope: added or removed spheres, a horizon or cosine term in omega, following the specular chain, fading coverage layers or
+ * lens guides, groups. */
+int rtiow_set_edit_influence(rtiow_handle h, double kappa /* 0: off; > 0: on */);
+int rtiow_read_edit_influence(rtiow_handle h, void* lambda /* npix T */, size_t npix);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

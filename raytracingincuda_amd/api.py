@@ -145,6 +145,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_set_guide_lens": (_H, _int),
     "rtiow_edit_scene": (_H, _int, _vp, _vp, _vp, _i32p, _i32p),
     "rtiow_read_scene_motion": (_H, _vp, _i32p, _i32p, _size),
+    "rtiow_set_edit_influence": (_H, _dbl),
+    "rtiow_read_edit_influence": (_H, _vp, _size),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -464,6 +466,11 @@ GUIDE_MAX_FUZZ = 0.0
 # Renderer.set_guide_lens: the lens points per side the wrapper turns on.  2 x 2 is the lattice the rule of
 # DESIGN.md section 4.18 is stated for; 4 x 4 traces four times the rays.  A handle starts with the lattice off.
 GUIDE_LENS_GRID = 2
+# Renderer.set_edit_influence: the kappa the wrapper turns on.  From the sweep of scripts/edit_influence_probe.py
+# (profiles/edit_influence/edit_influence_probe.json): the kappa with the smallest worst-of-four-walks whole-frame
+# MSE ratio among those within 1.10 x the rays of kappa == 0.  No kappa of the sweep brought that ratio below 1 (0.25: 1.006), which is
+# why a handle starts with kappa == 0, off.
+EDIT_INFLUENCE_KAPPA = 0.25
 
 
 def _out(ctype, wanted=True):
@@ -826,6 +833,21 @@ class Renderer:
         self._read_fresh_guides(self._lib.rtiow_read_scene_motion, prev_point.ctypes.data, carry.ctypes.data_as(_i32p), ids.ctypes.data_as(_i32p),
                                 ids.size)
         return prev_point, carry, ids
+
+    def set_edit_influence(self, kappa=EDIT_INFLUENCE_KAPPA):
+        """Shorten the history where an edit_scene() changes the light: with kappa > 0 every pixel's history
+        length is multiplied by 1 - min(1, kappa * s), s the share of the pixel's surroundings that the edited spheres occupy before and
+        after the edit (edit_influence()); float("inf") drops the history wherever s > 0; 0 turns it off, which is how a handle starts.
+        A change makes the motion plane, the guides, the plan, the temporal image and the denoised image stale; the knob survives
+        set_scene, set_camera and set_shard."""
+        self._check(self._lib.rtiow_set_edit_influence(self._h, float(kappa)))
+
+    def edit_influence(self):
+        """lambda [rows, W] of the influence plane while an edit_scene() is in effect and set_edit_influence() is on: how much of each
+        pixel's history the updates and the plan drop (0: none, 1: all).  Renders stale guides, and the planes with them, first."""
+        lam = self._plane()
+        self._read_fresh_guides(self._lib.rtiow_read_edit_influence, lam.ctypes.data, lam.size)
+        return lam
 
     def render_coverage(self, subsamples_per_side=COVERAGE_GRID, sync=True):
         """Sub-pixel coverage layers for the current camera, scene and shard: which first-hit spheres share

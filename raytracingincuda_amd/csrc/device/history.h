@@ -35,7 +35,9 @@ template <class T> using Vec4 = T __attribute__((ext_vector_type(4)));
 // carry_p == 0 (a surface that changed colour or kind) takes no taps, m = 0.  Everything after d is shared.  Where the first hit is the
 // sky or a sphere that neither moved nor changed, Q_p has the bits of O + t_p D and carry_p is 1: the bits of MOTION == false.  A pixel
 // that now sees what a moved sphere used to hide fails the depth test against the base as any disocclusion does.  The normal test needs no
-// change: translation and scaling about the centre keep the normal of corresponding points.  MOTION == false never reads `motion`, and
+// change: translation and scaling about the centre keep the normal of corresponding points.  After the cap, m = m * w with w the plane's
+// fourth T: carry_p, or with edit influence on (section 20, device/edit_influence.h) fade_p = 1 - lambda_p in [0, 1], which shortens the
+// history where the edit can have changed the pixel's light; w = 1 leaves the bits of m.  MOTION == false never reads `motion`, and
 // its instantiations compile to the code they had before the parameter existed.
 template <class T> struct Gathered { T hx = 0, hy = 0, hz = 0, m = 0; };
 
@@ -100,6 +102,7 @@ __device__ __forceinline__ Gathered<T> gather_history(FrameShape fr, HistoryPara
         }
     }
     h.m = h.m < hp.max_history ? h.m : hp.max_history;
+    if constexpr (MOTION) h.m = h.m * mq.w;                      // section 20: the fade; with w = 1 the product has the bits of m
     return h;
 }
 

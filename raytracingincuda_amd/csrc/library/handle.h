@@ -156,6 +156,14 @@ struct rtiow_handle_s {
     int scene_slots = 0;
     DeviceBuffer<> motion_snap, motion_qc;
     DeviceBuffer<int32_t> motion_flags, motion_ids;
+    // edit influence (rtiow_set_edit_influence): the knob (0: off; preview.influence_on says whether it is > 0; it survives set_scene /
+    // _camera / _shard), the edit list of the last rtiow_edit_scene with motion in effect ({C, r} as 4 T and the owner per entry, written
+    // beside motion_snap / motion_flags; edit_entries may be 0) and the influence plane lambda, 1 T per local pixel, written wherever the
+    // motion plane is while the knob is on.  All allocated at first use.
+    double edit_kappa = 0;
+    int edit_entries = 0;
+    DeviceBuffer<> edit_list, edit_lambda;
+    DeviceBuffer<int32_t> edit_owner;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

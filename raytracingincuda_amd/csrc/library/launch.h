@@ -488,7 +488,9 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
 // RTIOW_GUIDES_SPECULAR: guide_chain_kernel follows on the same layout and grid and writes the filter guides to h->chain_nd / h->chain_alb.
 // With the lens lattice in effect (rtiow_set_guide_lens, lens_in_effect) guide_lens_kernel writes them instead, in either guide mode.
 // While motion is in effect (rtiow_edit_scene on a handle with a base) surface_motion_kernel follows on the same layout and grid and writes
-// the motion plane to h->motion_qc / h->motion_ids, sized by the current frame; the table it reads is rtiow_edit_scene's.
+// the motion plane to h->motion_qc / h->motion_ids, sized by the current frame; the table it reads is rtiow_edit_scene's.  With edit
+// influence on (rtiow_set_edit_influence, kappa > 0) edit_influence_kernel follows it, one lane per pixel in 16 x 16 workgroups: it writes
+// lambda to h->edit_lambda and the fade over the carry of h->motion_qc, from the guides, the ids and rtiow_edit_scene's edit list.
 template <class T>
 int launch_guides(rtiow_handle_s* h) {
     Launch<T> L{make_params<T>(h)};
@@ -529,6 +531,19 @@ int launch_guides(rtiow_handle_s* h) {
         hipLaunchKernelGGL(km, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->motion_snap.as<const Vec4<T>>(),
                            (const int32_t*)h->motion_flags, h->motion_qc.as<Vec4<T>>(), (int32_t*)h->motion_ids);
         HIP_TRY(h, hipGetLastError());
+        if (influence_in_effect(h->preview)) {
+            HIP_TRY(h, h->edit_lambda.ensure(npix * sizeof(T)));
+            const auto& c = camera<T>(h);
+            InfluenceParams<T> ip{};
+            ip.O = L.p.cam.center; ip.pixel00 = L.p.cam.pixel00; ip.du = L.p.cam.du; ip.dv = L.p.cam.dv;
+            ip.kappa = (T)h->edit_kappa;
+            ip.W = c.img_width; ip.local_rows = h->local_rows; ip.strip_rows = h->strip_rows; ip.nranks = h->preview.nranks; ip.rank = h->rank;
+            ip.entries = h->edit_entries;
+            hipLaunchKernelGGL(edit_influence_kernel<T>, dim3((unsigned)((ip.W + 15) / 16), (unsigned)((ip.local_rows + 15) / 16)), dim3(256), 0, h->stream, ip, h->guide_nd.as<const Vec4<T>>(),
+                               (const int32_t*)h->motion_ids, h->edit_list.as<const Vec4<T>>(), (const int32_t*)h->edit_owner, h->motion_qc.as<Vec4<T>>(),
+                               h->edit_lambda.as<T>());
+            HIP_TRY(h, hipGetLastError());
+        }
     }
     on_guides_rendered(h->preview);
     return 0;

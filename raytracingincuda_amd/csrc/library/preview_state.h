@@ -1,4 +1,4 @@
-// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 19): what the handle holds that is current
+// preview_state.h -- the policy of the preview chain (INTEGRATION.md sections 7 to 20): what the handle holds that is current
 // (PreviewState), what every event makes current or stale (on_*: one function per event, each stating everything that event touches),
 // what a call needs (need_*: a predicate that carries its refusal) and the argument checks the calls share (check_*).
 // rtiow_hip.hip and launch.h ask here and write none of these fields themselves; nothing here touches the device.
@@ -48,6 +48,9 @@ struct PreviewState {
     // that made the base -- motion is in effect; it is cleared wherever the base is made or emptied.  motion_ok: the motion plane belongs to
     // the current scene, camera and shard; it is written wherever the guides are while motion is in effect and goes stale with them.
     bool scene_edited = false, motion_ok = false;
+    // edit influence.  influence_on: rtiow_set_edit_influence holds a kappa > 0.  While it does, the influence
+    // plane is written wherever the motion plane is, and the motion plane's fourth T holds the fade: both are current exactly when motion_ok.
+    bool influence_on = false;
 };
 
 // ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
@@ -64,6 +67,10 @@ inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok 
 // rtiow_edit_scene, before the upload: rtiow_set_scene's event without emptying the base; with a base, motion is in effect from here on.
 inline void on_scene_edited(PreviewState& s) { on_frame_changed(s); s.scene_edited = s.hist_base_ok; }
 inline void on_scene_uploaded(PreviewState& s) { s.scene = true; }
+// rtiow_set_edit_influence with another kappa than the handle has (`on`: the new one is > 0): everything that depends on the motion plane
+// is stale -- the plane, the guides it is rendered with, the plan, the temporal image and the denoised image.  The knob itself survives
+// every other event.
+inline void on_edit_influence_changed(PreviewState& s, bool on) { s.influence_on = on; on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; }
 // rtiow_set_camera: a bad image size takes the camera away and leaves everything else; a good one -- the very camera the handle
 // already has is no exception -- also asks for new RNG states.  The base survives.
 inline void on_set_camera(PreviewState& s, bool good_size) { s.have_camera = good_size; if (good_size) { on_frame_changed(s); s.rng_ready = false; } }
@@ -156,6 +163,16 @@ inline Refusal need_motion(const PreviewState& s, const char* call) {
     if (Refusal r = refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)"); r.code) return r;
     return refuse_unless(s.have_camera && s.guides_ok && s.motion_ok, PREVIEW_E_STATE, call, ": no motion plane for the current scene, camera and shard (rtiow_render_guides)");
 }
+// rtiow_read_edit_influence: motion in effect, the knob on (no plane is made while it is off), and the plane current with the motion plane.
+inline Refusal need_edit_influence(const PreviewState& s, const char* call) {
+    if (Refusal r = refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)"); r.code) return r;
+    if (Refusal r = refuse_unless(s.influence_on, PREVIEW_E_STATE, call, ": edit influence is off (rtiow_set_edit_influence with kappa > 0)"); r.code) return r;
+    return refuse_unless(s.have_camera && s.guides_ok && s.motion_ok, PREVIEW_E_STATE, call, ": no influence plane for the current scene, camera and shard (rtiow_render_guides)");
+}
+// Does the influence plane follow the motion plane at the next guide render?
+inline bool influence_in_effect(const PreviewState& s) { return motion_in_effect(s) && s.influence_on; }
+// rtiow_set_edit_influence: kappa >= 0 (+inf: any influence at all drops the history); NaN is refused by the same comparison.
+inline Refusal check_edit_influence(const char* call, double kappa) { return refuse_unless(kappa >= 0, PREVIEW_E_BADARG, call, ": need kappa >= 0 (0: off, +inf: any influence drops the history)"); }
 // The grid the layers would be rendered with when they are stale: the last one asked for, else COVERAGE_DEFAULT_GRID.
 constexpr int COVERAGE_DEFAULT_GRID = 4;
 inline int coverage_grid_or_default(const PreviewState& s) { return s.coverage_grid ? s.coverage_grid : COVERAGE_DEFAULT_GRID; }

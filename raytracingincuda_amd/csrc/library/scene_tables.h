@@ -2,8 +2,11 @@
 // Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
 #pragma once
 #include "handle.h"
+#include "edit_list.h"
 
 namespace {
+
+static_assert(EDIT_MOVED == MOTION_MOVED && EDIT_CHANGED == MOTION_CHANGED, "edit_list.h states the flags of device/scene_motion.h");
 
 template <class T>
 int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri, const int32_t* type, const int32_t* valid) {
@@ -66,20 +69,26 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
 
 // The per-sphere table of the motion plane (surface_motion_kernel) after an rtiow_edit_scene on a handle with a base: {C'_k, r'_k} of the
 // snapshot, and MOTION_MOVED / MOTION_CHANGED from comparing the current tables with the snapshot, bits against bits.  The caller has
-// checked that the edit kept the shape, so both hold h->n spheres.  The copies are synchronous: the vectors are gone on return.
+// checked that the edit kept the shape, so both hold h->n spheres.  Beside it, from the same comparison, the edit list of
+// edit_influence_kernel (edit_list.h), which may be empty.  The copies are synchronous: the vectors are gone on return.
 template <class T>
 int upload_motion_table(rtiow_handle_s* h) {
     const size_t m = (size_t)h->n, gs = 4 * sizeof(T), ms = sizeof(int32_t) + 5 * sizeof(T);
-    std::vector<int32_t> flags(m, 0);
-    for (size_t k = 0; k < m; ++k) {
-        if (std::memcmp(h->scene_geom.data() + k * gs, h->snap_geom.data() + k * gs, gs) != 0) flags[k] |= MOTION_MOVED;
-        if (std::memcmp(h->scene_mat.data() + k * ms, h->snap_mat.data() + k * ms, ms) != 0) flags[k] |= MOTION_CHANGED;
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));         // a plane of the previous edit may still be reading the table
+    const std::vector<int32_t> flags = edit_flags(h->scene_geom.data(), h->snap_geom.data(), gs, h->scene_mat.data(), h->snap_mat.data(), ms, m);
+    const EditList list = build_edit_list(h->scene_geom.data(), h->snap_geom.data(), gs, flags);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));         // a plane of the previous edit may still be reading the tables
     HIP_TRY(h, h->motion_snap.ensure(m * gs));
     HIP_TRY(h, h->motion_flags.ensure(m * sizeof(int32_t)));
     HIP_TRY(h, hipMemcpy(h->motion_snap, h->snap_geom.data(), m * gs, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->motion_flags, flags.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->edit_entries = 0;
+    if (list.entries()) {
+        HIP_TRY(h, h->edit_list.ensure(list.geom.size()));
+        HIP_TRY(h, h->edit_owner.ensure(list.entries() * sizeof(int32_t)));
+        HIP_TRY(h, hipMemcpy(h->edit_list, list.geom.data(), list.geom.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->edit_owner, list.owner.data(), list.entries() * sizeof(int32_t), hipMemcpyHostToDevice));
+        h->edit_entries = (int)list.entries();
+    }
     return 0;
 }
 

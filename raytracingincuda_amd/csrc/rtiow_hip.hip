@@ -71,6 +71,7 @@
 #include "device/guide_chain.h"
 #include "device/edge_resolve.h"
 #include "device/scene_motion.h"
+#include "device/edit_influence.h"
 #include "library/xorwow_jump.h"
 #include "library/handle.h"
 #include "library/scene_tables.h"
@@ -956,11 +957,29 @@ int rtiow_read_scene_motion(rtiow_handle h, void* prev_point, int32_t* carry, in
         std::vector<unsigned char> c(want * es);
         if (int rc = read_planes(h, h->motion_qc, want, prev_point, c.data())) return rc;
         for (size_t k = 0; k < want; ++k) {
-            if (es == 4) { float v; std::memcpy(&v, c.data() + k * es, 4); carry[k] = (int32_t)v; }
-            else { double v; std::memcpy(&v, c.data() + k * es, 8); carry[k] = (int32_t)v; }
+            if (es == 4) { float v; std::memcpy(&v, c.data() + k * es, 4); carry[k] = v != 0; }     // w != 0: with edit influence on, w is the fade
+            else { double v; std::memcpy(&v, c.data() + k * es, 8); carry[k] = v != 0; }
         }
     } else if (int rc = read_planes(h, h->motion_qc, want, prev_point, nullptr)) return rc;
     return copy_out(h, ids, h->motion_ids, want * sizeof(int32_t));
+}
+
+// ---- Edit influence
+int rtiow_set_edit_influence(rtiow_handle h, double kappa) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, check_edit_influence("rtiow_set_edit_influence", kappa));
+    if (h->edit_kappa == kappa) return 0;
+    h->edit_kappa = kappa;
+    on_edit_influence_changed(h->preview, kappa > 0);
+    return 0;
+}
+
+int rtiow_read_edit_influence(rtiow_handle h, void* lambda, size_t npix) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, need_edit_influence(h->preview, "rtiow_read_edit_influence"));
+    const size_t want = local_pixels(h);
+    if (npix != want) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_edit_influence: npix must be local_rows x width");
+    return copy_out(h, lambda, h->edit_lambda, want * elem_size(h));
 }
 
 int rtiow_stream(rtiow_handle h, void** hip_stream) {
