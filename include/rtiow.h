@@ -662,6 +662,49 @@ int rtiow_read_scene_motion(rtiow_handle h, void* prev_point /* npix*3 T */, int
 int rtiow_set_edit_influence(rtiow_handle h, double kappa /* 0: off; > 0: on */);
 int rtiow_read_edit_influence(rtiow_handle h, void* lambda /* npix T */, size_t npix);
 
+/* ---- Scene edits that add and remove spheres without restarting the history.  rtiow_edit_scene accepts a
+ * scene of the current shape only, because it matches the spheres of the current scene with those of the snapshot index for index.
+ * rtiow_edit_scene_mapped takes the correspondence from the caller, so the new scene may have any n and any `valid`.  No kernel is added
+ * or changed: the motion plane and the edit influence read per-sphere tables that the host builds through the map.
+ * rtiow_edit_scene_mapped is rtiow_edit_scene in every respect it documents -- tables uploaded, screen and grid tables rebuilt at the next
+ * render, the accumulation back to 0, guides, coverage layers, plan, temporal image and denoised image stale, the carried hand-out order
+ * dropped, the base and its snapshot kept, motion in effect from the call until the next commit, rtiow_history_reset, rtiow_set_scene or
+ * rtiow_set_shard; without a base a rtiow_set_scene of the new tables -- except for the shape.  rtiow_edit_scene itself is unchanged.
+ * origin[i], for every slot i that `valid` keeps, names the slot OF THE SCENE THE HANDLE HOLDS NOW that slot i continues, or is -1 for a
+ * new sphere.  origin[i] of a dropped slot is not read.  A kept sphere of the current scene that no slot continues is removed.
+ * The map.  The handle keeps from_snapshot[k] per kept sphere k of the current scene: the number j of the sphere it continues among the
+ * kept spheres of the snapshot, or -1.
+ *   both commits:               the identity (they take the snapshot).
+ *   rtiow_edit_scene:           left alone.
+ *   rtiow_history_reset, rtiow_set_scene, rtiow_set_shard: dropped with the snapshot.
+ *   rtiow_edit_scene_mapped:    for kept slot i of the new scene, numbered k': origin[i] == -1: from_snapshot'[k'] = -1; origin[i] == s,
+ *                               s numbered k in the current scene: from_snapshot'[k'] = from_snapshot[k].
+ * So mapped edits between two commits compose, and a sphere added and then moved before the next commit still has no origin.  Without a
+ * base no map is kept.
+ * The tables.  Per kept sphere k of the current scene with j = from_snapshot[k]:
+ *   j >= 0:   moved_k and changed_k from the current record of k against the snapshot's record of j, bits against bits, and {C'_j, r'_j}
+ *             in the motion plane's table: section 19 with j in the place of k.
+ *   j == -1:  changed_k alone and four zeros of T: the motion plane gives the sphere's pixels Q = 0, carry = 0, id = k.
+ * A removed sphere has no entry in either table: the pixel that now sees what it hid reprojects to a base pixel that holds the removed
+ * sphere's depth and normal, fails the gather's tests and gets m = 0, as a pixel does that a moved sphere uncovers.
+ * The edit list (rtiow_set_edit_influence), in two passes.
+ *   pass 1, the kept spheres of the current scene in ascending k, owner k: moved_k: {C'_j, r'_j}, then {C_k, r_k}; changed_k only -- an
+ *           added sphere is this case: {C_k, r_k}; neither: none.
+ *   pass 2, the kept spheres j of the snapshot in ascending order that no current sphere continues: {C'_j, r'_j} with the owner -2.
+ * A hit pixel's id is >= 0 and a miss has lambda = 0, so no pixel skips an entry of owner -2 as its own.
+ * RTIOW_E_BADARG and RTIOW_E_STATE, asked in this order before anything is touched: a NULL handle (-1 before any device work); a null or
+ * empty table or n <= 0; no scene yet (RTIOW_E_STATE); origin == NULL; for a kept slot, an origin[i] below -1, at or above the current
+ * scene's slot count, or naming a slot the current scene drops; two kept slots naming the same origin (a sphere is continued at most
+ * once: no duplication); a material type outside 0..2 on a kept slot, or no kept slot at all.  A failing call leaves the handle as it
+ * was.  Not available on groups; on a handle of several ranks there is never a base, so the call is a rtiow_set_scene there.
+ * rtiow_read_scene_origin copies the map, `count` int32 (the pointer may be NULL).  RTIOW_E_STATE: motion is not in effect.  A count other
+ * than the number of kept spheres: RTIOW_E_BADARG.
+ * Out of scope: duplicating a sphere, motion-aware coverage layers and lens guides, groups and sharded bases. */
+int rtiow_edit_scene_mapped(rtiow_handle h, int n, const void* center_radius, const void* albedo_fuzz,
+                            const void* refraction_index, const int32_t* type, const int32_t* valid,
+                            const int32_t* origin /* n */);
+int rtiow_read_scene_origin(rtiow_handle h, int32_t* from_snapshot /* kept spheres */, size_t count);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

@@ -147,6 +147,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_read_scene_motion": (_H, _vp, _i32p, _i32p, _size),
     "rtiow_set_edit_influence": (_H, _dbl),
     "rtiow_read_edit_influence": (_H, _vp, _size),
+    "rtiow_edit_scene_mapped": (_H, _int, _vp, _vp, _vp, _i32p, _i32p, _i32p),
+    "rtiow_read_scene_origin": (_H, _i32p, _size),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -480,14 +482,16 @@ def _out(ctype, wanted=True):
     return holder, (ctypes.byref(holder) if wanted else None)
 
 
-def _set_scene(fn, handle, scene, dt):
-    """rtiow_set_scene / rtiow_group_set_scene: build_scene()'s five tables in the handle's precision ('valid' may be absent)."""
+def _set_scene(fn, handle, scene, dt, *more):
+    """rtiow_set_scene / rtiow_group_set_scene: build_scene()'s five tables in the handle's precision ('valid' may be absent); `more`:
+    what the call takes behind them."""
     cr = np.ascontiguousarray(scene["center_radius"], dt)
     af = np.ascontiguousarray(scene["albedo_fuzz"], dt)
     ri = np.ascontiguousarray(scene["refraction_index"], dt)
     ty = np.ascontiguousarray(scene["type"], np.int32)
     va = np.ascontiguousarray(scene["valid"], np.int32) if scene.get("valid") is not None else None
-    return fn(handle, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data, ty.ctypes.data_as(_i32p), va.ctypes.data_as(_i32p) if va is not None else None)
+    return fn(handle, len(ty), cr.ctypes.data, af.ctypes.data, ri.ctypes.data, ty.ctypes.data_as(_i32p), va.ctypes.data_as(_i32p) if va is not None else None,
+              *more)
 
 
 class Renderer:
@@ -562,6 +566,26 @@ class Renderer:
         the history of a moved sphere along with it until the next commit.  The loop of an edited frame: edit_scene, set_camera if it
         moved, init_rng, history_plan, accumulate_budget ..., history_update_clipped, history_commit."""
         self._check(_set_scene(self._lib.rtiow_edit_scene, self._h, scene, self.dtype))
+
+    def edit_scene_mapped(self, scene, origin):
+        """edit_scene() for a scene of another shape: spheres added and removed, slots reordered, any 'valid'.
+        origin[i] is the slot of the scene the renderer holds now that slot i of `scene` continues, or -1 for a new sphere (one entry per
+        slot of `scene`; those of dropped slots are not read); a sphere of the current scene that no slot continues is removed.  A
+        continued sphere carries its history as under edit_scene(), an added one carries none, and the pixels a removed one uncovers fail
+        the gather's depth test, so accumulate_budget() samples them."""
+        origin = np.ascontiguousarray(origin, np.int32).reshape(-1)
+        if origin.size != len(scene["type"]):
+            raise ValueError("origin needs one entry per slot of the scene")
+        self._check(_set_scene(self._lib.rtiow_edit_scene_mapped, self._h, scene, self.dtype, origin.ctypes.data_as(_i32p)))
+
+    def scene_origin(self):
+        """from_snapshot [kept spheres] int32 while an edit is in effect: per kept sphere of the current scene, the number of the sphere it
+        continues among the kept spheres of the scene the base was committed under, or -1 for one added since."""
+        st = Stats()
+        self._check(self._lib.rtiow_get_stats(self._h, ctypes.byref(st)))
+        out = np.empty(st.num_spheres, np.int32)
+        self._check(self._lib.rtiow_read_scene_origin(self._h, out.ctypes.data_as(_i32p), out.size))
+        return out
 
     def set_camera(self, cam):
         want = CameraF64 if self.precision == 64 else CameraF32

@@ -154,6 +154,10 @@ struct rtiow_handle_s {
     // as 4 T and the id per local pixel, written wherever the guides are while motion is in effect).
     std::vector<unsigned char> scene_geom, scene_mat, snap_geom, snap_mat, scene_kept;
     int scene_slots = 0;
+    // rtiow_edit_scene_mapped: per kept sphere of the current scene, the number of the sphere it continues among the kept spheres of the
+    // snapshot, or -1 (added since).  The identity from both commits, composed by every mapped edit, left alone by rtiow_edit_scene, and
+    // gone wherever the snapshot goes; without a base it is empty.
+    std::vector<int32_t> from_snapshot;
     DeviceBuffer<> motion_snap, motion_qc;
     DeviceBuffer<int32_t> motion_flags, motion_ids;
     // edit influence (rtiow_set_edit_influence): the knob (0: off; preview.influence_on says whether it is > 0; it survives set_scene /

@@ -6,6 +6,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
 constexpr int PREVIEW_E_BADARG = -1, PREVIEW_E_STATE = -2;   // RTIOW_E_BADARG, RTIOW_E_STATE (include/rtiow.h); handle.h asserts them equal
 enum { ACC_MODE_NONE = 0, ACC_MODE_PLAIN = 1, ACC_MODE_ADAPTIVE = 2 };   // PreviewState::acc_mode: no chunk since the reset, rtiow_accumulate, rtiow_accumulate_adaptive / _budget
@@ -64,7 +65,8 @@ inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.moti
 inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; s.coverage_ok = false; }
 // rtiow_set_scene, before the upload: also the history base goes, which a new camera keeps.  The RNG states stay.
 inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; s.scene_edited = false; }
-// rtiow_edit_scene, before the upload: rtiow_set_scene's event without emptying the base; with a base, motion is in effect from here on.
+// rtiow_edit_scene and rtiow_edit_scene_mapped, before the upload: rtiow_set_scene's event without emptying the base; with a base, motion
+// is in effect from here on.
 inline void on_scene_edited(PreviewState& s) { on_frame_changed(s); s.scene_edited = s.hist_base_ok; }
 inline void on_scene_uploaded(PreviewState& s) { s.scene = true; }
 // rtiow_set_edit_influence with another kappa than the handle has (`on`: the new one is > 0): everything that depends on the motion plane
@@ -163,6 +165,10 @@ inline Refusal need_motion(const PreviewState& s, const char* call) {
     if (Refusal r = refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)"); r.code) return r;
     return refuse_unless(s.have_camera && s.guides_ok && s.motion_ok, PREVIEW_E_STATE, call, ": no motion plane for the current scene, camera and shard (rtiow_render_guides)");
 }
+// rtiow_read_scene_origin: motion in effect, in rtiow_read_scene_motion's words; the map is the host's, so no plane is asked for.
+inline Refusal need_motion_in_effect(const PreviewState& s, const char* call) {
+    return refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)");
+}
 // rtiow_read_edit_influence: motion in effect, the knob on (no plane is made while it is off), and the plane current with the motion plane.
 inline Refusal need_edit_influence(const PreviewState& s, const char* call) {
     if (Refusal r = refuse_unless(motion_in_effect(s), PREVIEW_E_STATE, call, ": motion is not in effect (rtiow_edit_scene on a handle with a history base)"); r.code) return r;
@@ -208,6 +214,31 @@ inline Refusal check_scene_edit(const char* call, int n, const int32_t* valid, i
     for (int i = 0; i < n; ++i)
         if ((!valid || valid[i] != 0) != (kept[i] != 0)) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": valid must keep the slots the current scene keeps"};
     return Refusal{};
+}
+// rtiow_edit_scene_mapped, in the order it asks after check_scene_tables and need_scene_to_edit: an origin
+// table; for every slot i that `valid` keeps, origin[i] is -1 (a new sphere) or a slot the current scene keeps; no two kept slots continue
+// the same sphere; then upload_scene's own refusals, in its words: a material type in 0..2 on every kept slot, and a kept slot at all.
+// origin[i] of a slot `valid` drops is not read.  The new scene may have any n and any `valid`.
+inline Refusal check_scene_mapped(const char* call, int n, const int32_t* valid, const int32_t* type, const int32_t* origin, int current_n,
+                                  const unsigned char* kept) {
+    if (!origin) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": origin must not be NULL (-1 per slot: every sphere is new)"};
+    auto keeps = [&](int i) { return !valid || valid[i] != 0; };
+    for (int i = 0; i < n; ++i)
+        if (keeps(i) && origin[i] != -1 && (origin[i] < -1 || origin[i] >= current_n || !kept[origin[i]]))
+            return Refusal{PREVIEW_E_BADARG, std::string(call) + ": origin must be -1 or a slot the current scene keeps"};
+    std::vector<unsigned char> continued((size_t)(current_n > 0 ? current_n : 0), 0);
+    for (int i = 0; i < n; ++i) {
+        if (!keeps(i) || origin[i] < 0) continue;
+        if (continued[(size_t)origin[i]]) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": two slots continue the same sphere (a sphere is continued at most once)"};
+        continued[(size_t)origin[i]] = 1;
+    }
+    int spheres = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!keeps(i)) continue;
+        if (type[i] < 0 || type[i] > 2) return Refusal{PREVIEW_E_BADARG, "material type out of range"};
+        ++spheres;
+    }
+    return spheres ? Refusal{} : Refusal{PREVIEW_E_BADARG, "scene has no valid spheres"};
 }
 // rtiow_resolve_edges: radius in 1..max_radius, sigma[2] (normal, depth) each > 0 with inv2[k] = 1 / sigma[k]^2, prior > 0.
 inline Refusal check_edge_resolve(const char* call, int radius, int max_radius, const double (&sigma)[2], double prior, double (&inv2)[2]) {

@@ -67,19 +67,24 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
     return 0;
 }
 
-// The per-sphere table of the motion plane (surface_motion_kernel) after an rtiow_edit_scene on a handle with a base: {C'_k, r'_k} of the
-// snapshot, and MOTION_MOVED / MOTION_CHANGED from comparing the current tables with the snapshot, bits against bits.  The caller has
-// checked that the edit kept the shape, so both hold h->n spheres.  Beside it, from the same comparison, the edit list of
-// edit_influence_kernel (edit_list.h), which may be empty.  The copies are synchronous: the vectors are gone on return.
+// The per-sphere table of the motion plane (surface_motion_kernel) after an rtiow_edit_scene or rtiow_edit_scene_mapped on a handle with a
+// base, indexed by the h->n kept spheres of the current scene: for the sphere j = h->from_snapshot[k] of the snapshot that k continues,
+// {C'_j, r'_j} and MOTION_MOVED / MOTION_CHANGED from comparing the current record of k with the snapshot's of j, bits against bits; for
+// an added sphere (j == -1) zeros and MOTION_CHANGED alone.  The snapshot may hold another number of spheres than the scene.  Beside it,
+// from the same comparison, the edit list of edit_influence_kernel (edit_list.h), which may be empty.  The copies are synchronous: the
+// vectors are gone on return.
 template <class T>
 int upload_motion_table(rtiow_handle_s* h) {
     const size_t m = (size_t)h->n, gs = 4 * sizeof(T), ms = sizeof(int32_t) + 5 * sizeof(T);
-    const std::vector<int32_t> flags = edit_flags(h->scene_geom.data(), h->snap_geom.data(), gs, h->scene_mat.data(), h->snap_mat.data(), ms, m);
-    const EditList list = build_edit_list(h->scene_geom.data(), h->snap_geom.data(), gs, flags);
+    if (h->from_snapshot.size() != m) return fail_arg(h, RTIOW_E_STATE, "scene edit: the map does not cover the scene (a base without a snapshot)");
+    const int32_t* from = h->from_snapshot.data();       // m entries: the commit's identity, composed by every mapped edit since
+    const std::vector<int32_t> flags = edit_flags_mapped(h->scene_geom.data(), h->snap_geom.data(), gs, h->scene_mat.data(), h->snap_mat.data(), ms, m, from);
+    const std::vector<unsigned char> snap = motion_snap_table(h->snap_geom.data(), gs, m, from);
+    const EditList list = build_edit_list_mapped(h->scene_geom.data(), h->snap_geom.data(), gs, flags, from, h->snap_geom.size() / gs);
     HIP_TRY(h, hipStreamSynchronize(h->stream));         // a plane of the previous edit may still be reading the tables
     HIP_TRY(h, h->motion_snap.ensure(m * gs));
     HIP_TRY(h, h->motion_flags.ensure(m * sizeof(int32_t)));
-    HIP_TRY(h, hipMemcpy(h->motion_snap, h->snap_geom.data(), m * gs, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->motion_snap, snap.data(), m * gs, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->motion_flags, flags.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
     h->edit_entries = 0;
     if (list.entries()) {

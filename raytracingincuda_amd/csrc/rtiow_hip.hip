@@ -126,7 +126,7 @@ static void release_stream(int device, hipStream_t s) {
 }
 
 // The snapshot of the scene the base was committed under goes wherever the base goes (rtiow_history_reset, rtiow_set_scene, rtiow_set_shard).
-void drop_snapshot(rtiow_handle_s* h) { h->snap_geom.clear(); h->snap_mat.clear(); }
+void drop_snapshot(rtiow_handle_s* h) { h->snap_geom.clear(); h->snap_mat.clear(); h->from_snapshot.clear(); }
 
 // The times a render call on a shard without rows reports.
 void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
@@ -265,6 +265,35 @@ int rtiow_edit_scene(rtiow_handle h, int n, const void* center_radius, const voi
         if (int rc = upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid)) return rc;
         return motion_in_effect(h->preview) ? upload_motion_table<T>(h) : 0;
     });
+}
+
+// ---- Scene edits that add and remove spheres
+int rtiow_edit_scene_mapped(rtiow_handle h, int n, const void* center_radius, const void* albedo_fuzz,
+                            const void* refraction_index, const int32_t* type, const int32_t* valid, const int32_t* origin) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, check_scene_tables("rtiow_edit_scene_mapped", center_radius && albedo_fuzz && refraction_index && type, n));
+    PREVIEW_TRY(h, need_scene_to_edit(h->preview, "rtiow_edit_scene_mapped"));
+    PREVIEW_TRY(h, check_scene_mapped("rtiow_edit_scene_mapped", n, valid, type, origin, h->scene_slots, h->scene_kept.data()));
+    HIP_TRY(h, hipSetDevice(h->device));
+    // composed against the slots of the scene the handle holds now, which the upload replaces; without a base no map is kept
+    std::vector<int32_t> map;
+    if (h->preview.hist_base_ok) map = compose_origin(n, valid, origin, h->scene_kept.data(), h->scene_slots, h->from_snapshot.data());
+    on_scene_edited(h->preview);
+    h->carried.clear();                                  // its cost map is of the old frame
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = upload_scene<T>(h, n, (const T*)center_radius, (const T*)albedo_fuzz, (const T*)refraction_index, type, valid)) return rc;
+        h->from_snapshot = std::move(map);
+        return motion_in_effect(h->preview) ? upload_motion_table<T>(h) : 0;
+    });
+}
+
+int rtiow_read_scene_origin(rtiow_handle h, int32_t* from_snapshot, size_t count) {
+    if (!h) return RTIOW_E_BADARG;
+    PREVIEW_TRY(h, need_motion_in_effect(h->preview, "rtiow_read_scene_origin"));
+    if (count != h->from_snapshot.size()) return fail_arg(h, RTIOW_E_BADARG, "rtiow_read_scene_origin: count must be the number of kept spheres");
+    if (from_snapshot) std::memcpy(from_snapshot, h->from_snapshot.data(), count * sizeof(int32_t));
+    return 0;
 }
 
 int rtiow_set_camera(rtiow_handle h, const void* camera) {
@@ -805,6 +834,8 @@ void commit_base(rtiow_handle_s* h) {
     std::swap(h->hist_base_nd, h->guide_nd);
     h->hist_cam32 = h->cam32; h->hist_cam64 = h->cam64;
     h->snap_geom = h->scene_geom; h->snap_mat = h->scene_mat;
+    h->from_snapshot.resize((size_t)h->n);               // the identity: every sphere continues itself
+    for (int k = 0; k < h->n; ++k) h->from_snapshot[(size_t)k] = k;
     on_commit(h->preview);
 }
 }  // namespace
