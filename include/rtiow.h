@@ -705,6 +705,52 @@ int rtiow_edit_scene_mapped(rtiow_handle h, int n, const void* center_radius, co
                             const int32_t* origin /* n */);
 int rtiow_read_scene_origin(rtiow_handle h, int32_t* from_snapshot /* kept spheres */, size_t count);
 
+/* ---- Guided upscaling: a preview at a multiple of the traced resolution.  Every buffer above has the
+ * camera's img_width x img_height; rtiow_upscale writes an image F = factor times as wide and as high from the frame that was traced.
+ * Every output pixel traces one primary ray of its own and gathers the colour of the four traced pixels around it, weighed by what that
+ * ray hit.  Everything in T, left to right as written, plain * + - /, a correctly rounded sqrt, no fused multiply-add.
+ * W, H = the camera's frame.  Output pixel (I, J) of the F W x F H image: i = I / F, a = I - F i; j, b likewise.
+ * The ray is rtiow_render_coverage's sub-sample ray with G = F, to the letter: o_a = ((T)a + 0.5) / (T)F - 0.5 and o_b likewise,
+ *   fx = (T)i + o_a, fy = (T)j + o_b, D = ((pixel00 + fx du) + fy dv) - O, (t, k) = hit_world(O, D).  On a hit N, A, Z are
+ *   rtiow_render_guides' normal (facing the ray), albedo ({1,1,1} for a dielectric) and depth t; on a miss k = -1, N = A = 0, Z = 0.
+ * The taps.  x0 = o_a < 0 ? i - 1 : i, gx = o_a < 0 ? (T)1 + o_a : o_a; y0, gy likewise.  The traced pixels q = (x0, y0), (x0 + 1, y0),
+ *   (x0, y0 + 1), (x0 + 1, y0 + 1), in this order, with b = ((T)1 - gx)((T)1 - gy), gx ((T)1 - gy), ((T)1 - gx) gy, gx gy.  A tap counts
+ *   when q is inside the frame, b > 0 and q holds colour.  By source:
+ *     RTIOW_UPSCALE_DENOISED  always;                                c_q = g_q g_q per channel, g the denoised image as stored
+ *     RTIOW_UPSCALE_LINEAR    n_q > 0 (rtiow_read_linear's count);   c_q = rtiow_read_linear's value
+ *     RTIOW_UPSCALE_HISTORY   Mout_q > 0;                            c_q = Cout_q of the temporal image
+ * The weight.  N_q, A_q, Z_q = the FIRST-HIT guides of q, in either guide mode and whatever rtiow_set_guide_lens is set to.  d = N_q - N,
+ *   en = (d.x d.x + d.y d.y) + d.z d.z; ea the same of the albedo; dz = Z_q - Z, ez = dz dz; e = (en i_n + ea i_a) + ez i_z with
+ *   i_* = (T)(1 / sigma_*^2) computed in double and rounded once (sigma = +inf turns a term off); w = b / ((T)1 + e).  From 0 in tap
+ *   order: S1 = S1 + w c_q per channel, W1 = W1 + w.
+ * The share, with use_coverage = 1.  (id_0, id_1, c_0, c_1) = the coverage layers of q, S their G G.  m = id_0 == k ? c_0 :
+ *   (id_1 == k ? c_1 : 0); when m > 0: wp = w * ((T)m / (T)S), Sp = Sp + wp c_q, Wp = Wp + wp.  A traced pixel's colour is an area mix;
+ *   this weighs a tap by how much of it is the surface the output pixel sees (the sky is k = -1 and matches sky layers).
+ * The result.  Wp > 0: out = Sp / Wp; otherwise W1 > 0: out = S1 / W1; otherwise 0.  Stored per channel: out > 0 ? sqrt(out) : 0.
+ *   *covered_pixels (may be NULL) = the output pixels with Wp > 0; 0 with use_coverage = 0.
+ * Stale guides are rendered first, inside kernel_ms; with use_coverage = 1 so are stale layers, with the G of the last
+ * rtiow_render_coverage, or 4 if there was none (G is independent of F).  kernel_ms == NULL and covered_pixels == NULL: asynchronous on
+ * the handle's stream.  The output buffer is the handle's own: allocated at first use, regrown for a larger F, freed by rtiow_destroy.
+ * rtiow_read_upscaled copies it, (F local_rows) x (F width) x 3 T, gamma-encoded like the preview; rtiow_upscaled_device_ptr gives its
+ * address and size.
+ * RTIOW_E_BADARG: factor outside 2..4; source outside 0..2; a sigma <= 0 or NaN; use_coverage not 0 or 1; an output wider or higher than
+ * 2^31 - 8 pixels or of more than 2^31 - 4 8x8 tiles, the kernel's int coordinates and tile count (the text says which; within them the
+ * byte size fits its size_t index); in the two readers, bytes other than the buffer's.
+ * RTIOW_E_STATE: before scene and camera are set; DENOISED before a filter has run; LINEAR without a chunk; HISTORY with a stale temporal
+ * image; a sharded handle; in the readers, before an rtiow_upscale or once the image is stale.  A NULL handle: -1 before any device work.
+ * A failing call leaves the handle as it was.
+ * The upscaled image goes stale with rtiow_set_scene, rtiow_edit_scene(_mapped), rtiow_set_camera and rtiow_set_shard and with nothing
+ * else: it is a finished output and survives chunks, filters, updates, commits and the guide knobs.  The call reads the framebuffer's
+ * sources -- accumulation and counts, denoised image, guides, layers, temporal image -- and writes only its own buffer: every existing
+ * path keeps its bits.  Not available on groups. */
+#define RTIOW_UPSCALE_DENOISED 0   /* the buffer of rtiow_read_denoised, whichever filter (or rtiow_resolve_edges) wrote it last */
+#define RTIOW_UPSCALE_LINEAR   1   /* the linear colour of the accumulation (rtiow_read_linear) */
+#define RTIOW_UPSCALE_HISTORY  2   /* the colour Cout of the temporal image (rtiow_read_history) */
+int rtiow_upscale(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                  int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+int rtiow_read_upscaled(rtiow_handle h, void* host_rgb, size_t bytes);      /* (F rows) x (F W) x 3 T, gamma-encoded like the preview */
+int rtiow_upscaled_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

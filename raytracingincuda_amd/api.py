@@ -16,6 +16,7 @@ There is no CPU fallback: if librtiow_hip.so is missing or no GPU is visible the
 raise.  (The CPU oracle lives in oracle/ and is test infrastructure only.)
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -26,6 +27,7 @@ SCENE_LDS, SCENE_SCALAR, SCENE_LDS_EXACT, SCENE_GRID = 0, 1, 2, 3
 SCHED_STATIC, SCHED_PERSISTENT, SCHED_SORTED = 0, 1, 2
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER, GATHER_HOST = 0, 1, 2, 3
 GUIDES_FIRST_HIT, GUIDES_SPECULAR = 0, 1  # rtiow_set_guide_mode
+UPSCALE_DENOISED, UPSCALE_LINEAR, UPSCALE_HISTORY = 0, 1, 2  # rtiow_upscale's source
 GROUP_MAX_STATS = 16
 ABI_VERSION = 6          # include/rtiow.h RTIOW_ABI_VERSION
 
@@ -149,6 +151,9 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_read_edit_influence": (_H, _vp, _size),
     "rtiow_edit_scene_mapped": (_H, _int, _vp, _vp, _vp, _i32p, _i32p, _i32p),
     "rtiow_read_scene_origin": (_H, _i32p, _size),
+    "rtiow_upscale": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
+    "rtiow_read_upscaled": (_H, _vp, _size),
+    "rtiow_upscaled_device_ptr": (_H, _vpp, _sizep),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -473,6 +478,16 @@ GUIDE_LENS_GRID = 2
 # MSE ratio among those within 1.10 x the rays of kappa == 0.  No kappa of the sweep brought that ratio below 1 (0.25: 1.006), which is
 # why a handle starts with kappa == 0, off.
 EDIT_INFLUENCE_KAPPA = 0.25
+# Renderer.upscale defaults: the factor, and the best of scripts/upscale_probe.py --sweep by the rule of DESIGN.md
+# section 4.22, i.e. the smallest worse-of-two-scenes ratio of the MSE of the upscaled half-resolution frame to that of the full-resolution
+# frame at the same number of rays, at 1 and 4 rays an output pixel, first of equals in grid order (profiles/upscale/upscale_probe.json).
+# At these the ratio is 0.10 / 0.08 at 1 ray and 0.38 / 0.35 at 4 (scenes 1 / 3), but plain bilinear interpolation of the same denoised
+# image is 8 to 21 % better still at factor 2 (at factor 4 the guided gather wins): it does not pay yet, and the call stays opt-in.
+UPSCALE_FACTOR = 2
+UPSCALE_SIGMA_NORMAL = 0.3
+UPSCALE_SIGMA_ALBEDO = float("inf")
+UPSCALE_SIGMA_DEPTH = float("inf")
+UPSCALE_COVERAGE = 0
 
 
 def _out(ctype, wanted=True):
@@ -910,6 +925,35 @@ class Renderer:
         (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
         self._check(self._lib.rtiow_resolve_edges(self._h, int(radius), float(sigma_normal), float(sigma_depth), float(prior), ms_out, n_out))
         return int(n.value) if sync else None
+
+    def upscale(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_SIGMA_NORMAL, sigma_albedo=UPSCALE_SIGMA_ALBEDO,
+                sigma_depth=UPSCALE_SIGMA_DEPTH, use_coverage=UPSCALE_COVERAGE, sync=True):
+        """A preview `factor` (2..4) times as wide and as high as the traced frame: every output pixel traces
+        one primary ray of its own and gathers the four traced pixels around it -- of the denoised image (UPSCALE_DENOISED, after any
+        filter or resolve_edges()), the accumulation (UPSCALE_LINEAR) or the temporal image (UPSCALE_HISTORY) -- each weighed bilinearly,
+        by first-hit normal, albedo and depth against what its ray hit (float("inf") turns a term off) and, with use_coverage, by the
+        share of the tap that is the surface the output pixel sees (render_coverage).  Stale guides and layers are rendered first, the
+        layers at the subsamples_per_side of the last render_coverage() (COVERAGE_GRID before any).  Read the image with read_upscaled();
+        it stays current until the next set_scene, edit_scene, set_camera or set_shard.  Returns the number of output pixels the share
+        decided (None when sync=False)."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                            int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
+    def read_upscaled(self):
+        """The image of the last upscale(), [factor * rows, factor * W, 3], gamma-encoded like the preview."""
+        _, nbytes = self.upscaled_device_ptr()
+        F = math.isqrt(nbytes // (self.local_rows * self.width * 3 * np.dtype(self.dtype).itemsize))     # the buffer holds F x F traced frames
+        out = np.empty((F * self.local_rows, F * self.width, 3), self.dtype)
+        self._check(self._lib.rtiow_read_upscaled(self._h, out.ctypes.data, out.nbytes))
+        return out
+
+    def upscaled_device_ptr(self):
+        """(device address, bytes) of the last upscale() output."""
+        return self._device_ptr(self._lib.rtiow_upscaled_device_ptr)
 
     def history(self):
         """(rgb [H, W, 3] linear, length [H, W]) of the temporal image: the blended colour and its history length in samples."""

@@ -168,6 +168,11 @@ struct rtiow_handle_s {
     int edit_entries = 0;
     DeviceBuffer<> edit_list, edit_lambda;
     DeviceBuffer<int32_t> edit_owner;
+    // guided upscaling (rtiow_upscale), allocated at first use and regrown for a larger factor: the upscaled image, (F local_rows) x (F W)
+    // x 3 T, gamma-encoded, with F = preview.upscale_factor and upscaled_bytes its size; the count of output pixels the share decided
+    DeviceBuffer<> upscaled;
+    size_t upscaled_bytes = 0;
+    DeviceBuffer<unsigned> upscale_ctr;
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

@@ -2,8 +2,8 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels
-// Host side of librtiow_hip.so; part of the single translation unit rtiow_hip.hip (internal linkage).
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone)
+// Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, and of rtiow_upscale.hip for launch_upscale (internal linkage).
 #pragma once
 #include "scene_tables.h"
 #include "../device/render_kernels.h"
@@ -18,6 +18,7 @@
 #include "../device/history_budget.h"
 #include "../device/temporal_noise.h"
 #include "../device/edge_resolve.h"
+#include "../device/upscale.h"
 
 namespace {
 
@@ -732,6 +733,45 @@ int launch_edge_resolve(rtiow_handle_s* h, int radius, const double inv2[2], dou
                        temporal ? nullptr : counts, n_uniform, temporal ? h->hist_cm.as<const Vec4<T>>() : nullptr, h->denoised.as<T>(), (unsigned*)h->edge_ctr);
     HIP_TRY(h, hipGetLastError());
     on_edges_resolved(h->preview);
+    return 0;
+}
+
+// upscale_kernel over the traced frame into h->upscaled (rtiow_upscale): the layout of launch_guides with one word per wave behind it for
+// the count, one 8x8 tile of the factor x larger image per wave.  source picks the colour (RTIOW_UPSCALE_*: the denoised image, the
+// accumulation's records and counts, the temporal image); the guides are the FIRST-HIT buffers whatever the guide mode; inv2[3] = 1 /
+// sigma^2 of normal, albedo, depth (double), rounded to T here.  h->upscale_ctr holds the number of output pixels the share decided, in
+// UPSCALE_COUNTERS words that rtiow_upscale sums.  The
+// caller has checked state and arguments -- out_bytes is check_upscale_extent's -- and made the guides and, with use_coverage, the layers
+// current.
+template <class T>
+int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+    Launch<T> L{make_params<T>(h)};
+    const int threads = 256;
+    int rc = layout_lds<T>(h, L, threads, false, false);
+    if (rc) return rc;
+    const size_t tally_offset = (L.lds + 15) / 16 * 16, lds = tally_offset + UPSCALE_TALLY_BYTES;
+    if (lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
+    HIP_TRY(h, h->upscaled.ensure(out_bytes));
+    constexpr size_t ctr_bytes = (size_t)UPSCALE_COUNTERS * UPSCALE_COUNTER_STRIDE * sizeof(unsigned);
+    HIP_TRY(h, h->upscale_ctr.ensure(ctr_bytes));
+    HIP_TRY(h, hipMemsetAsync(h->upscale_ctr, 0, ctr_bytes, h->stream));
+    UpscaleParams<T> u{};
+    u.F = factor; u.source = source; u.use_coverage = use_coverage;
+    u.S = h->preview.coverage_grid * h->preview.coverage_grid;
+    u.i_n = (T)inv2[0]; u.i_a = (T)inv2[1]; u.i_z = (T)inv2[2];
+    u.tally_offset = (int)tally_offset;
+    if (source == RTIOW_UPSCALE_LINEAR) accumulation_source(h, u.mid, u.counts, u.n_uniform);
+    if (source == RTIOW_UPSCALE_DENOISED) u.g = h->denoised.as<const T>();
+    if (source == RTIOW_UPSCALE_HISTORY) u.cm = h->hist_cm.as<const Vec4<T>>();
+    u.nd = h->guide_nd.as<const Vec4<T>>(); u.alb = h->guide_alb.as<const Vec4<T>>();
+    u.ic = use_coverage ? h->cov_ic.as<const int4>() : nullptr;
+    const auto k = by_source(L.lds_source, [](auto src) { return upscale_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, lds));
+    const int tiles = ((L.p.cold.W * factor + 7) / 8) * ((h->local_rows * factor + 7) / 8);
+    hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), lds, h->stream, L.p, u, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
+    HIP_TRY(h, hipGetLastError());
+    h->upscaled_bytes = out_bytes;
+    on_upscaled(h->preview, factor);
     return 0;
 }
 

@@ -52,6 +52,10 @@ struct PreviewState {
     // edit influence.  influence_on: rtiow_set_edit_influence holds a kappa > 0.  While it does, the influence
     // plane is written wherever the motion plane is, and the motion plane's fourth T holds the fade: both are current exactly when motion_ok.
     bool influence_on = false;
+    // guided upscaling.  upscaled_ok: rtiow_upscale has written the upscaled image of the current scene, camera
+    // and shard; upscale_factor: its F (0 before the first; it survives everything).  A finished output: only a new frame makes it stale.
+    bool upscaled_ok = false;
+    int upscale_factor = 0;
 };
 
 // ---- events.  Flags are raised behind a successful enqueue, never before it; on_chunk_begin alone comes before its launch.
@@ -60,9 +64,12 @@ inline void on_accumulation_reset(PreviewState& s) { s.acc_samples = 0; s.acc_mo
 // A new guide mode (rtiow_set_guide_mode) or lens lattice (rtiow_set_guide_lens) makes the guides and the denoised image stale and nothing else.
 inline void on_guide_mode_changed(PreviewState& s) { s.guides_ok = false; s.motion_ok = false; s.denoised_ok = false; }
 // What a new scene, camera or shard has in common: the accumulation, the guides and the denoised image, the temporal image and the
-// history plan and the coverage layers are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside it: its cost map is
-// of the old frame too.)
-inline void on_frame_changed(PreviewState& s) { on_accumulation_reset(s); on_guide_mode_changed(s); s.hist_ok = false; s.plan_ok = false; s.coverage_ok = false; }
+// history plan, the coverage layers and the upscaled image are of the old frame.  (rtiow_hip.hip drops the carried hand-out order beside
+// it: its cost map is of the old frame too.)
+inline void on_frame_changed(PreviewState& s) {
+    on_accumulation_reset(s); on_guide_mode_changed(s);
+    s.hist_ok = false; s.plan_ok = false; s.coverage_ok = false; s.upscaled_ok = false;
+}
 // rtiow_set_scene, before the upload: also the history base goes, which a new camera keeps.  The RNG states stay.
 inline void on_set_scene(PreviewState& s) { on_frame_changed(s); s.hist_base_ok = false; s.scene_edited = false; }
 // rtiow_edit_scene and rtiow_edit_scene_mapped, before the upload: rtiow_set_scene's event without emptying the base; with a base, motion
@@ -89,6 +96,7 @@ inline void on_guides_rendered(PreviewState& s) { s.guides_ok = true; s.motion_o
 inline void on_denoised(PreviewState& s, int from = DENOISED_FROM_ACCUMULATION) { s.denoised_ok = true; s.denoised_from = from; s.denoised_gen = s.acc_gen; s.resolved = false; }
 inline void on_coverage_rendered(PreviewState& s, int grid) { s.coverage_ok = true; s.coverage_grid = grid; }
 inline void on_edges_resolved(PreviewState& s) { s.resolved = true; }
+inline void on_upscaled(PreviewState& s, int factor) { s.upscaled_ok = true; s.upscale_factor = factor; }
 // rtiow_history_update / _clipped: V^0 was of the image this one replaces.
 inline void on_history_updated(PreviewState& s) { s.hist_ok = true; s.hist_var_ok = false; s.hist_gen = s.acc_gen; }
 inline void on_plan_written(PreviewState& s) { s.plan_ok = true; }
@@ -155,6 +163,10 @@ inline Refusal need_denoised_source(const PreviewState& s, const char* call) {
 }
 inline Refusal need_denoised_accumulation(const PreviewState& s, const char* call) {
     return refuse_unless(s.denoised_gen == s.acc_gen, PREVIEW_E_STATE, call, ": a chunk or a reset since the filter that wrote the denoised image (filter again)");
+}
+// rtiow_read_upscaled, rtiow_upscaled_device_ptr: an rtiow_upscale since the last new scene, camera or shard.
+inline Refusal need_upscaled(const PreviewState& s, const char* call) {
+    return refuse_unless(s.have_camera && s.upscaled_ok, PREVIEW_E_STATE, call, ": no upscaled image for the current scene, camera and shard (rtiow_upscale)");
 }
 // Motion is in effect: from an rtiow_edit_scene on a handle with a base until the next commit, history reset, set_scene or set_shard.
 inline bool motion_in_effect(const PreviewState& s) { return s.hist_base_ok && s.scene_edited; }
@@ -248,4 +260,30 @@ inline Refusal check_edge_resolve(const char* call, int radius, int max_radius, 
         inv2[k] = 1.0 / (sigma[k] * sigma[k]);
     }
     return refuse_unless(prior > 0, PREVIEW_E_BADARG, call, ": need prior > 0 (+inf: the rebuilt colour alone)");
+}
+// rtiow_upscale: factor in min_factor..max_factor, source one of the `sources` RTIOW_UPSCALE_*, sigma[3] (normal, albedo, depth) each > 0
+// with inv2[k] = 1 / sigma[k]^2, use_coverage 0 or 1.
+inline Refusal check_upscale(const char* call, int factor, int min_factor, int max_factor, int source, int sources, const double (&sigma)[3], int use_coverage,
+                             double (&inv2)[3]) {
+    if (factor < min_factor || factor > max_factor)
+        return Refusal{PREVIEW_E_BADARG, std::string(call) + ": factor must be " + std::to_string(min_factor) + ".." + std::to_string(max_factor)};
+    if (source < 0 || source >= sources) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": unknown source (RTIOW_UPSCALE_*)"};
+    for (int k = 0; k < 3; ++k) {
+        if (!(sigma[k] > 0)) return Refusal{PREVIEW_E_BADARG, std::string(call) + ": every sigma must be > 0 (+inf turns its term off)"};
+        inv2[k] = 1.0 / (sigma[k] * sigma[k]);
+    }
+    return refuse_unless(use_coverage == 0 || use_coverage == 1, PREVIEW_E_BADARG, call, ": use_coverage must be 0 or 1");
+}
+// ... and its output, factor x the W x rows frame with elem_bytes per T.  The kernel's pixel coordinates are ints that it rounds up to
+// whole 8 x 8 tiles (width and height at most 2^31 - 8), and it counts the tiles, rounded up to whole workgroups of four, in an int (at
+// most 2^31 - 4 of them).  Within both limits the buffer has under 2^42 bytes, which the kernel indexes in size_t: *out_bytes.
+inline Refusal check_upscale_extent(const char* call, int factor, int64_t W, int64_t rows, int64_t elem_bytes, uint64_t* out_bytes) {
+    const uint64_t ow = (uint64_t)factor * (uint64_t)W, oh = (uint64_t)factor * (uint64_t)rows;
+    if (ow > 0x7ffffff8ull || oh > 0x7ffffff8ull)
+        return Refusal{PREVIEW_E_BADARG, std::string(call) + ": the output is wider or higher than the kernel's int coordinates count (2^31 - 8)"};
+    const uint64_t tx = (ow + 7) / 8, ty = (oh + 7) / 8;
+    if (ty != 0 && tx > 0x7ffffffcull / ty)
+        return Refusal{PREVIEW_E_BADARG, std::string(call) + ": the output has more 8 x 8 tiles than the kernel's int counts (2^31 - 4)"};
+    if (out_bytes) *out_bytes = ow * oh * 3 * (uint64_t)elem_bytes;
+    return Refusal{};
 }

@@ -1,4 +1,4 @@
-// rtiow_hip.hip -- the only translation unit compiled for gfx950.
+// rtiow_hip.hip -- the translation unit compiled for gfx950 (beside it only rtiow_upscale.hip: guided upscaling, one kernel of its own).
 //
 // Hand-written HIP for the `render` hot path of the reference tracer
 // (/root/reference/src/GlobalFloatCUDAInOneWeekend/camera.h:130-172 and the device
@@ -76,6 +76,7 @@
 #include "library/handle.h"
 #include "library/scene_tables.h"
 #include "library/launch.h"
+#include "library/pass.h"
 
 extern "C" {
 
@@ -131,20 +132,6 @@ void drop_snapshot(rtiow_handle_s* h) { h->snap_geom.clear(); h->snap_mat.clear(
 // The times a render call on a shard without rows reports.
 void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
 
-// kernel_ms: events around the work enqueued between timed_begin (or a launch that records ev0 itself) and timed_end (NULL: asynchronous,
-// nothing recorded).
-int timed_begin(rtiow_handle_s* h, float* kernel_ms) {
-    h->render_pending = false;                           // the call reuses the start / stop events of rtiow_render_async
-    if (kernel_ms) { *kernel_ms = 0; HIP_TRY(h, hipEventRecord(h->ev0, h->stream)); }
-    return 0;
-}
-int timed_end(rtiow_handle_s* h, float* kernel_ms) {
-    if (!kernel_ms) return 0;
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(h, hipEventSynchronize(h->ev1));
-    HIP_TRY(h, hipEventElapsedTime(kernel_ms, h->ev0, h->ev1));
-    return 0;
-}
 }  // namespace
 
 int rtiow_create(int device, int precision, rtiow_handle* out) {
@@ -585,14 +572,6 @@ int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, s
 namespace {
 int render_guides(rtiow_handle_s* h) {
     return by_precision(h, [&](auto t) { return launch_guides<decltype(t)>(h); });
-}
-// D2H copy of `bytes` from a device buffer on the handle's stream, then wait.  A NULL host wanted the call's checks only.
-int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
-    if (!bytes || !host) return 0;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return 0;
 }
 // What the calls that filter, reproject or plan share once they have checked their arguments and the state: the pass, enqueued by
 // pass(T()) in the handle's precision, between the events of kernel_ms and behind guides that are current (extern "C++": a template).

@@ -1,4 +1,4 @@
-"""Per-kernel resources of rtiow_hip.hip for gfx950, read from the compiler's metadata in a device-only listing (no GPU needed: hipcc
+"""Per-kernel resources of rtiow_hip.hip (or another translation unit of the library) for gfx950, read from the compiler's metadata in a device-only listing (no GPU needed: hipcc
 cross-compiles).  The register-budget tests and scripts/kernel_resources.py share it."""
 import functools
 import os
@@ -13,14 +13,14 @@ _META = re.compile(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:
 
 
 @functools.lru_cache(maxsize=None)
-def device_metadata(defines=(), keep=None):
+def device_metadata(defines=(), keep=None, source="rtiow_hip.hip"):
     """(metadata, listing text) of rtiow_hip.hip built with the product's flags plus `defines` (a tuple of -D flags), compiled once per
     process and set of arguments.  metadata maps each demangled kernel name to its scratch, sgpr, sgpr_spill, vgpr and vgpr_spill;
-    keep: a path to keep the listing at."""
+    keep: a path to keep the listing at; source: the translation unit under csrc/ (rtiow_upscale.hip holds upscale_kernel)."""
     with tempfile.TemporaryDirectory(prefix="rtiow_isa") as tmp:
         out = keep or os.path.join(tmp, "rtiow_hip.s")
         flags = [f for f in b.HIP_FLAGS if f != "-shared"]
-        subprocess.run([b._hipcc()] + flags + list(defines) + ["-S", "--cuda-device-only", "-o", out, os.path.join(b.CSRC, "rtiow_hip.hip")],
+        subprocess.run([b._hipcc()] + flags + list(defines) + ["-S", "--cuda-device-only", "-o", out, os.path.join(b.CSRC, source)],
                        check=True, stderr=subprocess.DEVNULL)
         text = open(out).read()
     found = list(_META.finditer(text))
