@@ -751,6 +751,30 @@ int rtiow_upscale(rtiow_handle h, int factor, int source, double sigma_normal, d
 int rtiow_read_upscaled(rtiow_handle h, void* host_rgb, size_t bytes);      /* (F rows) x (F W) x 3 T, gamma-encoded like the preview */
 int rtiow_upscaled_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
 
+/* ---- Wide-support guided upscaling: rtiow_upscale with a 4 x 4 cubic B-spline gather.  rtiow_upscale's four
+ * bilinear taps average less than plain interpolation does once an edge-stop takes weight from some of them; sixteen taps under a smooth,
+ * non-negative kernel average more where nothing stops them and still refuse taps across a silhouette.
+ * Everything in T, left to right as written, plain * + - /, a correctly rounded sqrt, no fused multiply-add.
+ * rtiow_upscale's, to the letter: the output pixel (I, J), i, a, j, b, o_a, o_b, the ray, hit_world, k, N, A, Z;
+ *   x0 = o_a < 0 ? i - 1 : i, gx = o_a < 0 ? (T)1 + o_a : o_a; y0, gy likewise.
+ * The taps.  The 16 traced pixels q = (x0 - 1 + u, y0 - 1 + v), u, v = 0..3, in row-major order (v outer, u inner).  Per axis, from
+ *   g (gx or gy) and h = (T)1 - g, the cubic B-spline:
+ *     c[0] = ((h*h)*h) / (T)6
+ *     c[1] = ((((T)3*g - (T)6)*g)*g + (T)4) / (T)6
+ *     c[2] = ((((T)3*h - (T)6)*h)*h + (T)4) / (T)6
+ *     c[3] = ((g*g)*g) / (T)6
+ *   b = cy[v] * cx[u].  The kernel is non-negative, so sqrt and the test b > 0 keep their meaning (g = 0: c[3] = 0, a 3 x 3 gather).
+ *   A tap counts when q is inside the frame -- tested before any load --, b > 0 and q holds colour, by rtiow_upscale's rule per source.
+ * rtiow_upscale's unchanged: c_q per source; e, w = b / ((T)1 + e), S1, W1 from 0 in tap order; the share (m, wp, Sp, Wp); the result;
+ *   the gamma store; *covered_pixels; the guides are the FIRST-HIT buffers whatever the guide mode and lens knob; stale guides and, with
+ *   the share, stale layers are rendered first inside kernel_ms; both out-pointers NULL: asynchronous on the handle's stream.
+ * The call writes the handle's upscaled buffer: rtiow_read_upscaled and rtiow_upscaled_device_ptr serve whichever of rtiow_upscale and
+ * rtiow_upscale_wide ran last, and the image goes stale by the same rule.
+ * Refusals: rtiow_upscale's, in its order, under this call's name; a sharded handle is refused; not available on groups.  A NULL
+ * handle: -1 before any device work.  A failing call leaves the handle as it was. */
+int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                       int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller
  * supply device memory (e.g. a torch tensor that torch.distributed will gather). */

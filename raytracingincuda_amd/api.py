@@ -154,6 +154,7 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_upscale": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_read_upscaled": (_H, _vp, _size),
     "rtiow_upscaled_device_ptr": (_H, _vpp, _sizep),
+    "rtiow_upscale_wide": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -488,6 +489,14 @@ UPSCALE_SIGMA_NORMAL = 0.3
 UPSCALE_SIGMA_ALBEDO = float("inf")
 UPSCALE_SIGMA_DEPTH = float("inf")
 UPSCALE_COVERAGE = 0
+# Renderer.upscale_wide defaults: the best of scripts/upscale_wide_probe.py's sweep by the same rule over the same
+# 24 settings (profiles/upscale_wide/upscale_wide_probe.json): the setting upscale() has.  At it the ratio to the
+# full-resolution frame is 0.08 / 0.07 at 1 ray and 0.40 / 0.37 at 4 (scenes 1 / 3); against bilinear interpolation of the same denoised
+# image it wins at 1 ray at factor 2 (0.91 / 0.94) and loses at 4 rays (1.14 / 1.29): it does not pay yet, and the call stays opt-in.
+UPSCALE_WIDE_SIGMA_NORMAL = 0.3
+UPSCALE_WIDE_SIGMA_ALBEDO = float("inf")
+UPSCALE_WIDE_SIGMA_DEPTH = float("inf")
+UPSCALE_WIDE_COVERAGE = 0
 
 
 def _out(ctype, wanted=True):
@@ -943,8 +952,21 @@ class Renderer:
                                             int(use_coverage), ms_out, n_out))
         return int(n.value) if sync else None
 
+    def upscale_wide(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_WIDE_SIGMA_NORMAL, sigma_albedo=UPSCALE_WIDE_SIGMA_ALBEDO,
+                     sigma_depth=UPSCALE_WIDE_SIGMA_DEPTH, use_coverage=UPSCALE_WIDE_COVERAGE, sync=True):
+        """upscale() with a wider support: every output pixel gathers the 4 x 4 traced pixels around it under the
+        cubic B-spline where upscale() gathers 2 x 2 bilinearly; the ray, the sources, the edge-stops, the share, the count returned and the
+        image's life are upscale()'s.  With every sigma float("inf") and no share it is the unguided B-spline interpolation.  It writes the
+        buffer upscale() writes: read_upscaled() serves whichever of the two ran last."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale_wide(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                 int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
     def read_upscaled(self):
-        """The image of the last upscale(), [factor * rows, factor * W, 3], gamma-encoded like the preview."""
+        """The image of the last upscale() or upscale_wide(), [factor * rows, factor * W, 3], gamma-encoded like the preview."""
         _, nbytes = self.upscaled_device_ptr()
         F = math.isqrt(nbytes // (self.local_rows * self.width * 3 * np.dtype(self.dtype).itemsize))     # the buffer holds F x F traced frames
         out = np.empty((F * self.local_rows, F * self.width, 3), self.dtype)

@@ -2,8 +2,9 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone)
-// Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, and of rtiow_upscale.hip for launch_upscale (internal linkage).
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip alone)
+// Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, of rtiow_upscale.hip for launch_upscale and of rtiow_upscale_wide.hip
+// for launch_upscale_wide (internal linkage).
 #pragma once
 #include "scene_tables.h"
 #include "../device/render_kernels.h"
@@ -19,6 +20,7 @@
 #include "../device/temporal_noise.h"
 #include "../device/edge_resolve.h"
 #include "../device/upscale.h"
+#include "../device/upscale_wide.h"
 
 namespace {
 
@@ -769,6 +771,43 @@ int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[
     HIP_TRY(h, allow_lds(k, lds));
     const int tiles = ((L.p.cold.W * factor + 7) / 8) * ((h->local_rows * factor + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), lds, h->stream, L.p, u, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
+    HIP_TRY(h, hipGetLastError());
+    h->upscaled_bytes = out_bytes;
+    on_upscaled(h->preview, factor);
+    return 0;
+}
+
+// upscale_wide_kernel over the traced frame into h->upscaled (rtiow_upscale_wide): launch_upscale's arguments, buffers and counters, one
+// workgroup of 256 per 16 x 16 block of the factor x larger image.  Behind the staged scene the LDS holds the block's footprint of traced
+// pixels (upscale_wide_stage_bytes) and, behind that, the word per wave of the count.  The caller has checked state and arguments --
+// out_bytes is check_upscale_extent's, whose limits on 8 x 8 tiles hold a fortiori for 16 x 16 blocks -- and made the guides and, with
+// use_coverage, the layers current.
+template <class T>
+int launch_upscale_wide(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+    Launch<T> L{make_params<T>(h)};
+    const int threads = 256;
+    int rc = layout_lds<T>(h, L, threads, false, false);
+    if (rc) return rc;
+    const size_t stage_offset = (L.lds + 15) / 16 * 16, tally_offset = stage_offset + upscale_wide_stage_bytes<T>(), lds = tally_offset + UPSCALE_TALLY_BYTES;
+    if (lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
+    HIP_TRY(h, h->upscaled.ensure(out_bytes));
+    constexpr size_t ctr_bytes = (size_t)UPSCALE_COUNTERS * UPSCALE_COUNTER_STRIDE * sizeof(unsigned);
+    HIP_TRY(h, h->upscale_ctr.ensure(ctr_bytes));
+    HIP_TRY(h, hipMemsetAsync(h->upscale_ctr, 0, ctr_bytes, h->stream));
+    UpscaleParams<T> u{};
+    u.F = factor; u.source = source; u.use_coverage = use_coverage;
+    u.S = h->preview.coverage_grid * h->preview.coverage_grid;
+    u.i_n = (T)inv2[0]; u.i_a = (T)inv2[1]; u.i_z = (T)inv2[2];
+    u.tally_offset = (int)tally_offset;
+    if (source == RTIOW_UPSCALE_LINEAR) accumulation_source(h, u.mid, u.counts, u.n_uniform);
+    if (source == RTIOW_UPSCALE_DENOISED) u.g = h->denoised.as<const T>();
+    if (source == RTIOW_UPSCALE_HISTORY) u.cm = h->hist_cm.as<const Vec4<T>>();
+    u.nd = h->guide_nd.as<const Vec4<T>>(); u.alb = h->guide_alb.as<const Vec4<T>>();
+    u.ic = use_coverage ? h->cov_ic.as<const int4>() : nullptr;
+    const auto k = by_source(L.lds_source, [](auto src) { return upscale_wide_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, lds));
+    const int blocks = ((L.p.cold.W * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK) * ((h->local_rows * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, L.p, u, (int)stage_offset, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
     HIP_TRY(h, hipGetLastError());
     h->upscaled_bytes = out_bytes;
     on_upscaled(h->preview, factor);

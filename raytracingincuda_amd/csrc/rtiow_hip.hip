@@ -1,4 +1,5 @@
-// rtiow_hip.hip -- the translation unit compiled for gfx950 (beside it only rtiow_upscale.hip: guided upscaling, one kernel of its own).
+// rtiow_hip.hip -- the translation unit compiled for gfx950 (beside it only rtiow_upscale.hip and rtiow_upscale_wide.hip: guided upscaling, one kernel of
+// its own each).
 //
 // Hand-written HIP for the `render` hot path of the reference tracer
 // (/root/reference/src/GlobalFloatCUDAInOneWeekend/camera.h:130-172 and the device

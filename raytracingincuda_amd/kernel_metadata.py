@@ -16,7 +16,8 @@ _META = re.compile(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:
 def device_metadata(defines=(), keep=None, source="rtiow_hip.hip"):
     """(metadata, listing text) of rtiow_hip.hip built with the product's flags plus `defines` (a tuple of -D flags), compiled once per
     process and set of arguments.  metadata maps each demangled kernel name to its scratch, sgpr, sgpr_spill, vgpr and vgpr_spill;
-    keep: a path to keep the listing at; source: the translation unit under csrc/ (rtiow_upscale.hip holds upscale_kernel)."""
+    keep: a path to keep the listing at; source: the translation unit under csrc/ (rtiow_upscale.hip holds upscale_kernel,
+    rtiow_upscale_wide.hip upscale_wide_kernel)."""
     with tempfile.TemporaryDirectory(prefix="rtiow_isa") as tmp:
         out = keep or os.path.join(tmp, "rtiow_hip.s")
         flags = [f for f in b.HIP_FLAGS if f != "-shared"]

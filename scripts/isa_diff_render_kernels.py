@@ -3,6 +3,7 @@
     python scripts/isa_diff_render_kernels.py --ref HEAD~1        # the tree at a git ref (exported with git archive) against the working tree
     python scripts/isa_diff_render_kernels.py BEFORE.s AFTER.s    # two `hipcc -S --cuda-device-only` listings
     python scripts/isa_diff_render_kernels.py --ref HEAD~1 --summary    # ... and what changed in each kernel that differs
+    python scripts/isa_diff_render_kernels.py --ref HEAD~1 --unit rtiow_upscale.hip    # another translation unit than rtiow_hip.hip
 
 Every function of the older listing is cut from its label to its .Lfunc_end and compared text for text with the newer one's, after the
 function-local labels (.LBB<n>_<k>, .Lfunc_end<n>: n follows the order in which the module instantiates the functions) are renumbered
@@ -30,10 +31,10 @@ FP = re.compile(r"_f32|_f64|rcp|sqrt|div_|floor|cvt")
 RESOURCES = (("vgpr", "vgpr_count"), ("sgpr spills", "sgpr_spill_count"), ("vgpr spills", "vgpr_spill_count"), ("scratch", "private_segment_fixed_size"))
 
 
-def listing(src_root, out):
+def listing(src_root, out, unit="rtiow_hip.hip"):
     from raytracingincuda_amd import build as b
     flags = [f for f in b.HIP_FLAGS if f != "-shared" and not f.startswith("-I")] + ["-I" + os.path.join(src_root, "include")]
-    subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(src_root, "raytracingincuda_amd", "csrc", "rtiow_hip.hip")],
+    subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(src_root, "raytracingincuda_amd", "csrc", unit)],
                    check=True, stderr=subprocess.DEVNULL)
     return out
 
@@ -82,6 +83,7 @@ def main():
     ap.add_argument("listings", nargs="*")
     ap.add_argument("--ref", default="")
     ap.add_argument("--summary", action="store_true")
+    ap.add_argument("--unit", default="rtiow_hip.hip")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         if a.ref:
@@ -90,7 +92,7 @@ def main():
             old_root = os.path.join(tmp, "ref")
             with tarfile.open(tar) as t:
                 t.extractall(old_root)
-            before, after = listing(old_root, os.path.join(tmp, "before.s")), listing(ROOT, os.path.join(tmp, "after.s"))
+            before, after = listing(old_root, os.path.join(tmp, "before.s"), a.unit), listing(ROOT, os.path.join(tmp, "after.s"), a.unit)
         elif len(a.listings) == 2:
             before, after = a.listings
         else:
