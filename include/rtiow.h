@@ -49,6 +49,9 @@ extern "C" {
                                  * lane walks the cells its ray crosses and tests only their spheres,
                                  * exactly; big spheres are tested by every ray.  Same image bit for
                                  * bit.  Scenes the grid does not suit run as RTIOW_SCENE_LDS.     */
+#define RTIOW_SCENE_DEVICE_GRID 4 /* rtiow_render_large only (rtiow_set_scene_source refuses it): a uniform grid
+                                 * whose cells, index lists and spheres stay in device memory; what
+                                 * rtiow_stats.scene_source reads after that call                    */
 
 /* Pixel scheduling (same image either way):
  * STATIC     = the reference's launch geometry: grid of T x T blocks, one lane per pixel
@@ -774,6 +777,38 @@ int rtiow_upscaled_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
  * handle: -1 before any device work.  A failing call leaves the handle as it was. */
 int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
                        int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+
+/* ---- Large scenes: rtiow_render through a uniform grid walked in device memory.
+ * rtiow_render is fast while a scene's tables fit a compute unit's LDS; beyond that (about 5 100 spheres in fp32, 3 400 in fp64) it reads
+ * the scene through the exact loop over every sphere (rtiow_stats.scene_source == RTIOW_SCENE_SCALAR).  rtiow_render_large renders the
+ * same frame -- same framebuffer, shard, RNG states in and out, rtiow_stats -- with only the spheres too big for a grid cell in LDS and
+ * everything else in a grid in device memory: variable-length cells of 32-bit sphere indices, no limit on spheres per cell, up to 2^20
+ * cells.  Every pixel draws its numbers in the reference's order from its own state: the image is rtiow_render's bit for bit.
+ * Opt-in: rtiow_render never selects it, the knobs of rtiow_set_scene_source and rtiow_set_schedule do not apply (the launch is the
+ * persistent hand-out in tile order; rtiow_stats.schedule reads RTIOW_SCHED_PERSISTENT, scene_source RTIOW_SCENE_DEVICE_GRID, and the
+ * grid_* fields describe the device grid).  Plan and device tables are built at the first call after rtiow_set_scene /
+ * rtiow_edit_scene(_mapped), before the start event; the time goes to rtiow_stats.scene_prepare_ms.
+ * kernel_ms NULL: asynchronous on the handle's stream.  RTIOW_E_BADARG, with the call's name in rtiow_last_error_string, without a
+ * scene or a camera and when the grid does not suit the scene (fewer than 24 spheres, fewer than 16 of them small enough for a cell,
+ * or a list of big spheres longer than max(8, n / 6) or 2048): use rtiow_render -- there is no silent fall-back.  RTIOW_E_STATE
+ * before rtiow_init_rng.
+ * The accumulate / adaptive / budget calls, every preview call and the groups keep rtiow_render's sources. */
+int rtiow_render_large(rtiow_handle h, float* kernel_ms);
+typedef struct {
+    int32_t  usable;             /* 1: rtiow_render_large renders this scene; 0: it refuses (every other field is then 0)  */
+    int32_t  nx, nz;             /* cells along x and z                                                                    */
+    double   cell;               /* cell width                                                                             */
+    double   rfar;               /* origins farther than this from the scene's centre send their wave through the exact loop */
+    int32_t  registered;         /* spheres in cells (each in up to 2 x 2 of them)                                         */
+    int32_t  direct;             /* spheres too big for a cell: in LDS, tested by every ray                                */
+    uint64_t index_entries;      /* length of the index array: the sum of the cells' list lengths                          */
+    int32_t  longest_list;       /* spheres in the fullest cell                                                            */
+    int32_t  reserved;
+    uint64_t blob_bytes;         /* device memory of cells, indices, sphere table and direct list                          */
+} rtiow_large_grid_info;
+/* The device grid of the handle's scene in the handle's precision, built here if no rtiow_render_large has built it yet (host work and one
+ * upload; no kernel).  RTIOW_E_BADARG without a scene. */
+int rtiow_read_large_grid(rtiow_handle h, rtiow_large_grid_info* out);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

@@ -78,6 +78,17 @@ int rtiow_debug_jump_matrices(uint32_t* out_words, size_t cap_words, int from_sc
  * use the grid for this scene, 0 when it keeps the screened loop, negative on bad arguments. */
 int rtiow_debug_grid_plan(int n, const double* center_radius, const double* centre3, int32_t* dims4, double* params8,
                           uint16_t* cells, size_t cells_cap, int32_t* direct, size_t direct_cap, double* halfwidth);
+/* The device grid's plan (rtiow_render_large, csrc/library/device_grid.h) for n spheres {cx,cy,cz,r} (doubles) around the recentring
+ * point centre3, as the library builds it.  Host arithmetic only (no GPU needed).  dims6 = {nx, nz, registered spheres, direct-list
+ * length, index entries, longest cell list}; params8 as rtiow_debug_grid_plan's; cells (optional) = nx*nz {first, count} pairs into
+ * indices (optional); direct (optional) = the direct list; halfwidth (optional, n entries).  A first call with NULL buffers gives the
+ * sizes.  Returns 1 when rtiow_render_large would render the scene, 0 when it would refuse, negative on bad arguments. */
+int rtiow_debug_large_grid_plan(int n, const double* center_radius, const double* centre3, int32_t* dims6, double* params8,
+                                uint32_t* cells, size_t cells_cap, uint32_t* indices, size_t indices_cap, int32_t* direct, size_t direct_cap, double* halfwidth);
+/* rtiow_debug_hit_world through the device grid of rtiow_render_large (whatever the handle's scene source), and per ray the number of
+ * cells its walk read, or -1 when its wave took the exact loop (a far, NaN or huge ray among its 64).  RTIOW_E_BADARG when the grid
+ * does not suit the scene. */
+int rtiow_debug_hit_world_large(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out, int32_t* cells_out);
 
 /* Test hook, host only (no GPU, no RCCL): the exchange's schedule -- the very function rtiow_group_gather runs --
  * against a recording table instead of HIP / RCCL, for n ranks on `devices` with `rows` local rows each.

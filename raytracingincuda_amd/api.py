@@ -24,6 +24,7 @@ import numpy as np
 
 LAMBERTIAN, METAL, DIELECTRIC = 0, 1, 2
 SCENE_LDS, SCENE_SCALAR, SCENE_LDS_EXACT, SCENE_GRID = 0, 1, 2, 3
+SCENE_DEVICE_GRID = 4                                       # what stats()["scene_source"] reads after render_large(); set_scene_source refuses it
 SCHED_STATIC, SCHED_PERSISTENT, SCHED_SORTED = 0, 1, 2
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER, GATHER_HOST = 0, 1, 2, 3
 GUIDES_FIRST_HIT, GUIDES_SPECULAR = 0, 1  # rtiow_set_guide_mode
@@ -77,6 +78,13 @@ class Stats(ctypes.Structure):
                 ("staged_stores", ctypes.c_int32), ("num_cus", ctypes.c_int32), ("place_ms", ctypes.c_double),
                 ("clock_mhz", ctypes.c_int32), ("order_reused", ctypes.c_int32),
                 ("main_clock_mhz", ctypes.c_double), ("prepass_clock_mhz", ctypes.c_double), ("main_wave0_ms", ctypes.c_double)]
+
+
+class LargeGridInfo(ctypes.Structure):
+    """rtiow_large_grid_info (include/rtiow.h)."""
+    _fields_ = [("usable", ctypes.c_int32), ("nx", ctypes.c_int32), ("nz", ctypes.c_int32), ("cell", ctypes.c_double), ("rfar", ctypes.c_double),
+                ("registered", ctypes.c_int32), ("direct", ctypes.c_int32), ("index_entries", ctypes.c_uint64), ("longest_list", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("blob_bytes", ctypes.c_uint64)]
 
 
 class GroupStats(ctypes.Structure):
@@ -155,6 +163,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_read_upscaled": (_H, _vp, _size),
     "rtiow_upscaled_device_ptr": (_H, _vpp, _sizep),
     "rtiow_upscale_wide": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
+    "rtiow_render_large": (_H, _f32p),
+    "rtiow_read_large_grid": (_H, ctypes.POINTER(LargeGridInfo)),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -198,6 +208,8 @@ DEBUG_ABI = {
     "rtiow_debug_scatter": (_H, _int, _int, _vp, _i32p, _u32p, _vp, _i32p, _u32p, _intp),
     "rtiow_debug_jump_matrices": (_u32p, _size, _int),
     "rtiow_debug_grid_plan": (_int, _f64p, _f64p, _i32p, _f64p, _u16p, _size, _i32p, _size, _f64p),
+    "rtiow_debug_large_grid_plan": (_int, _f64p, _f64p, _i32p, _f64p, _u32p, _size, _u32p, _size, _i32p, _size, _f64p),
+    "rtiow_debug_hit_world_large": (_H, _int, _vp, _vp, _i32p, _i32p),
     "rtiow_debug_gather_schedule": (_int, _intp, _intp, _int, _int, _int, _int, _i64p, _size, _intp),
 }
 HOST_ABI = {                                                # include/rtiow_host.h: librtiow_host.so
@@ -634,6 +646,17 @@ class Renderer:
         self._check(self._lib.rtiow_debug_hit_world(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data_as(_i32p)))
         return t, idx
 
+    def debug_hit_world_large(self, rays):
+        """debug_hit_world() through the device grid of render_large(): (t [n], sphere index [n], cells [n]) -- cells: how many cells the
+        ray's walk read, or -1 when its wave took the exact loop."""
+        self._need_debug()
+        dt = _dtype(self.precision)
+        rays = np.ascontiguousarray(rays, dt)
+        n = rays.shape[0]
+        t = np.zeros(n, dt); idx = np.zeros(n, np.int32); cells = np.zeros(n, np.int32)
+        self._check(self._lib.rtiow_debug_hit_world_large(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data_as(_i32p), cells.ctypes.data_as(_i32p)))
+        return t, idx, cells
+
     def debug_scatter(self, form, O, D, closest, hit, atten, sky_uy, depth, states):
         """The scatter step alone, one call per lane (calls 64 w ... 64 w + 63 share wave w), from caller-supplied (closest, hit).
         form 0: shade_step; 1: the bounded shade_step until it stops retrying; 2 (fp64): shade_front, merged_rounds, shade_back.
@@ -677,6 +700,21 @@ class Renderer:
         ms, ms_out = _out(ctypes.c_float, sync)
         self._check(self._lib.rtiow_render(self._h, int(threads), ms_out))
         return ms.value if sync else None
+
+    def render_large(self, sync=True):
+        """render() through a uniform grid walked in device memory, for scenes whose tables outgrow a compute
+        unit's LDS: the same framebuffer, bit for bit.  Raises RtiowError (RTIOW_E_BADARG) when the grid does not suit the scene -- use
+        render() then.  Returns the HIP-event kernel time in ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_large(self._h, ms_out))
+        return ms.value if sync else None
+
+    def large_grid(self):
+        """The device grid render_large() uses for the current scene: a dict of usable, nx, nz, cell, rfar, registered, direct,
+        index_entries, longest_list and blob_bytes (all 0 when the grid does not suit the scene)."""
+        info = LargeGridInfo()
+        self._check(self._lib.rtiow_read_large_grid(self._h, ctypes.byref(info)))
+        return {name: getattr(info, name) for name, _ in LargeGridInfo._fields_ if name != "reserved"}
 
     def accumulate(self, samples, threads=0, sync=True):
         """Progressive rendering: add `samples` samples per pixel to the accumulation and write the preview to the framebuffer (bit for bit
@@ -1128,6 +1166,36 @@ class Renderer:
         out = np.empty_like(a)
         self._check(self._lib.rtiow_debug_ops(self._h, op, a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
         return out
+
+
+def debug_large_grid_plan(center_radius, centre=None, tables=False):
+    """The device grid's plan (render_large) for spheres [n, 4] = {cx, cy, cz, r} around `centre` (default: the library's own recentring
+    point, the centroid of the finite spheres with r < 100 rounded to fp32), on the host: no GPU needed.  A dict of usable, nx, nz,
+    registered, direct, index_entries, longest_list, x0, z0, cell, ylo, yhi, rfar, eps, cmax; tables=True adds cells [nz, nx, 2]
+    ({first, count}), indices, direct_list and halfwidth."""
+    lib = load_hip_library(debug=True)
+    cr = np.ascontiguousarray(center_radius, np.float64).reshape(-1, 4)
+    n = len(cr)
+    if centre is None:
+        keep = (cr[:, 3] < 100.0) & np.isfinite(cr[:, :3]).all(axis=1)
+        centre = cr[keep, :3].mean(axis=0).astype(np.float32) if keep.any() else np.zeros(3)
+    centre = np.ascontiguousarray(centre, np.float64)
+    dims, params = (ctypes.c_int32 * 6)(), (ctypes.c_double * 8)()
+    args = (n, cr.ctypes.data_as(_f64p), centre.ctypes.data_as(_f64p), dims, params)
+    rc = lib.rtiow_debug_large_grid_plan(*args, None, 0, None, 0, None, 0, None)
+    if rc < 0:
+        raise RtiowError(rc, "rtiow_debug_large_grid_plan")
+    out = dict(zip(("nx", "nz", "registered", "direct", "index_entries", "longest_list"), dims), usable=bool(rc))
+    out.update(zip(("x0", "z0", "cell", "ylo", "yhi", "rfar", "eps", "cmax"), params))
+    if tables and out["nx"] > 0:
+        cells = np.zeros((out["nz"], out["nx"], 2), np.uint32); indices = np.zeros(max(1, out["index_entries"]), np.uint32)
+        direct = np.zeros(max(1, out["direct"]), np.int32); half = np.zeros(n, np.float64)
+        rc = lib.rtiow_debug_large_grid_plan(*args, cells.ctypes.data_as(_u32p), cells.size, indices.ctypes.data_as(_u32p), indices.size,
+                                             direct.ctypes.data_as(_i32p), direct.size, half.ctypes.data_as(_f64p))
+        if rc < 0:
+            raise RtiowError(rc, "rtiow_debug_large_grid_plan")
+        out.update(cells=cells, indices=indices[:out["index_entries"]], direct_list=direct[:out["direct"]], halfwidth=half)
+    return out
 
 
 def debug_gather_schedule(devices, rows, width, precision=32, mode=GATHER_RCCL, fail_at=-1, fallback=False):

@@ -31,6 +31,7 @@ struct Options {
     bool have_scene = false, help = false;
     int scene_id = 0, width = 320, height = 192, samples = 10, bounces = 25, threads = 8;   // main.cu:45-54
     int scene_source = RTIOW_SCENE_GRID;
+    bool large = false;                 // --scene_source device_grid: rtiow_render_large instead of rtiow_render (one GPU only)
     bool stats = false;
     bool binary_ppm = false;
     int schedule = RTIOW_SCHED_SORTED;
@@ -94,6 +95,7 @@ Options parse(int argc, char** argv) {
             if (value == "grid") o.scene_source = RTIOW_SCENE_GRID;
             else if (value == "lds") o.scene_source = RTIOW_SCENE_LDS;
             else if (value == "scalar") o.scene_source = RTIOW_SCENE_SCALAR;
+            else if (value == "device_grid") o.large = true;
             else parse_abort("Argument '" + value + "' failed to parse");
             continue;
         }
@@ -266,6 +268,10 @@ int main(int argc, char** argv) {
         std::fputs(kUsage, stdout); std::fputs("\n", stdout);
         return 1;
     }
+    if (opt.large && (opt.gpus != 0 || !opt.devices.empty())) {
+        std::fputs("Error: --scene_source device_grid renders on one GPU (no --gpus / --devices).\n", stderr);
+        return 1;
+    }
     if (opt.gpus != 0 || !opt.devices.empty()) return main_multi_gpu(opt);
     const int precision = RTIOW_PRECISION;
     const size_t elem = precision == 64 ? 8 : 4;
@@ -311,7 +317,7 @@ int main(int argc, char** argv) {
         check(h, rtiow_render(h, opt.threads, &render_ms));
         check(h, rtiow_init_rng(h, 1227));
     }
-    check(h, rtiow_render(h, opt.threads, &render_ms));
+    check(h, opt.large ? rtiow_render_large(h, &render_ms) : rtiow_render(h, opt.threads, &render_ms));
     std::printf("%15.8f,", (double)render_ms);
     std::fflush(stdout);
     const double t_render = lap();
@@ -375,7 +381,7 @@ int main(int argc, char** argv) {
                      "\"launch_ms\": {\"prepass\": %.4f, \"main\": %.4f, \"place\": %.4f}, \"clock_mhz\": {\"nominal\": %d, \"prepass\": %.0f, \"main\": %.0f, \"main_wave0_ms\": %.3f}, "
                      "\"wall_ms\": {\"setup\": %.3f, \"rng_init\": %.3f, \"render\": %.3f, \"readback\": %.3f, \"ppm_write\": %.3f, \"destroy\": %.3f, \"end_to_end\": %.3f}, \"destroy_overlaps\": \"ppm_write\"}\n",
                      render_ms > 0 ? rays / render_ms / 1e3 : 0.0, (double)render_ms, st.rng_init_ms, st.num_spheres,
-                     st.block_x, st.block_y, st.vgprs, st.lds_bytes, st.scene_source == RTIOW_SCENE_GRID ? "grid" : (st.scene_source == RTIOW_SCENE_SCALAR ? "scalar" : "lds"), st.solo_waves, st.scene_prepare_ms,
+                     st.block_x, st.block_y, st.vgprs, st.lds_bytes, st.scene_source == RTIOW_SCENE_DEVICE_GRID ? "device_grid" : (st.scene_source == RTIOW_SCENE_GRID ? "grid" : (st.scene_source == RTIOW_SCENE_SCALAR ? "scalar" : "lds")), st.solo_waves, st.scene_prepare_ms,
                      st.prepass_ms, st.main_ms, st.place_ms, st.clock_mhz, st.prepass_clock_mhz, st.main_clock_mhz, st.main_wave0_ms,
                      t_setup, t_rng, t_render, t_read, t_write, t_destroy, e2e_ms);
     }

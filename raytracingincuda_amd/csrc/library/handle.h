@@ -173,6 +173,14 @@ struct rtiow_handle_s {
     DeviceBuffer<> upscaled;
     size_t upscaled_bytes = 0;
     DeviceBuffer<unsigned> upscale_ctr;
+    // large scenes (rtiow_render_large, rtiow_large.hip): the device grid of the current scene -- blob, its description with offsets
+    // relative to the blob, the recentring point and what rtiow_read_large_grid reports -- built at first use after an upload
+    // (large_dirty, set by upload_scene)
+    DeviceBuffer<> large_blob;
+    GridParams large_grid{};
+    double large_ctr[3] = {0, 0, 0};
+    bool large_dirty = true;
+    rtiow_large_grid_info large_info{};
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;
