@@ -46,6 +46,15 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+# The translation units of librtiow_hip.so, in link order (the build id hashes them in this order).
+HIP_UNITS = ("rtiow_hip.hip", "rtiow_group.hip", "rtiow_upscale.hip", "rtiow_upscale_wide.hip", "rtiow_large.hip")
+
+
+def hip_units(csrc=None):
+    """The paths of HIP_UNITS in `csrc` (default: this tree's csrc/)."""
+    return [os.path.join(csrc or CSRC, u) for u in HIP_UNITS]
+
+
 def hip_includes():
     """The device / library headers rtiow_hip.hip is made of (csrc/device, csrc/library)."""
     out = []
@@ -61,7 +70,7 @@ def hip_build_id(extra_flags=()):
     they were measured on; bench.py uses a record only when it matches the library that is loaded."""
     import hashlib
     h = hashlib.sha256()
-    files = [os.path.join(CSRC, "rtiow_hip.hip"), os.path.join(CSRC, "rtiow_group.hip"), os.path.join(CSRC, "rtiow_upscale.hip"), os.path.join(CSRC, "rtiow_upscale_wide.hip"), os.path.join(CSRC, "rtiow_large.hip")] + hip_includes() + [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_debug.h")]
+    files = hip_units() + hip_includes() + [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_debug.h")]
     for f in files:
         h.update(os.path.relpath(f, ROOT).encode() + b"\0")
         h.update(open(f, "rb").read())
@@ -83,7 +92,7 @@ def build_stats(verbose=True):
     (lib/librtiow_hip_stats.so, -DRTIOW_PATH_STATS; used by scripts/path_stats_probe.py only)."""
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, "librtiow_hip_stats.so")
-    _run([_hipcc()] + HIP_FLAGS + ["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API", '-DRTIOW_BUILD_ID="%s"' % hip_build_id(["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API"]), "-o", out, os.path.join(CSRC, "rtiow_hip.hip"), os.path.join(CSRC, "rtiow_group.hip"), os.path.join(CSRC, "rtiow_upscale.hip"), os.path.join(CSRC, "rtiow_upscale_wide.hip"), os.path.join(CSRC, "rtiow_large.hip")] + HIP_LINK, verbose)
+    _run([_hipcc()] + HIP_FLAGS + ["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API", '-DRTIOW_BUILD_ID="%s"' % hip_build_id(["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API"]), "-o", out] + hip_units() + HIP_LINK, verbose)
     return out
 
 
@@ -95,7 +104,7 @@ def build_variant(name, defines=(), csrc=None, verbose=True):
     src = csrc or CSRC
     out = os.path.join(out_dir, name + ".so")
     flags = [f for f in HIP_FLAGS if not f.startswith("-I")] + ["-I" + (os.path.join(os.path.dirname(os.path.dirname(src)), "include") if csrc else INC)]
-    _run([_hipcc()] + flags + list(defines) + ['-DRTIOW_BUILD_ID="variant:%s"' % name, "-o", out, os.path.join(src, "rtiow_hip.hip"), os.path.join(src, "rtiow_group.hip")] + [f for f in [os.path.join(src, "rtiow_upscale.hip"), os.path.join(src, "rtiow_upscale_wide.hip"), os.path.join(src, "rtiow_large.hip")] if os.path.exists(f)] + HIP_LINK, verbose)
+    _run([_hipcc()] + flags + list(defines) + ['-DRTIOW_BUILD_ID="variant:%s"' % name, "-o", out] + [f for f in hip_units(src) if os.path.exists(f)] + HIP_LINK, verbose)
     return out
 
 
@@ -105,7 +114,7 @@ def build(force=False, verbose=True):
     headers = [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_host.h"), os.path.join(INC, "rtiow_debug.h")]
     me = os.path.abspath(__file__)
 
-    hip_srcs = [os.path.join(CSRC, "rtiow_hip.hip"), os.path.join(CSRC, "rtiow_group.hip"), os.path.join(CSRC, "rtiow_upscale.hip"), os.path.join(CSRC, "rtiow_upscale_wide.hip"), os.path.join(CSRC, "rtiow_large.hip")]
+    hip_srcs = hip_units()
     hip_so = os.path.join(LIB, "librtiow_hip.so")
     if force or _newer(hip_so, hip_srcs + hip_includes() + [me, os.path.join(CSRC, "librtiow_hip.map")] + headers):
         # librccl is NOT linked: rtiow_group.hip dlopens it on first use (-ldl for old glibc)

@@ -2,7 +2,7 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip alone)
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; prepare_upscale / finish_upscale: what the upscale launches share; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip alone); upscale_call: the body of both entry points
 // Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, of rtiow_upscale.hip for launch_upscale and of rtiow_upscale_wide.hip
 // for launch_upscale_wide (internal linkage).
 #pragma once
@@ -738,21 +738,29 @@ int launch_edge_resolve(rtiow_handle_s* h, int radius, const double inv2[2], dou
     return 0;
 }
 
-// upscale_kernel over the traced frame into h->upscaled (rtiow_upscale): the layout of launch_guides with one word per wave behind it for
-// the count, one 8x8 tile of the factor x larger image per wave.  source picks the colour (RTIOW_UPSCALE_*: the denoised image, the
-// accumulation's records and counts, the temporal image); the guides are the FIRST-HIT buffers whatever the guide mode; inv2[3] = 1 /
-// sigma^2 of normal, albedo, depth (double), rounded to T here.  h->upscale_ctr holds the number of output pixels the share decided, in
-// UPSCALE_COUNTERS words that rtiow_upscale sums.  The
-// caller has checked state and arguments -- out_bytes is check_upscale_extent's -- and made the guides and, with use_coverage, the layers
-// current.
+// What launch_upscale and launch_upscale_wide share.  source picks the colour (RTIOW_UPSCALE_*: the denoised image, the accumulation's
+// records and counts, the temporal image); the guides are the FIRST-HIT buffers whatever the guide mode; inv2[3] = 1 / sigma^2 of normal,
+// albedo, depth (double), rounded to T here.  h->upscale_ctr holds the number of output pixels the share decided, in UPSCALE_COUNTERS
+// words that upscale_call sums.  The caller has checked state and arguments -- out_bytes is check_upscale_extent's -- and made the guides
+// and, with use_coverage, the layers current.
 template <class T>
-int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
-    Launch<T> L{make_params<T>(h)};
-    const int threads = 256;
-    int rc = layout_lds<T>(h, L, threads, false, false);
+struct UpscaleLaunch {
+    Launch<T> L;
+    UpscaleParams<T> u;         // all but tally_offset, which follows from the kernel's own LDS layout
+    size_t own_offset = 0;      // where the kernel's own_lds bytes begin, behind the staged scene
+    size_t lds = 0;             // own_offset + own_lds
+};
+
+// Parameters, the layout of launch_guides with the kernel's own_lds bytes behind it, h->upscaled, the zeroed counters and u.  A scene that
+// does not fit is refused here, before h->upscaled is touched: growing it loses the image of an earlier call, which stays readable.
+template <class T>
+int prepare_upscale(rtiow_handle_s* h, UpscaleLaunch<T>& U, size_t own_lds, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+    U.L = Launch<T>{make_params<T>(h)};
+    int rc = layout_lds<T>(h, U.L, 64 * UPSCALE_WAVES, false, false);
     if (rc) return rc;
-    const size_t tally_offset = (L.lds + 15) / 16 * 16, lds = tally_offset + UPSCALE_TALLY_BYTES;
-    if (lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
+    U.own_offset = (U.L.lds + 15) / 16 * 16;
+    U.lds = U.own_offset + own_lds;
+    if (U.lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
     HIP_TRY(h, h->upscaled.ensure(out_bytes));
     constexpr size_t ctr_bytes = (size_t)UPSCALE_COUNTERS * UPSCALE_COUNTER_STRIDE * sizeof(unsigned);
     HIP_TRY(h, h->upscale_ctr.ensure(ctr_bytes));
@@ -761,57 +769,52 @@ int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[
     u.F = factor; u.source = source; u.use_coverage = use_coverage;
     u.S = h->preview.coverage_grid * h->preview.coverage_grid;
     u.i_n = (T)inv2[0]; u.i_a = (T)inv2[1]; u.i_z = (T)inv2[2];
-    u.tally_offset = (int)tally_offset;
     if (source == RTIOW_UPSCALE_LINEAR) accumulation_source(h, u.mid, u.counts, u.n_uniform);
     if (source == RTIOW_UPSCALE_DENOISED) u.g = h->denoised.as<const T>();
     if (source == RTIOW_UPSCALE_HISTORY) u.cm = h->hist_cm.as<const Vec4<T>>();
     u.nd = h->guide_nd.as<const Vec4<T>>(); u.alb = h->guide_alb.as<const Vec4<T>>();
     u.ic = use_coverage ? h->cov_ic.as<const int4>() : nullptr;
-    const auto k = by_source(L.lds_source, [](auto src) { return upscale_kernel<T, src>; });
-    HIP_TRY(h, allow_lds(k, lds));
-    const int tiles = ((L.p.cold.W * factor + 7) / 8) * ((h->local_rows * factor + 7) / 8);
-    hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), lds, h->stream, L.p, u, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
+    U.u = u;
+    return 0;
+}
+
+// Behind the enqueue: the image is there, at this factor.
+inline int finish_upscale(rtiow_handle_s* h, int factor, size_t out_bytes) {
     HIP_TRY(h, hipGetLastError());
     h->upscaled_bytes = out_bytes;
     on_upscaled(h->preview, factor);
     return 0;
 }
 
-// upscale_wide_kernel over the traced frame into h->upscaled (rtiow_upscale_wide): launch_upscale's arguments, buffers and counters, one
-// workgroup of 256 per 16 x 16 block of the factor x larger image.  Behind the staged scene the LDS holds the block's footprint of traced
-// pixels (upscale_wide_stage_bytes) and, behind that, the word per wave of the count.  The caller has checked state and arguments --
-// out_bytes is check_upscale_extent's, whose limits on 8 x 8 tiles hold a fortiori for 16 x 16 blocks -- and made the guides and, with
-// use_coverage, the layers current.
+// upscale_kernel over the traced frame into h->upscaled (rtiow_upscale): one word per wave behind the staged scene for the count, one 8x8
+// tile of the factor x larger image per wave.
+template <class T>
+int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+    UpscaleLaunch<T> U;
+    if (int rc = prepare_upscale<T>(h, U, UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
+    U.u.tally_offset = (int)U.own_offset;
+    const auto k = by_source(U.L.lds_source, [](auto src) { return upscale_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, U.lds));
+    const int tiles = ((U.L.p.cold.W * factor + 7) / 8) * ((h->local_rows * factor + 7) / 8);
+    hipLaunchKernelGGL(k, dim3((unsigned)((tiles + UPSCALE_WAVES - 1) / UPSCALE_WAVES)), dim3(64 * UPSCALE_WAVES), U.lds, h->stream, U.L.p, U.u, h->upscaled.as<T>(),
+                       (unsigned*)h->upscale_ctr);
+    return finish_upscale(h, factor, out_bytes);
+}
+
+// upscale_wide_kernel over the traced frame into h->upscaled (rtiow_upscale_wide): one workgroup of 256 per 16 x 16 block of the factor x
+// larger image.  Behind the staged scene the LDS holds the block's footprint of traced pixels (upscale_wide_stage_bytes) and, behind that,
+// the word per wave of the count.  check_upscale_extent's limits on 8 x 8 tiles hold a fortiori for 16 x 16 blocks.
 template <class T>
 int launch_upscale_wide(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
-    Launch<T> L{make_params<T>(h)};
-    const int threads = 256;
-    int rc = layout_lds<T>(h, L, threads, false, false);
-    if (rc) return rc;
-    const size_t stage_offset = (L.lds + 15) / 16 * 16, tally_offset = stage_offset + upscale_wide_stage_bytes<T>(), lds = tally_offset + UPSCALE_TALLY_BYTES;
-    if (lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
-    HIP_TRY(h, h->upscaled.ensure(out_bytes));
-    constexpr size_t ctr_bytes = (size_t)UPSCALE_COUNTERS * UPSCALE_COUNTER_STRIDE * sizeof(unsigned);
-    HIP_TRY(h, h->upscale_ctr.ensure(ctr_bytes));
-    HIP_TRY(h, hipMemsetAsync(h->upscale_ctr, 0, ctr_bytes, h->stream));
-    UpscaleParams<T> u{};
-    u.F = factor; u.source = source; u.use_coverage = use_coverage;
-    u.S = h->preview.coverage_grid * h->preview.coverage_grid;
-    u.i_n = (T)inv2[0]; u.i_a = (T)inv2[1]; u.i_z = (T)inv2[2];
-    u.tally_offset = (int)tally_offset;
-    if (source == RTIOW_UPSCALE_LINEAR) accumulation_source(h, u.mid, u.counts, u.n_uniform);
-    if (source == RTIOW_UPSCALE_DENOISED) u.g = h->denoised.as<const T>();
-    if (source == RTIOW_UPSCALE_HISTORY) u.cm = h->hist_cm.as<const Vec4<T>>();
-    u.nd = h->guide_nd.as<const Vec4<T>>(); u.alb = h->guide_alb.as<const Vec4<T>>();
-    u.ic = use_coverage ? h->cov_ic.as<const int4>() : nullptr;
-    const auto k = by_source(L.lds_source, [](auto src) { return upscale_wide_kernel<T, src>; });
-    HIP_TRY(h, allow_lds(k, lds));
-    const int blocks = ((L.p.cold.W * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK) * ((h->local_rows * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), lds, h->stream, L.p, u, (int)stage_offset, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
-    HIP_TRY(h, hipGetLastError());
-    h->upscaled_bytes = out_bytes;
-    on_upscaled(h->preview, factor);
-    return 0;
+    UpscaleLaunch<T> U;
+    if (int rc = prepare_upscale<T>(h, U, upscale_wide_stage_bytes<T>() + UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
+    const size_t stage_offset = U.own_offset;
+    U.u.tally_offset = (int)(stage_offset + upscale_wide_stage_bytes<T>());
+    const auto k = by_source(U.L.lds_source, [](auto src) { return upscale_wide_kernel<T, src>; });
+    HIP_TRY(h, allow_lds(k, U.lds));
+    const int blocks = ((U.L.p.cold.W * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK) * ((h->local_rows * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * UPSCALE_WAVES), U.lds, h->stream, U.L.p, U.u, (int)stage_offset, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);
+    return finish_upscale(h, factor, out_bytes);
 }
 
 // history_length_kernel over the current guides and the base into h->plan_m (rtiow_history_plan): the m of launch_history for the same

@@ -28,56 +28,7 @@
 // bit): IEEE correctly-rounded + - * / sqrt, explicit fma() only where written, compiled
 // with -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt, denormals preserved.
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <array>
-#include <cstdlib>
-#include <chrono>
-#include <cstring>
-#include <new>
-#include <string>
-#include <type_traits>
-#include <mutex>
-#include <vector>
-
-#include "rtiow.h"
-#ifdef RTIOW_DEBUG_API
-#include "rtiow_debug.h"
-#endif
-
-#include "device/xorwow.h"
-#include "device/params.h"
-#include "device/probes.h"
-#include "device/vecmath.h"
-#include "device/sampling.h"
-#include "device/roots.h"
-#include "device/hit_loop.h"
-#include "device/hit_grid.h"
-#include "device/shade.h"
-#include "device/hit_coop.h"
-#include "device/pixel_io.h"
-#include "device/render_kernels.h"
-#include "device/cost_sort.h"
-#include "device/denoise.h"
-#include "device/denoise_variance.h"
-#include "device/history.h"
-#include "device/history_clip.h"
-#include "device/history_feedback.h"
-#include "device/history_budget.h"
-#include "device/temporal_noise.h"
-#include "device/guide_chain.h"
-#include "device/edge_resolve.h"
-#include "device/scene_motion.h"
-#include "device/edit_influence.h"
-#include "library/xorwow_jump.h"
-#include "library/handle.h"
-#include "library/scene_tables.h"
-#include "library/launch.h"
-#include "library/pass.h"
+#include "library/unit.h"
 
 extern "C" {
 

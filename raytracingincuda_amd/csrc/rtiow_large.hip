@@ -1,63 +1,13 @@
 // rtiow_large.hip -- large scenes: the fifth translation unit compiled for gfx950, linked
 // into librtiow_hip.so beside the others.  It holds large_scene_kernel and its debug probe (device/hit_device_grid.h), the device grid's
 // tables (library/device_grid.h: plan and blob), the launch and the entry points, and nothing else: the other code objects keep exactly
-// the kernels they had.  The headers are rtiow_upscale.hip's, in its order, plus the new one behind them (internal linkage; templates
+// the kernels they had.  The headers are library/unit.h's, as in every unit, with this unit's two behind them (internal linkage; templates
 // this unit does not call are not instantiated here).
 //
 // Floating-point contract: rtiow_hip.hip's, the same flags.
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <array>
-#include <cstdlib>
-#include <chrono>
-#include <cstring>
-#include <new>
-#include <string>
-#include <type_traits>
-#include <mutex>
-#include <vector>
-
-#include "rtiow.h"
-#ifdef RTIOW_DEBUG_API
-#include "rtiow_debug.h"
-#endif
-
-#include "device/xorwow.h"
-#include "device/params.h"
-#include "device/probes.h"
-#include "device/vecmath.h"
-#include "device/sampling.h"
-#include "device/roots.h"
-#include "device/hit_loop.h"
-#include "device/hit_grid.h"
-#include "device/shade.h"
-#include "device/hit_coop.h"
-#include "device/pixel_io.h"
-#include "device/render_kernels.h"
-#include "device/cost_sort.h"
-#include "device/denoise.h"
-#include "device/denoise_variance.h"
-#include "device/history.h"
-#include "device/history_clip.h"
-#include "device/history_feedback.h"
-#include "device/history_budget.h"
-#include "device/temporal_noise.h"
-#include "device/guide_chain.h"
-#include "device/edge_resolve.h"
-#include "device/scene_motion.h"
-#include "device/edit_influence.h"
-#include "device/upscale.h"
+#include "library/unit.h"
 #include "device/hit_device_grid.h"
-#include "library/xorwow_jump.h"
-#include "library/handle.h"
-#include "library/scene_tables.h"
-#include "library/launch.h"
-#include "library/pass.h"
 #include "library/device_grid.h"
 
 namespace {

@@ -8,11 +8,12 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.edge_resolve_model import coverage_np, scene_of
 from tests.preview_drive import E_BADARG, E_STATE, begin, move, moves, sample
 from tests.preview_model import LATTICE, same_bits
 from tests.test_edge_resolve import BIG, FRAMES, _budget_frame, start, view
-from tests.upscale_model import DENOISED, HISTORY, INF, LINEAR, colour_of, output_hits, upscale_np
+from tests.upscale_drive import Cpu, _bits, _everything, check_guides, colour
+from tests.upscale_drive import check as drive_check
+from tests.upscale_model import DENOISED, HISTORY, INF, LINEAR, upscale_np
 
 pytestmark = pytest.mark.gpu
 
@@ -30,63 +31,12 @@ def rt(native):
 
 @pytest.fixture(scope="module")
 def cpu(rt, oracle):
-    """The CPU side of the model, computed once per camera and shared: cpu.hits(prec, scene_id, cam, F) the output pixels' hits (F = 1: the
-    traced pixels' first-hit guides), cpu.layers(prec, scene_id, cam, G) the coverage layers.  Nothing here is changed by a test."""
-    class Cpu:
-        def __init__(self):
-            self.cache = {}
-
-        def _get(self, key, make):
-            if key not in self.cache:
-                self.cache[key] = make()
-            return self.cache[key]
-
-        def hits(self, prec, scene_id, cam, F):
-            rows = np.arange(cam.img_height)
-            return self._get(("hits", prec, scene_id, bytes(cam), F), lambda: output_hits(oracle, prec, scene_of(rt, scene_id, prec), cam, rows, F))
-
-        def layers(self, prec, scene_id, cam, G):
-            rows = np.arange(cam.img_height)
-            return self._get(("layers", prec, scene_id, bytes(cam), G), lambda: coverage_np(oracle, prec, scene_of(rt, scene_id, prec), cam, rows, G)[:2])
-    return Cpu()
+    return Cpu(rt, oracle)
 
 
-def colour(r, source, adaptive=False):
-    """colour_of's (c, has) of a source, read back from the handle."""
-    if source == DENOISED:
-        return colour_of(DENOISED, g=r.read_denoised())
-    if source == LINEAR:
-        lin = r.read_linear()
-        n = r.adaptive_state()[0] if adaptive else np.full(lin.shape[:2], r.accumulated_samples, np.int32)
-        return colour_of(LINEAR, linear=lin, n=n)
-    C, M = r.history()
-    return colour_of(HISTORY, C=C, M=M)
-
-
-def check(r, cpu, prec, scene_id, cam, source, setting, G, where, adaptive=False):
-    """upscale() at `setting` with the layers of lattice G against the model, every pixel, and the count; returns the image."""
-    F, sn, sa, sz, flag = setting
-    where = where + (source, setting, G)
-    c, has = colour(r, source, adaptive)
-    _, N, A, Z = cpu.hits(prec, scene_id, cam, 1)
-    ids, counts = cpu.layers(prec, scene_id, cam, G)
-    count = r.upscale(F, source, sn, sa, sz, flag)
-    out = r.read_upscaled()
-    want, covered = upscale_np(c, has, N, A, Z, ids, counts, G * G, cpu.hits(prec, scene_id, cam, F), F, sn, sa, sz, flag)
-    H, W = c.shape[:2]
-    assert out.shape == (F * H, F * W, 3) and out.dtype == c.dtype, where
-    assert same_bits(out, want), (where, int((out != want).any(axis=-1).sum()))
-    assert count == int(covered.sum()), (where, count, int(covered.sum()))
-    ptr, nbytes = r.upscaled_device_ptr()
-    assert ptr and nbytes == out.nbytes, where
-    return out
-
-
-def check_guides(r, cpu, prec, scene_id, cam, where):
-    """The traced pixels' guides of the model are the handle's, bit for bit."""
-    _, N, A, Z = cpu.hits(prec, scene_id, cam, 1)
-    for name, a, b in zip(("normal", "albedo", "depth"), r.guides(), (N, A, Z)):
-        assert same_bits(a, b), (where, name)
+def check(r, *args, **kwargs):
+    """upscale() against tests/upscale_model.py (upscale_drive.check)."""
+    return drive_check(r.upscale, upscale_np, r, *args, **kwargs)
 
 
 # ---- 1. every source
@@ -238,12 +188,6 @@ def test_stale_guides_and_layers_are_rendered_inside_the_call(rt, cpu, prec):
 
 # ---- 3. refusals, staleness, isolation
 
-def _bits(r):
-    """What a refused call must leave alone."""
-    return {"upscaled": r.read_upscaled(), "denoised": r.read_denoised(), "fb": r.read_framebuffer(), "linear": r.read_linear(),
-            "samples": np.array([r.accumulated_samples])}
-
-
 def test_refusals_leave_the_handle_as_it_was(rt):
     W, H, prec = 33, 17, 32
     nan = float("nan")
@@ -319,15 +263,6 @@ def test_the_image_survives_everything_but_a_new_frame(rt, cpu):
             assert stale(), name                              # nothing but an upscale brings it back
             r.render_coverage(2)
             assert same_bits(check(r, cpu, prec, scene_id, cam, LINEAR, SETTINGS[1], 2, (name,)), image), name
-
-
-def _everything(r):
-    out = {"fb": r.read_framebuffer(), "linear": r.read_linear(), "denoised": r.read_denoised(), "temporal": r.history()[0], "length": r.history()[1],
-           "base": r.history_base()[0], "base_length": r.history_base()[1], "plan": r.history_plan_lengths()}
-    out["counts"], out["err"] = r.adaptive_state()
-    out["normal"], out["albedo"], out["depth"] = r.guides()
-    out["ids"], out["layer_counts"], out["layer_normal"], out["layer_depth"] = r.coverage()
-    return out
 
 
 @pytest.mark.parametrize("prec", [32, 64])

@@ -101,6 +101,7 @@ def test_kernel_count_and_resources(native, name):
     assert len(ks) == KERNELS[name], (name, sorted(ks))
     for k, v in ks.items():
         assert v["scratch"] == 0 and v["vgpr_spill"] == 0, (k, v)
+        assert v["vgpr"] <= (64 if "<float" in k else 80), (k, v)        # eight / six waves per SIMD (granule 8, min(8, 512 // alloc))
         assert "render_" not in k and "variance_" not in k, k      # the families other tests count by
     for prec in ("float", "double"):
         for src in (0, 1):

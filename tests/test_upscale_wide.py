@@ -10,13 +10,13 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.edge_resolve_model import coverage_np, scene_of
 from tests.preview_drive import E_BADARG, E_STATE, begin, move, moves, sample
 from tests.preview_model import LATTICE, same_bits
 from tests.test_edge_resolve import _budget_frame, start, view
-from tests.test_upscale import _bits, _everything, check_guides, colour
+from tests.upscale_drive import Cpu, _bits, _everything, check_guides, colour
+from tests.upscale_drive import check as drive_check, model as drive_model
 from tests.upscale_model import upscale_np
-from tests.upscale_wide_model import DENOISED, HISTORY, INF, LINEAR, output_hits, upscale_wide_np
+from tests.upscale_wide_model import DENOISED, HISTORY, INF, LINEAR, upscale_wide_np
 
 pytestmark = pytest.mark.gpu
 
@@ -36,49 +36,17 @@ def rt(native):
 
 @pytest.fixture(scope="module")
 def cpu(rt, oracle):
-    """The CPU side of the model, computed once per camera and shared: cpu.hits(prec, scene_id, cam, F) the output pixels' hits (F = 1: the
-    traced pixels' first-hit guides), cpu.layers(prec, scene_id, cam, G) the coverage layers.  Nothing here is changed by a test."""
-    class Cpu:
-        def __init__(self):
-            self.cache = {}
-
-        def _get(self, key, make):
-            if key not in self.cache:
-                self.cache[key] = make()
-            return self.cache[key]
-
-        def hits(self, prec, scene_id, cam, F):
-            rows = np.arange(cam.img_height)
-            return self._get(("hits", prec, scene_id, bytes(cam), F), lambda: output_hits(oracle, prec, scene_of(rt, scene_id, prec), cam, rows, F))
-
-        def layers(self, prec, scene_id, cam, G):
-            rows = np.arange(cam.img_height)
-            return self._get(("layers", prec, scene_id, bytes(cam), G), lambda: coverage_np(oracle, prec, scene_of(rt, scene_id, prec), cam, rows, G)[:2])
-    return Cpu()
+    return Cpu(rt, oracle)
 
 
-def model(r, cpu, prec, scene_id, cam, source, setting, G, adaptive=False, np_model=upscale_wide_np):
-    """The model's (image, covered) of `setting` on what the handle holds."""
-    F, sn, sa, sz, flag = setting
-    c, has = colour(r, source, adaptive)
-    _, N, A, Z = cpu.hits(prec, scene_id, cam, 1)
-    ids, counts = cpu.layers(prec, scene_id, cam, G)
-    return np_model(c, has, N, A, Z, ids, counts, G * G, cpu.hits(prec, scene_id, cam, F), F, sn, sa, sz, flag)
+def model(r, *args, np_model=upscale_wide_np, **kwargs):
+    """The model's (image, covered) of a setting on what the handle holds (upscale_drive.model)."""
+    return drive_model(np_model, r, *args, **kwargs)
 
 
-def check(r, cpu, prec, scene_id, cam, source, setting, G, where, adaptive=False):
-    """upscale_wide() at `setting` with the layers of lattice G against the model, every pixel, and the count; returns the image."""
-    F, sn, sa, sz, flag = setting
-    where = where + (source, setting, G)
-    want, covered = model(r, cpu, prec, scene_id, cam, source, setting, G, adaptive)
-    count = r.upscale_wide(F, source, sn, sa, sz, flag)
-    out = r.read_upscaled()
-    assert out.shape == want.shape and out.dtype == want.dtype, where
-    assert same_bits(out, want), (where, int((out != want).any(axis=-1).sum()))
-    assert count == int(covered.sum()), (where, count, int(covered.sum()))
-    ptr, nbytes = r.upscaled_device_ptr()
-    assert ptr and nbytes == out.nbytes, where
-    return out
+def check(r, *args, **kwargs):
+    """upscale_wide() against tests/upscale_wide_model.py (upscale_drive.check)."""
+    return drive_check(r.upscale_wide, upscale_wide_np, r, *args, **kwargs)
 
 
 # ---- 1. every source
