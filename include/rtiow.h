@@ -781,9 +781,9 @@ int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_norm
 /* ---- Large scenes: rtiow_render through a uniform grid walked in device memory.
  * rtiow_render is fast while a scene's tables fit a compute unit's LDS; beyond that (about 5 100 spheres in fp32, 3 400 in fp64) it reads
  * the scene through the exact loop over every sphere (rtiow_stats.scene_source == RTIOW_SCENE_SCALAR).  rtiow_render_large renders the
- * same frame -- same framebuffer, shard, RNG states in and out, rtiow_stats -- with only the spheres too big for a grid cell in LDS and
- * everything else in a grid in device memory: variable-length cells of 32-bit sphere indices, no limit on spheres per cell, up to 2^20
- * cells.  Every pixel draws its numbers in the reference's order from its own state: the image is rtiow_render's bit for bit.
+ * same frame -- same framebuffer, shard, RNG states (read from where rtiow_init_rng left them and left there, as by rtiow_render), rtiow_stats -- with only the spheres too big for a grid cell in LDS and
+ * everything else in a grid in device memory: variable-length cells of 32-bit sphere indices, no limit on spheres per cell, at most about
+ * 190 x 190 cells (beyond that the lists grow).  Every pixel draws its numbers in the reference's order from its own state: the image is rtiow_render's bit for bit.
  * Opt-in: rtiow_render never selects it, the knobs of rtiow_set_scene_source and rtiow_set_schedule do not apply (the launch is the
  * persistent hand-out in tile order; rtiow_stats.schedule reads RTIOW_SCHED_PERSISTENT, scene_source RTIOW_SCENE_DEVICE_GRID, and the
  * grid_* fields describe the device grid).  Plan and device tables are built at the first call after rtiow_set_scene /

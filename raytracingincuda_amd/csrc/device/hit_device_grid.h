@@ -19,7 +19,7 @@ namespace {
 // could accept.  Far, NaN and huge rays send the wave through the exact loop over the device table.
 //
 // The walk's boundaries.  The LDS grid advances the leaving parameters incrementally, which is exact enough only because its walks
-// take at most nx + nz <= 128 steps.  This grid has up to 2^20 cells, so the parameters are computed in CLOSED FORM at every step:
+// take at most nx + nz <= 128 steps.  This grid has up to about 190 cells an axis (library/device_grid.h), so the parameters are computed in CLOSED FORM at every step:
 //     b = (float)(c + 1 or c) * cell          one rounding: <= 2^-24 |b|
 //     t = (b - o) * inv_d                     the difference rounds once (<= 2^-24 max(|b|, |o|)), the raw reciprocal is within 1 ulp
 //                                             (2^-23 relative) and the product rounds once (2^-24 relative): <= 2^-22 relative of t

@@ -20,10 +20,13 @@
 //  cells                    {first, count} per cell into ONE array of 32-bit sphere indices, ascending within a cell;
 //  cell size                a mean of about two spheres per occupied cell: cell^2 = 1.5 x (area / spheres) -- a sphere of the r = 0.2, pitch 1
 //                           lattices is in ~1.3 cells -- or the lower bound above when that is wider (large scenes: E grows with Cmax^2);
-//  cell-count cap           DEVICE_GRID_MAX_CELLS = 2^20.  The cell table is 8 bytes a cell: 8 MB at the cap, which the 256 MB last-level
-//                           cache holds beside the sphere table of any scene the cap lets through, and (iz nx + ix) 8 stays far inside
-//                           an int (the kernel computes the record's byte offset in 32 bits).  A plan over the cap widens its cells by
-//                           1.25 until it fits;
+//  cell-count cap           DEVICE_GRID_MAX_CELLS = 2^20, a guard that no scene reaches.  The cell's lower bound grows with the scene:
+//                           w >= sqrt(E) >= sqrt(18 * 2^-24 * 1.01) (Rfar + Cmax) >= 5.2e-3 Cmax (Rfar >= 4 Cmax, Cmax the plan's
+//                           1.0001 Cmax), so cell > 2.04 w > 0.0106 Cmax, while an axis extends over at most 2 Cmax + 2 wmax: nx and nz
+//                           are at most about 190 each, the grid about 36 000 cells (0.3 MB of records), and beyond that many cells'
+//                           worth of spheres the LISTS grow instead (1.6 million lattice spheres: 128 x 128 cells, a longest list of
+//                           about 400).  The loop that widens the cells by 1.25 under the cap is kept as the guard's other half and does not
+//                           run; (iz nx + ix) 8 stays far inside an int (the kernel computes the record's byte offset in 32 bits);
 //  which spheres are small  candidates as in plan_grid (every finite sphere, then without the largest radii, ...), but a candidate whose
 //                           natural cell is narrower than its lower bound is kept with the bound instead of dropped -- a lattice of equal
 //                           spheres has no smaller radii to fall back to.  The candidates are ranked by an estimate of a ray's tests:

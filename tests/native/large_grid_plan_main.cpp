@@ -1,7 +1,8 @@
 // Stand-alone check of the device grid's plan and blob (raytracingincuda_amd/csrc/library/device_grid.h), built with
 // -fsanitize=address,undefined by tests/test_large_grid_plan.py and run directly.  The invariants held here are what keeps the kernel's
 // gathers inside the blob: every {first, count} inside the index array, every index <= m, lists ascending, every finite sphere on the
-// direct list or in every cell its inflated square touches, offsets and sizes of the blob consistent in both precisions.
+// direct list or in every cell its inflated square touches, offsets and sizes of the blob consistent in both precisions.  Also pinned:
+// the reachable size of the grid (nx, nz <= 192 whatever the scene; see main).
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -33,10 +34,59 @@ static std::vector<double> lattice(int n, uint64_t seed) {
     }
     return cr;
 }
-static std::vector<double> line(int n) {
+static std::vector<double> line(int n, double r = 0.2, double pitch = 1.0) {
     std::vector<double> cr;
     push(cr, 0, -1000, 0, 1000);
-    for (int k = 0; k < n; ++k) push(cr, k - 0.5 * n, 0.2, 0.0, 0.2);
+    for (int k = 0; k < n; ++k) push(cr, (k - 0.5 * n) * pitch, r, 0.0, r);
+    return cr;
+}
+
+// One scene of each kind of tests/large_scene.py's EDGE_SCENES (the same shapes, this file's generator).
+// clusters: the ground, 600 spheres over 40 x 40 and clusters of 1 .. 24 within 0.05 of a point, the last of every third an exact copy of its first.
+static std::vector<double> clusters(uint64_t seed) {
+    std::vector<double> cr;
+    push(cr, 0, -1000, 0, 1000);
+    Lcg g{seed};
+    for (int k = 0; k < 600; ++k) { const double x = 40 * g.next() - 20, z = 40 * g.next() - 20; push(cr, x, 0.2, z, 0.2); }
+    for (int k = 1; k <= 24; ++k) {
+        const double px = 36 * g.next() - 18, pz = 36 * g.next() - 18;
+        const size_t first = cr.size();
+        for (int j = 0; j < k; ++j) { const double r = 0.15 + 0.05 * g.next(); push(cr, px + 0.07 * (g.next() - 0.5), r + 0.3 * g.next(), pz + 0.07 * (g.next() - 0.5), r); }
+        if (k % 3 == 2) for (int q = 0; q < 4; ++q) cr[cr.size() - 4 + q] = cr[first + q];
+    }
+    return cr;
+}
+// equal_no_ground: 900 equal spheres on a jittered lattice at heights in [0, 3] and nothing else.
+static std::vector<double> equal_no_ground(uint64_t seed) {
+    std::vector<double> cr;
+    Lcg g{seed};
+    for (int k = 0; k < 900; ++k) { const double x = k % 30 - 15 + 0.5 * (g.next() - 0.5), z = k / 30 - 15 + 0.5 * (g.next() - 0.5); push(cr, x, 3 * g.next(), z, 0.2); }
+    return cr;
+}
+// mixed_with_bad: the ground, four big spheres, 800 of mixed radii and heights; four of them r < 0, r = NaN, cx = inf and r = 0.
+static std::vector<double> mixed_with_bad(uint64_t seed) {
+    std::vector<double> cr;
+    push(cr, 0, -1000, 0, 1000);
+    push(cr, 0, 1, 0, 1.0); push(cr, -6, 1, 3, 1.0); push(cr, 7, 1, -4, 1.0); push(cr, 2, 1.5, 9, 1.5);
+    Lcg g{seed};
+    for (int k = 0; k < 800; ++k) { const double x = 30 * g.next() - 15, y = 4 * g.next() - 1, z = 30 * g.next() - 15; push(cr, x, y, z, 0.05 + 0.3 * g.next()); }
+    cr[4 * 105 + 3] = -0.3; cr[4 * 305 + 3] = NAN; cr[4 * 505] = INFINITY; cr[4 * 705 + 3] = 0.0;
+    return cr;
+}
+// far_centre: 900 equal spheres on a jittered lattice on a ground, translated by (3000, 0, -2000).
+static std::vector<double> far_centre(uint64_t seed) {
+    std::vector<double> cr;
+    push(cr, 3000, -1000, -2000, 1000);
+    Lcg g{seed};
+    for (int k = 0; k < 900; ++k) { const double x = k % 30 - 15 + 0.5 * (g.next() - 0.5), z = k / 30 - 15 + 0.5 * (g.next() - 0.5); push(cr, 3000 + x, 0.2, -2000 + z, 0.2); }
+    return cr;
+}
+// sparse_wide: the ground and 1 000 spheres of r = 0.2 over 4000 x 4000.
+static std::vector<double> sparse_wide(uint64_t seed) {
+    std::vector<double> cr;
+    push(cr, 0, -1000, 0, 1000);
+    Lcg g{seed};
+    for (int k = 0; k < 1000; ++k) { const double x = 4000 * g.next() - 2000, z = 4000 * g.next() - 2000; push(cr, x, 0.2, z, 0.2); }
     return cr;
 }
 
@@ -153,7 +203,35 @@ int main() {
         const DeviceGridPlan pl = check_scene("line", line(2000), true);
         CHECK(pl.nx + pl.nz > 128);                                                   // longer than any walk of the LDS grid
     }
-    check_scene("lattice 100000", lattice(100000, 3), true);
+    {   // the five kinds of tests/large_scene.py's edge scenes, each with the property it exists for
+        DeviceGridPlan pl = check_scene("clusters", clusters(21), true);
+        int long_lists = 0, odd = 0, even = 0;
+        for (size_t c = 0; c < (size_t)pl.nx * pl.nz; ++c)
+            if (pl.cells[2 * c + 1] >= 7) { ++long_lists; (pl.cells[2 * c + 1] % 2 ? odd : even)++; }
+        CHECK(pl.longest >= 24 && long_lists >= 20 && odd > 0 && even > 0 && pl.direct.size() == 1);
+        pl = check_scene("equal_no_ground", equal_no_ground(22), true);
+        CHECK(pl.direct.empty() && pl.registered == 900 && pl.yhi - pl.ylo > 3.3);
+        CHECK(build_device_grid_blob<float>(pl, 900, equal_no_ground(22)).n_direct_padded == 0);     // an LDS table of size 0
+        pl = check_scene("mixed_with_bad", mixed_with_bad(23), true);
+        CHECK(pl.direct.size() % 4 != 0 && pl.direct.size() >= 5);
+        for (int bad : {105, 305, 505, 705}) CHECK(std::find(pl.direct.begin(), pl.direct.end(), bad) != pl.direct.end());
+        pl = check_scene("far_centre", far_centre(24), true);
+        CHECK(pl.eps >= 0.04);
+        pl = check_scene("sparse_wide", sparse_wide(25), true);
+        CHECK(pl.cellf > 100 && pl.yhi - pl.ylo > 20);
+    }
+    {   // The reachable size of the grid.  With Cmax' = 1.0001 Cmax and Rfar >= 4 Cmax', the half-width of any registered sphere is
+        //   w >= sqrt(E) >= sqrt(18 * 2^-24 * 1.01) (Rfar + Cmax') >= 1.04e-3 * 5 Cmax' = 5.2e-3 Cmax',
+        // so cell >= 2 (wmax + eps) 1.02 > 2.04 w > 0.0106 Cmax', while the extent of an axis is at most 2 Cmax + 2 wmax: nx and nz are
+        // each at most about 2 / 0.0106 + 3 = 191, the grid at most about 36 000 cells, whatever the scene.  DEVICE_GRID_MAX_CELLS
+        // (2^20) is never reached and the loop that widens the cells under it never runs; beyond that many cells' worth of spheres
+        // it is the lists that grow.
+        DeviceGridPlan pl = check_scene("lattice 100000", lattice(100000, 3), true);
+        CHECK(pl.nx <= 192 && pl.nz <= 192);
+        pl = check_scene("line 200000", line(200000, 0.02, 0.05), true);
+        CHECK(pl.nx <= 192 && pl.nz <= 192);
+        CHECK(pl.longest > 2000);                                                     // check_blob above: a list of more than 2 000 entries
+    }
     {
         const DeviceGridPlan pl = check_scene("lattice 70000", lattice(70000, 5), true);
         bool wide = false;
