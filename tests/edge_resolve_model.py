@@ -13,7 +13,9 @@ INF = float("inf")
 
 
 def scene_of(rt, scene_id, prec):
-    """The compact scene tables of a built-in scene or of tests/lattice.py."""
+    """The compact scene tables of a built-in scene or of tests/lattice.py, or the tables themselves (tests/range_scene.py)."""
+    if isinstance(scene_id, dict):
+        return scene_id
     return lattice_scene(prec) if scene_id == LATTICE else compact(rt.build_scene(scene_id, prec))
 
 

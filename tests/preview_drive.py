@@ -57,8 +57,9 @@ def budget_moves(rt, prec, W, H, B=10):
 # ---- a handle, set up and sampled
 
 def begin(r, rt, prec, scene_id, cam, source=3, sched=None, shard=None, seed=1227):
+    """scene_id: a built-in scene's id, or scene tables as they are (tests/range_scene.py)."""
     r.set_camera(cam)
-    r.set_scene(rt.build_scene(scene_id, prec))
+    r.set_scene(scene_id if isinstance(scene_id, dict) else rt.build_scene(scene_id, prec))
     r.set_scene_source(source)
     if sched is not None:
         r.set_schedule(sched, 0)
@@ -137,32 +138,33 @@ def check_against_err(r, where):
     return counts, V
 
 
-def check_update(r, cam, cur, base, params, where):
-    """history() and the pixel count after an update with `params` against the model; returns the model's."""
+def check_update(r, cam, cur, base, params, where, same=same_bits):
+    """history() and the pixel count after an update with `params` against the model; returns the model's.  same: how colours are
+    compared -- same_bits_nan where a colour can be NaN (tests/test_number_range.py); lengths and counts are always compared strictly."""
     count = r.history_update(*params)
     rgb, length = r.history()
     want_c, want_m, want_count = update_np(cam, cur, base, *params)
     assert same_bits(length, want_m), where
-    assert same_bits(rgb, want_c), where
+    assert same(rgb, want_c), where
     assert count == want_count, (where, count, want_count)
     return want_c, want_m, want_count
 
 
-def check_clipped(r, cam, cur, base, params, radius, gamma, where):
+def check_clipped(r, cam, cur, base, params, radius, gamma, where, same=same_bits):
     """A plain update, then the clipped one with the same three arguments, against each other and against the model; the clipped
-    image is what the handle holds afterwards.  Returns the model's."""
+    image is what the handle holds afterwards.  Returns the model's.  same: as in check_update."""
     plain_count = r.history_update(*params)
     plain_rgb, plain_len = r.history()
     count, clipped = r.history_update_clipped(radius, gamma, *params)
     rgb, length = r.history()
-    want = clipped_np(cam, cur, base, params, radius, gamma)
+    want = clipped_np(cam, cur, base, params, radius, gamma, same)
     assert same_bits(length, want["M"]), where
-    assert same_bits(rgb, want["C"]), where
+    assert same(rgb, want["C"]), where
     assert (count, clipped) == (want["reprojected"], want["clipped"]), (where, count, clipped, want["reprojected"], want["clipped"])
     assert same_bits(length, plain_len) and count == plain_count, where
-    assert same_bits(plain_rgb, want["plain_C"]), where
+    assert same(plain_rgb, want["plain_C"]), where
     keep = ~want["mask"]
-    assert same_bits(np.ascontiguousarray(rgb[keep]), np.ascontiguousarray(plain_rgb[keep])), where
+    assert same(np.ascontiguousarray(rgb[keep]), np.ascontiguousarray(plain_rgb[keep])), where
     return want
 
 

@@ -16,6 +16,33 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+def same_bits_nan(a, b):
+    """same_bits where a NaN can occur: x86 and gfx950 give a NaN different bits (inf - inf has the sign set on the one and clear on the
+    other, and propagation picks payloads), so the NaN masks must be equal and every other value identical bit for bit -- +0 and -0,
+    +inf and -inf and the subnormals are told apart as same_bits tells them."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    if not np.array_equal(na, nb):
+        return False
+    bits = np.dtype("u%d" % a.dtype.itemsize)
+    return np.array_equal(np.ascontiguousarray(a).view(bits)[~na], np.ascontiguousarray(b).view(bits)[~nb])
+
+
+def positive_part(x):
+    """max(0, x) as the library states it (sections 8, 10, 14 and 15): x > 0 ? x : 0.  A NaN compares false and gives 0, where
+    np.maximum would keep it; on every other value the two agree."""
+    with np.errstate(invalid="ignore"):
+        return np.where(x > 0, x, np.zeros_like(x))
+
+
+def scene_tables(rt, scene, prec):
+    """The compact scene tables: of a built-in scene id, of tests/lattice.py (LATTICE), or the tables themselves (tests/range_scene.py)."""
+    if isinstance(scene, dict):
+        return scene
+    return lattice_scene(prec) if scene == LATTICE else compact(rt.build_scene(scene, prec))
+
+
 def gamma(x):
     z = np.zeros_like(x)
     pos = x > 0
@@ -51,7 +78,7 @@ def quality(out):
 def guides_np(rt, oracle, prec, scene_id, cam, rows):
     """(normal, albedo, depth) as defined: centre ray per pixel, hit_world on the CPU oracle, the rest in T with plain ops."""
     dt = np.float32 if prec == 32 else np.float64
-    sc = compact(rt.build_scene(scene_id, prec))
+    sc = scene_tables(rt, scene_id, prec)
     cr = np.asarray(sc["center_radius"], dt).reshape(-1, 4)
     W = cam.img_width
     O = np.array(cam.center[:], dt)
@@ -108,6 +135,22 @@ def filter_np(c0, normal, albedo, depth, levels, sc, sn, sa, sz):
                 Wt = np.where(valid, Wt + w, Wt)
         c = S / Wt[..., None]
     return gamma(c)
+
+
+# ---- sections 8 and 10: the error estimate and the variance plane, in double from Y = Y(acc) in T, s2 in T and the count
+
+def noise_np(Y, s2, n, dt, clamp=positive_part):
+    """(err float32, V in dt) of a pixel's record: m = Y / n, var = max(0, (s2 - n m m) / (n - 1)) with max as positive_part states it,
+    err = sqrt(var / n) / (m + 1e-3), V = (T)(var / n); err = +inf and V = 0 below two samples."""
+    Y, s2 = np.asarray(Y, np.float64), np.asarray(s2, np.float64)
+    dn = np.asarray(n).astype(np.float64)
+    with np.errstate(all="ignore"):
+        mean = Y / dn
+        var = clamp((s2 - dn * mean * mean) / (dn - 1.0))
+        err = (np.sqrt(var / dn) / (mean + 1e-3)).astype(np.float32)
+        V = (var / dn).astype(dt)
+    few = np.asarray(n) < 2
+    return np.where(few, np.float32(np.inf), err).astype(np.float32), np.where(few, dt(0), V).astype(dt)
 
 
 # ---- section 10: the filter whose colour edge-stop follows the variance plane
@@ -208,8 +251,9 @@ def blend_np(cur, h, m):
     return Cout, Mout
 
 
-def update_np(cam, cur, base, depth_tol, normal_cos, max_history):
-    """(Cout, Mout, reprojected pixels).  base: None, or {"cam", "H", "M", "N", "z"} as rtiow_history_commit keeps them."""
+def gather_np(cam, cur, base, depth_tol, normal_cos, max_history):
+    """(h, m): the gathered history and its capped length, before the blend.  base: None, or {"cam", "H", "M", "N", "z"} as
+    rtiow_history_commit keeps them."""
     c, n, N, t = cur["c"], cur["n"], cur["N"], cur["t"]
     dt = c.dtype.type
     Hh, W = n.shape
@@ -244,6 +288,12 @@ def update_np(cam, cur, base, depth_tol, normal_cos, max_history):
             h = np.where(got[..., None], S / Bs[..., None], dt(0)).astype(c.dtype)
             m = np.where(got, L / Bs, dt(0)).astype(c.dtype)
             m = np.where(m < dt(max_history), m, dt(max_history)).astype(c.dtype)
+    return h, m
+
+
+def update_np(cam, cur, base, depth_tol, normal_cos, max_history):
+    """(Cout, Mout, reprojected pixels): the gather, then the blend."""
+    h, m = gather_np(cam, cur, base, depth_tol, normal_cos, max_history)
     Cout, Mout = blend_np(cur, h, m)
     return Cout, Mout, int((m > 0).sum())
 
@@ -302,14 +352,18 @@ def clip_np(cur, h, m, radius, gamma):
     return out, (below | above).any(axis=-1)
 
 
-def clipped_np(cam, cur, base, params, radius, gamma):
-    """Section 11 with the clamp of section 14 between the cap and the blend.  update_np with c = 0 and n = 0 returns h and m themselves
-    (alpha = 0: Cout = h + 0 (0 - h), the bits of h); blending them again with the real c and n must reproduce update_np's own image."""
+def clipped_np(cam, cur, base, params, radius, gamma, same=same_bits):
+    """Section 11 with the clamp of section 14 between the cap and the blend.  h and m come from gather_np itself: update_np with c = 0
+    and n = 0 returns them too where h is finite (alpha = 0: Cout = h + 0 (0 - h), the bits of h), but turns an infinite h into a NaN,
+    which the clamp would then leave alone where it moves the infinity to its bound.  same: how colours are compared (same_bits_nan
+    where one can be NaN)."""
     zero = {"c": np.zeros_like(cur["c"]), "n": np.zeros_like(cur["n"]), "N": cur["N"], "t": cur["t"]}
-    h, m, carried = update_np(cam, zero, base, *params)
+    h, m = gather_np(cam, cur, base, *params)
+    carried = int((m > 0).sum())
     plain_c, plain_m, plain_count = update_np(cam, cur, base, *params)
-    again_c, again_m = blend_np(cur, h, m)
-    assert same_bits(again_c, plain_c) and same_bits(again_m, plain_m) and carried == plain_count
+    through_c, through_m, _ = update_np(cam, zero, base, *params)
+    finite = np.isfinite(h).all(axis=-1)
+    assert same(np.ascontiguousarray(through_c[finite]), np.ascontiguousarray(h[finite])) and same_bits(through_m, m) and carried == plain_count
     hc, mask = clip_np(cur, h, m, radius, gamma)
     C, M = blend_np(cur, hc, m)
     return {"C": C, "M": M, "h": h, "m": m, "reprojected": carried, "clipped": int(mask.sum()), "mask": mask, "plain_C": plain_c}
@@ -401,7 +455,7 @@ def chain_np(rt, oracle, prec, scene_id, cam, rows, max_bounces, max_fuzz):
     """(normal', albedo', depth', bounces, facts) as section 12 defines them: hit_world on the CPU oracle once per bounce level for the
     chains still alive, the rest in T with plain operations.  facts counts what the tests want to have met."""
     dt = np.float32 if prec == 32 else np.float64
-    sc = lattice_scene(prec) if scene_id == LATTICE else compact(rt.build_scene(scene_id, prec))
+    sc = scene_tables(rt, scene_id, prec)
     cr = np.asarray(sc["center_radius"], dt).reshape(-1, 4)
     af = np.asarray(sc["albedo_fuzz"], dt).reshape(-1, 4)
     eta = np.asarray(sc["refraction_index"], dt).reshape(-1)

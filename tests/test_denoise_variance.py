@@ -9,7 +9,7 @@ import pytest
 
 from tests.preview_drive import E_BADARG, E_STATE, INF, check_against_err, run_mixed
 from tests.preview_drive import setup as _setup    # not a bare `setup`: older pytests take that name for a module hook
-from tests.preview_model import luminance, same_bits, variance_filter_np
+from tests.preview_model import luminance, positive_part, same_bits, variance_filter_np
 
 pytestmark = pytest.mark.gpu
 
@@ -74,7 +74,7 @@ def test_variance_against_rebuilt_samples(rt):
     ys = np.array(ys)
     s2 = (ys ** 2).sum(axis=0)
     m = luminance(prev) / N
-    var = np.maximum(0.0, (s2 - N * m * m) / (N - 1))
+    var = positive_part((s2 - N * m * m) / (N - 1))       # x > 0 ? x : 0, as the library states max(0, x): a NaN gives 0
     want = var / N
     with rt.Renderer(0, prec) as r:
         _setup(r, rt, prec, 3, W, H, B=B)

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 from tests.preview_drive import INF, history_defaults, moves
-from tests.preview_model import (as_base, clipped_np, feedback_np, filter_np, gamma, guides_np, plan_np, same_bits, temporal_noise_np, update_np,
-                                 variance_filter_np)
+from tests.preview_model import (as_base, clipped_np, feedback_np, filter_np, gamma, guides_np, noise_np, plan_np, positive_part, same_bits,
+                                 same_bits_nan, temporal_noise_np, update_np, variance_filter_np)
 
 W, H = 48, 32
 PINS = {
@@ -72,3 +72,46 @@ def test_the_model_keeps_its_bits(native, oracle, prec):
     full, _ = feedback_np(C, M, N, A, Z, (0.5, 0.3, 0.3, 1.0), 1.0)
     level0 = filter_np(C, N, A, Z, 1, 0.5, 0.3, 0.3, 1.0)
     assert same_bits(np.ascontiguousarray(gamma(full)[~short]), np.ascontiguousarray(level0[~short]))
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_the_nan_aware_comparison(T):
+    """same_bits_nan tells apart what same_bits tells apart, except the bits of two NaNs."""
+    bits = np.dtype("u%d" % np.dtype(T).itemsize)
+    tiny = np.finfo(T).tiny
+    a = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, tiny / 4, 1.5], T)
+    assert same_bits_nan(a, a.copy()) and not same_bits_nan(a, a[:-1]) and not same_bits_nan(a, a.astype(np.float16))
+
+    def other(k, value):
+        b = a.copy()
+        b[k] = value
+        return b
+
+    assert not same_bits_nan(a, other(0, -0.0)) and not same_bits_nan(a, other(1, 0.0))          # +0 against -0
+    assert not same_bits_nan(a, other(2, -np.inf)) and not same_bits_nan(a, other(3, np.inf))     # +inf against -inf
+    assert not same_bits_nan(a, other(6, np.nan)) and not same_bits_nan(a, other(4, 1.0))         # a NaN on one side only
+    assert not same_bits_nan(a, other(5, tiny / 2)) and not same_bits_nan(a, other(5, 0.0))       # subnormals count
+    # two payloads and both signs of NaN: what x86 and gfx950 give inf - inf, and a propagated payload
+    quiet = a.copy().view(bits)
+    quiet[4] = (np.array([np.nan], T).view(bits)[0] | 1) ^ (bits.type(1) << bits.type(8 * bits.itemsize - 1))
+    b = quiet.view(T)
+    assert np.isnan(b[4]) and not same_bits(a, b) and same_bits_nan(a, b) and same_bits_nan(b, a)
+    with np.errstate(invalid="ignore"):
+        made = np.array([np.inf], T) - np.array([np.inf], T)
+    assert same_bits_nan(made, np.array([np.nan], T))
+
+
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_max_zero_as_the_library_states_it(T):
+    """positive_part is np.maximum(0, x) on everything but a NaN, which it turns into 0 (sections 8 and 10: a NaN variance estimate is
+    no spread); noise_np, the restatement of err_p and V_p, through it."""
+    tiny = np.finfo(T).tiny
+    x = np.array([-np.inf, -1.0, -tiny / 4, -0.0, 0.0, tiny / 4, tiny, 1.0, np.finfo(T).max, np.inf], T)
+    assert same_bits(positive_part(x), np.maximum(T(0), x) + T(0)) and positive_part(x).dtype == T
+    assert same_bits(positive_part(np.array([np.nan, -np.nan], T)), np.zeros(2, T)) and np.isnan(np.maximum(T(0), T(np.nan)))
+    # Y = Y(acc), s2, n -> (err, V): a finite pixel; s2 and the sum both overflowed (inf - inf); a NaN sum; s2 alone overflowed; n < 2
+    err, V = noise_np(np.array([3.0, np.inf, np.nan, 3.0, 3.0]), np.array([5.0, np.inf, np.nan, np.inf, 5.0]), np.array([2, 2, 2, 2, 1]), T)
+    assert err.dtype == np.float32 and V.dtype == T
+    assert err[0] == np.float32(np.sqrt(0.25) / (1.5 + 1e-3)) and V[0] == T(0.25)
+    assert err[1] == 0 and V[1] == 0 and np.isnan(err[2]) and V[2] == 0 and not np.signbit(V[1:3]).any()
+    assert err[3] == np.inf and V[3] == np.inf and err[4] == np.inf and V[4] == 0

@@ -19,13 +19,20 @@ class Cpu:
             self.cache[key] = make()
         return self.cache[key]
 
+    @staticmethod
+    def _name(scene_id):
+        """What a scene is cached under: its id, or the "name" of scene tables handed in as they are (tests/range_scene.py)."""
+        return scene_id["name"] if isinstance(scene_id, dict) else scene_id
+
     def hits(self, prec, scene_id, cam, F):
         rows = np.arange(cam.img_height)
-        return self._get(("hits", prec, scene_id, bytes(cam), F), lambda: output_hits(self.oracle, prec, scene_of(self.rt, scene_id, prec), cam, rows, F))
+        return self._get(("hits", prec, self._name(scene_id), bytes(cam), F),
+                         lambda: output_hits(self.oracle, prec, scene_of(self.rt, scene_id, prec), cam, rows, F))
 
     def layers(self, prec, scene_id, cam, G):
         rows = np.arange(cam.img_height)
-        return self._get(("layers", prec, scene_id, bytes(cam), G), lambda: coverage_np(self.oracle, prec, scene_of(self.rt, scene_id, prec), cam, rows, G)[:2])
+        return self._get(("layers", prec, self._name(scene_id), bytes(cam), G),
+                         lambda: coverage_np(self.oracle, prec, scene_of(self.rt, scene_id, prec), cam, rows, G)[:2])
 
 
 def colour(r, source, adaptive=False):
