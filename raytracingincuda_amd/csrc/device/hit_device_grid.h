@@ -13,7 +13,7 @@ namespace {
 //     cells {first, count} x nx nz | indices (32 bit) | AoS spheres {cx, cy, cz, r^2} x (n + 1) | direct table | direct ids
 // and a lane reads the record of each cell its ray crosses, the cell's slice of the index array and the listed spheres from there.
 //
-// Why the result is unchanged: hit_world_grid's argument, word for word.  The registration (half-width, eps, Rfar) is plan_grid's, the
+// Why the result is unchanged: hit_world_grid's argument, word for word.  The registration (half-width, eps, Rfar) is library/grid_plan.h's, the
 // setup below is hit_world_grid's (near / sane / crosses, clip_axis), every listed sphere is tested with the reference's arithmetic and
 // the ANYORDER tie rule, so the result is the lexicographic minimum of (root, index) over a superset of the spheres the reference
 // could accept.  Far, NaN and huge rays send the wave through the exact loop over the device table.
@@ -67,7 +67,7 @@ __device__ __forceinline__ void list_slot(const unsigned char* __restrict__ blob
     disc = RT_FMA(h, h, -(a * c));                                                  // :47
 }
 
-// The spheres of one cell, in pairs: a pair's two discriminants share one candidate branch (cell_tests, RTIOW_CELL_PAIRS == 2), and the
+// The spheres of one cell, in pairs: a pair's two discriminants share one candidate branch (as in cell_tests), and the
 // next pair runs behind ONE wave-level branch -- only while some lane of this step still has entries.  A lane whose list is shorter
 // tests the never-hit entry `pad` (index n of the sphere table) instead: no load outside its slice of the index array.  list_at: the
 // byte offset of the cell's slice from the blob's start.

@@ -71,10 +71,8 @@ __device__ __forceinline__ void load_sphere(const double* aos, int i, double& cx
 // Cells fill from slot 0 and pad with the never-hit entry (index n, `pad2` = n in both halves of a word): 35 % of the headline
 // scene's occupied cells hold one sphere, 43 % two, 18 % three, 5 % four (29 / 43 / 24 / 4 % on the 487-sphere scene).  Slots 2-3 are
 // therefore tested behind ONE wave-level branch: only when some lane of this step holds a third sphere -- 24 operations and
-// two gathers less for the late steps of a walk, which a handful of lanes run (RTIOW_CELL_PAIRS, default on; 0 = every slot always).
-#ifndef RTIOW_CELL_PAIRS
-#define RTIOW_CELL_PAIRS 2
-#endif
+// two gathers less for the late steps of a walk, which a handful of lanes run -- and pair after pair, each with its own candidate
+// branch: two discriminants live at a time instead of four.
 template <class T>
 __device__ __forceinline__ void cell_tests(const T* aos, unsigned rec_lo, unsigned rec_hi, unsigned pad2, V3<T> O, V3<T> D, T a, T& closest, int& hit, FastDiv<T> fd) {
     const int id[4] = {(int)(rec_lo & 0xffffu), (int)(rec_lo >> 16), (int)(rec_hi & 0xffffu), (int)(rec_hi >> 16)};
@@ -87,32 +85,16 @@ __device__ __forceinline__ void cell_tests(const T* aos, unsigned rec_lo, unsign
         const T c = RT_FMA(ocz, ocz, RT_FMA(ocy, ocy, ocx * ocx)) - r2;                  // :45
         disc[k] = RT_FMA(h[k], h[k], -(a * c));                                          // :47
     };
-    if (RTIOW_CELL_PAIRS == 2) {
-        // pair after pair, each with its own candidate branch: two discriminants live at a time instead of four
-        auto pair = [&](int k) __attribute__((always_inline)) {
-            slot(k); slot(k + 1);
-            if (Real<T>::fmax(disc[k], disc[k + 1]) >= (T)0) {                              // :48 for either of the two
-                PATH_STAT(PS_EXACT_BLOCK);
-                if (disc[k] >= (T)0) finish_sphere_test<T, true>(id[k], h[k], disc[k], a, closest, hit, fd);
-                if (disc[k + 1] >= (T)0) finish_sphere_test<T, true>(id[k + 1], h[k + 1], disc[k + 1], a, closest, hit, fd);
-            }
-        };
-        pair(0);
-        if (__builtin_amdgcn_ballot_w64(rec_hi != pad2) != 0) { PATH_STAT(PS_CELL_PAIR2); pair(2); }
-        return;
-    }
-    slot(0); slot(1);
-    if (RTIOW_CELL_PAIRS) {
-        h[2] = h[3] = (T)0; disc[2] = disc[3] = (T)-1;                                    // what a pad entry amounts to: never a candidate
-        if (__builtin_amdgcn_ballot_w64(rec_hi != pad2) != 0) { PATH_STAT(PS_CELL_PAIR2); slot(2); slot(3); }
-    } else { slot(2); slot(3); }
-    const T m = Real<T>::fmax(Real<T>::fmax(disc[0], disc[1]), Real<T>::fmax(disc[2], disc[3]));
-    if (m >= (T)0) {                                                                    // :48 for any of the four
-        PATH_STAT(PS_EXACT_BLOCK);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
+    auto pair = [&](int k) __attribute__((always_inline)) {
+        slot(k); slot(k + 1);
+        if (Real<T>::fmax(disc[k], disc[k + 1]) >= (T)0) {                                  // :48 for either of the two
+            PATH_STAT(PS_EXACT_BLOCK);
             if (disc[k] >= (T)0) finish_sphere_test<T, true>(id[k], h[k], disc[k], a, closest, hit, fd);
-    }
+            if (disc[k + 1] >= (T)0) finish_sphere_test<T, true>(id[k + 1], h[k + 1], disc[k + 1], a, closest, hit, fd);
+        }
+    };
+    pair(0);
+    if (__builtin_amdgcn_ballot_w64(rec_hi != pad2) != 0) { PATH_STAT(PS_CELL_PAIR2); pair(2); }
 }
 
 // v_min_f32 without the canonicalising v_max_f32 x, x the compiler puts in front of fminf's operands (IEEE minNum quiets signalling NaNs): the walk's
@@ -125,20 +107,9 @@ __device__ __forceinline__ float raw_min(float a, float b) {
 
 // Clip of o + t d against [lo, hi] on one axis, folded into [t0, t1].  Raw reciprocal: see eps above.
 // Returns the raw reciprocal of d it used (0 for a parallel ray): the walk steps with the same values.
+// Predicated: the parallel-ray case (|d| < 1e-30: [t0, t1] stays as it is inside [lo, hi] and is emptied outside) is three selects
+// instead of a divergent region per axis (exec-mask save / branch / restore, ~8 scalar instructions each, for a case no camera ray takes).
 __device__ __forceinline__ float clip_axis(float o, float d, float lo, float hi, float& t0, float& t1) {
-#ifdef RTIOW_CLIP_BRANCHES
-    if (__builtin_fabsf(d) < 1e-30f) {
-        if (!(o >= lo && o <= hi)) t1 = -__builtin_huge_valf();
-        return 0.0f;
-    }
-    const float inv = __builtin_amdgcn_rcpf(d);
-    const float ta = (lo - o) * inv, tb = (hi - o) * inv;
-    t0 = __builtin_fmaxf(t0, __builtin_fminf(ta, tb));
-    t1 = __builtin_fminf(t1, __builtin_fmaxf(ta, tb));
-    return inv;
-#else
-    // The same, predicated: the parallel-ray case is three selects instead of a divergent region per axis (exec-mask
-    // save / branch / restore, ~8 scalar instructions each, for a case no camera ray takes).
     const bool par = __builtin_fabsf(d) < 1e-30f;
     const float inv = __builtin_amdgcn_rcpf(d);
     const float ta = (lo - o) * inv, tb = (hi - o) * inv;
@@ -148,7 +119,6 @@ __device__ __forceinline__ float clip_axis(float o, float d, float lo, float hi,
     t0 = par ? t0 : n0;
     t1 = par ? (inside ? t1 : -__builtin_huge_valf()) : n1;
     return par ? 0.0f : inv;
-#endif
 }
 
 template <class T>
@@ -218,7 +188,6 @@ __device__ __forceinline__ void hit_world_grid(const RenderParams<T>& p, const T
         bool walking = near && crosses;
         if (__builtin_amdgcn_ballot_w64(walking) == 0) { REGION_END(walk, RG_GRID_WALK); return; }
         const T* aos = sizeof(T) == 4 ? reinterpret_cast<const T*>(smem_raw + g.aos_offset) : lds_exact;
-        const uint2* cells = reinterpret_cast<const uint2*>(smem_raw + g.cells_offset); (void)cells;
         const unsigned pad2 = (unsigned)p.n * 0x10001u;     // a cell record's upper word when slots 2 and 3 are pads
         const float px = __builtin_fmaf(t0, dx, ox), pz = __builtin_fmaf(t0, dz, oz);
         int cx = (int)__builtin_floorf(px * g.inv_cell), cz = (int)__builtin_floorf(pz * g.inv_cell);
@@ -230,10 +199,6 @@ __device__ __forceinline__ void hit_world_grid(const RenderParams<T>& p, const T
         int step_no = 0;                                   // which step of its walk the wave is in (instrumented build: profiles/r04/path_stats_walk_steps*.json)
         if (walking) PATH_STAT(PS_WALK);
 #endif
-#ifndef RTIOW_DDA_INCREMENTAL
-#define RTIOW_DDA_INCREMENTAL 1
-#endif
-#if RTIOW_DDA_INCREMENTAL
         // The classic incremental form (round 5): the parameters at which the ray leaves the current cell, per axis, are carried and ADVANCED by
         // cell * |1 / d| on the axis that steps, and the cell record's LDS address by +-8 bytes / +-8 nx bytes -- 18 vector instructions a step instead
         // of 30 (closed form: two int -> float conversions, two boundary products, the address from cz * nx + cx with a quarter-rate integer
@@ -271,32 +236,6 @@ __device__ __forceinline__ void hit_world_grid(const RenderParams<T>& p, const T
                 }
             }
         }
-#else
-        while (__builtin_amdgcn_ballot_w64(walking) != 0) {
-#ifdef RTIOW_PATH_STATS
-            ++step_no;
-#endif
-            if (walking) {
-                PATH_STAT(PS_GRID_STEP);
-#ifdef RTIOW_PATH_STATS
-                path_stat(step_no == 1 ? PS_STEP_1 : step_no == 2 ? PS_STEP_2 : step_no == 3 ? PS_STEP_3 : step_no == 4 ? PS_STEP_4 : step_no <= 8 ? PS_STEP_5_8 : PS_STEP_9_UP);
-#endif
-                const uint2 rec = cells[cz * g.nx + cx];
-                if (rec.x != 0xffffffffu) cell_tests<T>(aos, rec.x, rec.y, pad2, O, D, a, closest, hit, fdc);
-                // the parameter at which the ray leaves this cell, per axis
-                const float bx = (float)(cx + (sx > 0 ? 1 : 0)) * g.cell, bz = (float)(cz + (sz > 0 ? 1 : 0)) * g.cell;
-                const float tx = step_x ? (bx - ox) * inv_dx : __builtin_huge_valf();
-                const float tz = step_z ? (bz - oz) * inv_dz : __builtin_huge_valf();
-                const float tnext = __builtin_fminf(tx, tz);
-                const float tend = __builtin_fminf(t1, (float)closest);           // (float) rounds to nearest: covered by eps
-                if (tnext >= tend) walking = false;                               // leaves the slab / the grid, or a nearer hit is known
-                else {
-                    if (tx <= tz) cx += sx; else cz += sz;
-                    if ((unsigned)cx >= (unsigned)g.nx || (unsigned)cz >= (unsigned)g.nz) walking = false;
-                }
-            }
-        }
-#endif
         REGION_END(walk, RG_GRID_WALK);
     };
     if (fd.on) direct_list_and_walk(std::true_type{});

@@ -6,6 +6,7 @@
 #include "order_key.h"
 #include "launch_plan.h"
 #include "preview_state.h"
+#include "grid_plan.h"
 
 // A device allocation owned by the handle or by one call: freed when it goes out of scope.  ensure() grows it to at least `bytes`
 // and never shrinks it; the old allocation is freed before the new one is made, so its contents are lost.
@@ -59,7 +60,7 @@ struct rtiow_handle_s {
     // uniform grid over the small spheres (RTIOW_SCENE_GRID; built with the screening table)
     DeviceBuffer<> grid_blob;
     GridParams grid{};                            // offsets are relative to the blob until layout_lds places it in LDS
-    int grid_cells_bytes = 0, grid_aos_bytes = 0, grid_direct_bytes = 0, grid_ids_bytes = 0;
+    GridBlobOffsets grid_at;                      // where the blob's sections start
     int grid_direct = 0, grid_registered = 0;
     // what of the preview chain is current: every rule that reads or writes it is in preview_state.h
     PreviewState preview;

@@ -116,10 +116,7 @@ int layout_lds(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bo
     if (record_stats) { h->stats.grid_nx = h->stats.grid_nz = h->stats.grid_registered = h->stats.grid_direct = 0; h->stats.grid_cell = 0; }
     if (lds_source && h->scene_source == RTIOW_SCENE_GRID && p.use_screen && h->grid.use_grid && lds + (size_t)h->grid.blob_bytes <= 160 * 1024) {
         p.grid = h->grid;
-        p.grid.cells_offset = (int)lds;
-        p.grid.aos_offset = p.grid.cells_offset + h->grid_cells_bytes;
-        p.grid.direct_offset = p.grid.aos_offset + h->grid_aos_bytes;
-        p.grid.direct_ids_offset = p.grid.direct_offset + h->grid_direct_bytes;
+        place_grid_blob(p.grid, h->grid_at, lds);
         lds += (size_t)h->grid.blob_bytes;
         p.use_grid = 1;
         if (record_stats) { h->stats.grid_nx = h->grid.nx; h->stats.grid_nz = h->grid.nz; h->stats.grid_registered = h->grid_registered; h->stats.grid_direct = h->grid_direct; h->stats.grid_cell = h->grid.cell; }

@@ -12,19 +12,12 @@
 
 namespace {
 
-// The recentring point of the device grid: build_screen_table's -- the centroid of the spheres that are not ground-like, rounded to T --
-// over the finite spheres.  (The handle's own ctr is built only when an LDS source renders the scene.)
+// The recentring point of the device grid: build_screen_table's (grid_plan.h's recentring_point, rounded to T) over the finite spheres.
+// (The handle's own ctr is built only when an LDS source renders the scene.)
 template <class T>
 void large_centre(const rtiow_handle_s* h, double* ctr) {
-    const std::vector<double>& cr = h->host_cr;
-    double sum[3] = {0, 0, 0};
-    int cnt = 0;
-    for (int i = 0; i < h->n; ++i) {
-        bool ok = cr[4 * (size_t)i + 3] < 100.0;
-        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(cr[4 * (size_t)i + k]);
-        if (ok) { for (int k = 0; k < 3; ++k) sum[k] += cr[4 * (size_t)i + k]; ++cnt; }
-    }
-    for (int k = 0; k < 3; ++k) ctr[k] = (double)(T)(cnt ? sum[k] / cnt : 0.0);
+    recentring_point(h->n, h->host_cr, true, ctr);
+    for (int k = 0; k < 3; ++k) ctr[k] = (double)(T)ctr[k];
 }
 
 // Plan, blob and description of the device grid for the current scene, once per upload.  h->large_info.usable says whether the scene has one.
@@ -45,16 +38,8 @@ int ensure_large_grid(rtiow_handle_s* h) {
         if (b.bytes.size() >= 0x7fffffffull) return fail_arg(h, RTIOW_E_BADARG, "rtiow_render_large: the device grid of this scene exceeds 2 GiB; use rtiow_render");
         HIP_TRY(h, h->large_blob.ensure(b.bytes.size()));
         HIP_TRY(h, hipMemcpy(h->large_blob, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
-        g.use_grid = 1;
-        g.nx = pl.nx; g.nz = pl.nz;
-        g.x0 = pl.x0f; g.z0 = pl.z0f; g.cell = pl.cellf; g.inv_cell = (float)(1.0 / (double)pl.cellf);
-        g.ylo = std::nextafter((float)pl.ylo, -INFINITY); g.yhi = std::nextafter((float)pl.yhi, INFINITY);
-        g.far2 = (float)(pl.rfar * pl.rfar * 0.999);
-        for (int k = 0; k < 3; ++k) { g.core_lo[k] = std::nextafter((float)pl.core_lo[k], -INFINITY); g.core_hi[k] = std::nextafter((float)pl.core_hi[k], INFINITY); }
-        g.rmax2 = (float)(pl.rmax_g * pl.rmax_g * 1.0001);
-        g.cmax = (float)(pl.cmax_g * 1.0001);
-        g.n_direct_padded = b.n_direct_padded;
-        g.cells_offset = (int)b.cells_offset; g.aos_offset = (int)b.aos_offset; g.direct_offset = (int)b.direct_offset; g.direct_ids_offset = (int)b.direct_ids_offset;
+        fill_grid_params(g, pl);
+        place_grid_blob(g, b, 0);
         g.blob = h->large_blob;
         g.blob_bytes = (int)b.bytes.size();
         rtiow_large_grid_info& o = h->large_info;
