@@ -49,7 +49,7 @@ extern "C" {
                                  * lane walks the cells its ray crosses and tests only their spheres,
                                  * exactly; big spheres are tested by every ray.  Same image bit for
                                  * bit.  Scenes the grid does not suit run as RTIOW_SCENE_LDS.     */
-#define RTIOW_SCENE_DEVICE_GRID 4 /* rtiow_render_large only (rtiow_set_scene_source refuses it): a uniform grid
+#define RTIOW_SCENE_DEVICE_GRID 4 /* rtiow_render_large and the _large preview calls only (rtiow_set_scene_source refuses it): a uniform grid
                                  * whose cells, index lists and spheres stay in device memory; what
                                  * rtiow_stats.scene_source reads after that call                    */
 
@@ -792,7 +792,8 @@ int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_norm
  * scene or a camera and when the grid does not suit the scene (fewer than 24 spheres, fewer than 16 of them small enough for a cell,
  * or a list of big spheres longer than max(8, n / 6) or 2048): use rtiow_render -- there is no silent fall-back.  RTIOW_E_STATE
  * before rtiow_init_rng.
- * The accumulate / adaptive / budget calls, every preview call and the groups keep rtiow_render's sources. */
+ * The accumulate / adaptive / budget calls, every preview call and the groups keep rtiow_render's sources; the chunks, the guides and
+ * the coverage layers have _large twins of their own (below). */
 int rtiow_render_large(rtiow_handle h, float* kernel_ms);
 typedef struct {
     int32_t  usable;             /* 1: rtiow_render_large renders this scene; 0: it refuses (every other field is then 0)  */
@@ -809,6 +810,29 @@ typedef struct {
 /* The device grid of the handle's scene in the handle's precision, built here if no rtiow_render_large has built it yet (host work and one
  * upload; no kernel).  RTIOW_E_BADARG without a scene. */
 int rtiow_read_large_grid(rtiow_handle h, rtiow_large_grid_info* out);
+
+/* ---- The preview chain on large scenes: chunks, guides and coverage layers through the device grid.
+ * Five opt-in calls, each the twin of the call it is named after: the same buffers, state, checks, refusals (under the new name) and bits,
+ * with the scene read through the device grid of rtiow_render_large instead of the handle's scene source.  A _large call and its twin
+ * are interchangeable at every point of a session: a chunk through the grid may follow a chunk through rtiow_accumulate and the other way
+ * round, and every filter, the history, the plan, the edge resolve and the upscalers read what a _large call left exactly as they read
+ * what the twin leaves.  rtiow_stats reports scene_source == RTIOW_SCENE_DEVICE_GRID and the grid_* fields as after rtiow_render_large.
+ * A scene the device grid does not suit is refused as rtiow_render_large refuses it, RTIOW_E_BADARG with the text
+ * "<call>: the device grid does not suit this scene (...); use <twin>", after the twin's own checks of state and arguments and before
+ * anything changes; it is never rendered another way.  The calls remember nothing: a filter call that finds the guides or the layers
+ * stale renders them through the handle's scene source, as today, so the caller renders them with the _large call after each change of
+ * camera or scene.  Not available on groups. */
+/* rtiow_accumulate (threads_per_block_row has no twin: chunks always run through the persistent hand-out). */
+int rtiow_accumulate_large(rtiow_handle h, int samples, float* kernel_ms);
+/* rtiow_accumulate_adaptive. */
+int rtiow_accumulate_adaptive_large(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels);
+/* rtiow_accumulate_budget: RTIOW_E_STATE before a plan that is current. */
+int rtiow_accumulate_budget_large(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels);
+/* rtiow_render_guides: the first-hit guides, then the lens guides or else the specular chain, then the motion plane while an edit is in
+ * effect and the edit influence behind it: what rtiow_render_guides launches, in its order and under its conditions. */
+int rtiow_render_guides_large(rtiow_handle h, float* kernel_ms);
+/* rtiow_render_coverage: subsamples_per_side 2 or 4. */
+int rtiow_render_coverage_large(rtiow_handle h, int subsamples_per_side, float* kernel_ms);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

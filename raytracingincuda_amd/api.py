@@ -165,6 +165,11 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_upscale_wide": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_render_large": (_H, _f32p),
     "rtiow_read_large_grid": (_H, ctypes.POINTER(LargeGridInfo)),
+    "rtiow_accumulate_large": (_H, _int, _f32p),
+    "rtiow_accumulate_adaptive_large": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_accumulate_budget_large": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_render_guides_large": (_H, _f32p),
+    "rtiow_render_coverage_large": (_H, _int, _f32p),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -715,6 +720,47 @@ class Renderer:
         info = LargeGridInfo()
         self._check(self._lib.rtiow_read_large_grid(self._h, ctypes.byref(info)))
         return {name: getattr(info, name) for name, _ in LargeGridInfo._fields_ if name != "reserved"}
+
+    # The preview chain on large scenes: each the twin of the method it is named after, with the scene read
+    # through the device grid of render_large().  Same buffers, state, refusals and bits; the two are interchangeable at every point of a
+    # session.  RtiowError (RTIOW_E_BADARG) when the grid does not suit the scene -- use the twin then.  The calls remember nothing: a
+    # filter that finds the guides or the layers stale renders them through the handle's scene source, so call these after each change
+    # of camera or scene.
+    def accumulate_large(self, samples, sync=True):
+        """accumulate() through the device grid.  Returns the HIP-event kernel time in ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_large(self._h, int(samples), ms_out))
+        return ms.value if sync else None
+
+    def accumulate_adaptive_large(self, samples, rel_error, min_samples=0, max_samples=2 ** 31 - 1, sync=True):
+        """accumulate_adaptive() through the device grid.  Returns (kernel ms or None when sync=False, active pixels)."""
+        active = ctypes.c_int(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_adaptive_large(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
+                                                              ms_out, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
+
+    def accumulate_budget_large(self, samples=BUDGET_CHUNK, target=BUDGET_TARGET, min_samples=BUDGET_MIN_SAMPLES, max_samples=2 ** 31 - 1, sync=True):
+        """accumulate_budget() through the device grid.  Returns (kernel ms or None when sync=False, active pixels)."""
+        active = ctypes.c_int(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_budget_large(self._h, int(samples), int(min_samples), float(target), int(max_samples),
+                                                            ms_out, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
+
+    def render_guides_large(self, sync=True):
+        """render_guides() through the device grid: the first-hit guides, the lens guides or the specular chain, the motion plane and the
+        edit influence, as render_guides() renders them.  Returns the kernel ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_guides_large(self._h, ms_out))
+        return ms.value if sync else None
+
+    def render_coverage_large(self, subsamples_per_side=COVERAGE_GRID, sync=True):
+        """render_coverage() through the device grid.  Returns the kernel ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_coverage_large(self._h, int(subsamples_per_side), ms_out))
+        self._coverage_grid = int(subsamples_per_side)
+        return ms.value if sync else None
 
     def accumulate(self, samples, threads=0, sync=True):
         """Progressive rendering: add `samples` samples per pixel to the accumulation and write the preview to the framebuffer (bit for bit

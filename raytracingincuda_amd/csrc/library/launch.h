@@ -3,8 +3,10 @@
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
 // launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; prepare_upscale / finish_upscale: what the upscale launches share; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip alone); upscale_call: the body of both entry points
-// Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, of rtiow_upscale.hip for launch_upscale and of rtiow_upscale_wide.hip
-// for launch_upscale_wide (internal linkage).
+// launch_accumulate, launch_adaptive, launch_guides and launch_coverage take the scene binding of the call (StagedScene below for the calls
+// that stage the scene by the handle's scene source; rtiow_large_preview.hip's for the device grid): each launch is stated once.
+// Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, of rtiow_upscale.hip for launch_upscale, of rtiow_upscale_wide.hip
+// for launch_upscale_wide and of rtiow_large_preview.hip for the four launches over the device grid (internal linkage).
 #pragma once
 #include "scene_tables.h"
 #include "../device/render_kernels.h"
@@ -21,6 +23,16 @@
 #include "../device/edge_resolve.h"
 #include "../device/upscale.h"
 #include "../device/upscale_wide.h"
+
+// The kernels of a chunk and of the guides that read no scene (the selects and the finish of an adaptive chunk, the edit influence) live in
+// rtiow_hip.hip's code object alone: launch_adaptive and launch_guides enqueue them through these, whichever unit instantiates the launch.
+// Defined in rtiow_hip.hip from the handle's own buffers, in its precision; not exported (librtiow_hip.map).
+namespace rtiow_shared {
+int enqueue_adaptive_select(rtiow_handle_s* h, int samples, int min_samples, int max_samples, bool budget, double rel_error, double target,
+                            const unsigned char* mid_in, unsigned char* mid_out);
+int enqueue_adaptive_finish(rtiow_handle_s* h, const unsigned char* mid_out);
+int enqueue_edit_influence(rtiow_handle_s* h);
+}  // namespace rtiow_shared
 
 namespace {
 
@@ -125,16 +137,33 @@ int layout_lds(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bo
     return 0;
 }
 
+// The scene binding of a launch: how the scene reaches its kernels.  prepare(h, call): what the entry point does for the scene
+// before it changes any state (a refusal under the call's name); layout: the parameters and the LDS of the launch; by_source: the scene-source
+// template argument of the kernels for that layout; accumulate_kernel / adaptive_kernel: the persistent kernels of a chunk.  This one is
+// the binding of every call that stages the scene by the handle's scene source: layout_lds, RTIOW_SCENE_LDS or RTIOW_SCENE_SCALAR, the
+// render_* kernels.  The device grid's is rtiow_large_preview.hip's.
+struct StagedScene {
+    int prepare(rtiow_handle_s*, const char*) const { return 0; }
+    template <class T>
+    int layout(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bool record_stats) const { return layout_lds<T>(h, L, threads, persistent, record_stats); }
+    template <class T, class F>
+    auto by_source(const Launch<T>& L, F f) const { return ::by_source(L.lds_source, f); }
+    template <class T, class SRC, class BOUNDED>
+    RenderFn<T> accumulate_kernel(SRC, BOUNDED) const { return render_accumulate_kernel<T, SRC::value, BOUNDED::value>; }
+    template <class T, class SRC, class BOUNDED>
+    RenderFn<T> adaptive_kernel(SRC, BOUNDED) const { return render_adaptive_kernel<T, SRC::value, BOUNDED::value>; }
+};
+
 // The setup the persistent launches share (launch_render's dynamic schedules, launch_accumulate, launch_adaptive): four-wave 16 x 16
-// workgroups, the main launch's clock stamps (stamp_clock), the LDS layout with drain scratch, the kernel pick(src, bounded) -- bounded:
-// std::true_type for fp32's bounded twin only -- allowed its LDS, and the two hand-out counters.
-template <class T, class Pick>
-int persistent_setup(rtiow_handle_s* h, Launch<T>& L, bool stamp_clock, bool record_stats, Pick pick) {
+// workgroups, the main launch's clock stamps (stamp_clock), the scene's LDS layout with drain scratch, the kernel pick(src, bounded) --
+// bounded: std::true_type for fp32's bounded twin only -- allowed its LDS, and the two hand-out counters.
+template <class T, class Scene, class Pick>
+int persistent_setup(rtiow_handle_s* h, Launch<T>& L, const Scene& scene, bool stamp_clock, bool record_stats, Pick pick) {
     block_shape(0, false, L.p.cold.bx, L.p.cold.by, L.p.cold.wave_tiles);
     L.p.cold.clock_stamps = stamp_clock && h->clock_stamps_dev ? h->clock_stamps_dev + 4 : nullptr;
-    if (int rc = layout_lds<T>(h, L, 256, true, record_stats)) return rc;
-    L.k = by_source(L.lds_source, [&](auto src) { return pick(src, std::false_type()); });
-    if constexpr (sizeof(T) == 4) L.kb = by_source(L.lds_source, [&](auto src) { return pick(src, std::true_type()); });
+    if (int rc = scene.template layout<T>(h, L, 256, true, record_stats)) return rc;
+    L.k = scene.by_source(L, [&](auto src) { return pick(src, std::false_type()); });
+    if constexpr (sizeof(T) == 4) L.kb = scene.by_source(L, [&](auto src) { return pick(src, std::true_type()); });
     HIP_TRY(h, allow_lds(L.k, L.lds));
     HIP_TRY(h, h->work_counter.ensure(2 * sizeof(unsigned int)));
     return 0;
@@ -238,7 +267,7 @@ int launch_render(rtiow_handle_s* h, int bx, int by, int wave_tiles, unsigned lo
         grid = dim3((p.cold.W + bx - 1) / bx, (h->local_rows + by - 1) / by);
         L.blocks = (long long)grid.x * grid.y;
     } else {
-        int rc = persistent_setup(h, L, !count, !count, [&](auto src, auto bounded) {
+        int rc = persistent_setup(h, L, StagedScene{}, !count, !count, [&](auto src, auto bounded) {
             return count ? render_persistent_kernel<T, src, true, bounded> : render_persistent_kernel<T, src, false, bounded>;
         });
         if (rc) return rc;
@@ -368,13 +397,13 @@ int launch_scatter_probe(rtiow_handle_s* h, int form, int n, const T* in_r, cons
 // render_accumulate_kernel, always with the persistent hand-out.  The first chunk after a reset starts from the RNG states of rtiow_init_rng
 // in tile order; under RTIOW_SCHED_SORTED every later chunk ranks the pixels heavy-first by the segments each ran in the previous chunk
 // (same limits as launch_render).  No solo waves, no staged stores: the preview is stored at its pixel.  timed: the start event goes
-// behind the allocations and table builds, in front of the first enqueued work.
-template <class T>
-int launch_accumulate(rtiow_handle_s* h, int samples, bool timed) {
+// behind the allocations and table builds, in front of the first enqueued work.  scene: the binding (StagedScene for rtiow_accumulate).
+template <class T, class Scene>
+int launch_accumulate(rtiow_handle_s* h, const Scene& scene, int samples, bool timed) {
     Launch<T> L{make_params<T>(h)};
     RenderParams<T>& p = L.p;
     LaunchPlan P = new_plan(h, p);
-    int rc = persistent_setup(h, L, timed, true, [](auto src, auto bounded) { return render_accumulate_kernel<T, src, bounded>; });
+    int rc = persistent_setup(h, L, scene, timed, true, [&](auto src, auto bounded) { return scene.template accumulate_kernel<T>(src, bounded); });
     if (rc) return rc;
     if ((rc = size_persistent<T>(h, L, P, plan_tile_slots(p.cold.W, h->local_rows)))) return rc;
     const int n = h->preview.acc_samples;
@@ -422,12 +451,12 @@ struct AdaptiveRule {
     bool budget;                                         // false: adaptive_select_kernel by rel_error; true: budget_select_kernel by target
     double rel_error, target;
 };
-template <class T>
-int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRule rule, int max_samples, bool timed, int& active) {
+template <class T, class Scene>
+int launch_adaptive(rtiow_handle_s* h, const Scene& scene, int samples, int min_samples, AdaptiveRule rule, int max_samples, bool timed, int& active) {
     Launch<T> L{make_params<T>(h)};
     RenderParams<T>& p = L.p;
     LaunchPlan P = new_plan(h, p);
-    int rc = persistent_setup(h, L, timed, true, [](auto src, auto bounded) { return render_adaptive_kernel<T, src, bounded>; });
+    int rc = persistent_setup(h, L, scene, timed, true, [&](auto src, auto bounded) { return scene.template adaptive_kernel<T>(src, bounded); });
     if (rc) return rc;
 
     const int W = p.cold.W, npix = W * h->local_rows;
@@ -445,14 +474,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
 
     if (timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->adapt_ctr, 0, 2 * sizeof(unsigned), h->stream));
-    const dim3 select_grid((unsigned)((plan_tiles(W, h->local_rows) + 3) / 4));
-    if (rule.budget)
-        hipLaunchKernelGGL(budget_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
-                           (T)rule.target, h->adapt_counts, h->plan_m.as<const T>(), h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
-    else
-        hipLaunchKernelGGL(adaptive_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
-                           rule.rel_error, h->adapt_counts, h->adapt_err, h->rng, p.cold.mid_in, p.cold.mid_out, h->order, h->adapt_ctr);
-    HIP_TRY(h, hipGetLastError());
+    if ((rc = rtiow_shared::enqueue_adaptive_select(h, samples, min_samples, max_samples, rule.budget, rule.rel_error, rule.target, p.cold.mid_in, p.cold.mid_out))) return rc;
     if (timed) HIP_TRY(h, hipEventRecord(h->ev_a, h->stream));
     unsigned n_active = 0;
     HIP_TRY(h, hipMemcpyAsync(&n_active, h->adapt_ctr, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
@@ -474,9 +496,7 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
         HIP_TRY(h, hipGetLastError());
     }
     h->order_rec = plan_adaptive_record(P);
-    hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (size_t)npix, (const unsigned char*)p.cold.mid_out,
-                       p.cold.fb, h->adapt_counts, h->adapt_err, h->adapt_ctr + 1);
-    HIP_TRY(h, hipGetLastError());
+    if ((rc = rtiow_shared::enqueue_adaptive_finish(h, p.cold.mid_out))) return rc;
     h->acc_cur = out;
     record_launch(h, L, plan_stats(P));
     h->stats.primary_rays = (uint64_t)n_active * (uint64_t)samples;
@@ -491,16 +511,16 @@ int launch_adaptive(rtiow_handle_s* h, int samples, int min_samples, AdaptiveRul
 // the motion plane to h->motion_qc / h->motion_ids, sized by the current frame; the table it reads is rtiow_edit_scene's.  With edit
 // influence on (rtiow_set_edit_influence, kappa > 0) edit_influence_kernel follows it, one lane per pixel in 16 x 16 workgroups: it writes
 // lambda to h->edit_lambda and the fade over the carry of h->motion_qc, from the guides, the ids and rtiow_edit_scene's edit list.
-template <class T>
-int launch_guides(rtiow_handle_s* h) {
+template <class T, class Scene>
+int launch_guides(rtiow_handle_s* h, const Scene& scene) {
     Launch<T> L{make_params<T>(h)};
     const int threads = 256;
-    int rc = layout_lds<T>(h, L, threads, false, false);
+    int rc = scene.template layout<T>(h, L, threads, false, false);
     if (rc) return rc;
     const size_t npix = local_pixels(h);
     HIP_TRY(h, h->guide_nd.ensure(npix * 4 * sizeof(T)));
     HIP_TRY(h, h->guide_alb.ensure(npix * 4 * sizeof(T)));
-    const auto k = by_source(L.lds_source, [](auto src) { return guide_kernel<T, src>; });
+    const auto k = scene.by_source(L, [](auto src) { return guide_kernel<T, src>; });
     HIP_TRY(h, allow_lds(k, L.lds));
     const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_nd.as<T>(), h->guide_alb.as<T>());
@@ -508,7 +528,7 @@ int launch_guides(rtiow_handle_s* h) {
     if (lens_in_effect(h)) {
         HIP_TRY(h, h->chain_nd.ensure(npix * 4 * sizeof(T)));
         HIP_TRY(h, h->chain_alb.ensure(npix * 4 * sizeof(T)));
-        const auto kl = by_source(L.lds_source, [](auto src) { return guide_lens_kernel<T, src>; });
+        const auto kl = scene.by_source(L, [](auto src) { return guide_lens_kernel<T, src>; });
         HIP_TRY(h, allow_lds(kl, L.lds));
         const bool chain = h->guide_mode == RTIOW_GUIDES_SPECULAR;   // RTIOW_GUIDES_FIRST_HIT: every chain ends at its first hit
         hipLaunchKernelGGL(kl, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_lens, chain ? h->guide_max_bounces : 0,
@@ -517,7 +537,7 @@ int launch_guides(rtiow_handle_s* h) {
     } else if (h->guide_mode == RTIOW_GUIDES_SPECULAR) {
         HIP_TRY(h, h->chain_nd.ensure(npix * 4 * sizeof(T)));
         HIP_TRY(h, h->chain_alb.ensure(npix * 4 * sizeof(T)));
-        const auto kc = by_source(L.lds_source, [](auto src) { return guide_chain_kernel<T, src>; });
+        const auto kc = scene.by_source(L, [](auto src) { return guide_chain_kernel<T, src>; });
         HIP_TRY(h, allow_lds(kc, L.lds));
         hipLaunchKernelGGL(kc, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->guide_max_bounces, h->guide_max_fuzz,
                            h->chain_nd.as<T>(), h->chain_alb.as<T>());
@@ -526,23 +546,14 @@ int launch_guides(rtiow_handle_s* h) {
     if (motion_in_effect(h->preview)) {
         HIP_TRY(h, h->motion_qc.ensure(npix * sizeof(Vec4<T>)));
         HIP_TRY(h, h->motion_ids.ensure(npix * sizeof(int32_t)));
-        const auto km = by_source(L.lds_source, [](auto src) { return surface_motion_kernel<T, src>; });
+        const auto km = scene.by_source(L, [](auto src) { return surface_motion_kernel<T, src>; });
         HIP_TRY(h, allow_lds(km, L.lds));
         hipLaunchKernelGGL(km, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, h->motion_snap.as<const Vec4<T>>(),
                            (const int32_t*)h->motion_flags, h->motion_qc.as<Vec4<T>>(), (int32_t*)h->motion_ids);
         HIP_TRY(h, hipGetLastError());
         if (influence_in_effect(h->preview)) {
             HIP_TRY(h, h->edit_lambda.ensure(npix * sizeof(T)));
-            const auto& c = camera<T>(h);
-            InfluenceParams<T> ip{};
-            ip.O = L.p.cam.center; ip.pixel00 = L.p.cam.pixel00; ip.du = L.p.cam.du; ip.dv = L.p.cam.dv;
-            ip.kappa = (T)h->edit_kappa;
-            ip.W = c.img_width; ip.local_rows = h->local_rows; ip.strip_rows = h->strip_rows; ip.nranks = h->preview.nranks; ip.rank = h->rank;
-            ip.entries = h->edit_entries;
-            hipLaunchKernelGGL(edit_influence_kernel<T>, dim3((unsigned)((ip.W + 15) / 16), (unsigned)((ip.local_rows + 15) / 16)), dim3(256), 0, h->stream, ip, h->guide_nd.as<const Vec4<T>>(),
-                               (const int32_t*)h->motion_ids, h->edit_list.as<const Vec4<T>>(), (const int32_t*)h->edit_owner, h->motion_qc.as<Vec4<T>>(),
-                               h->edit_lambda.as<T>());
-            HIP_TRY(h, hipGetLastError());
+            if ((rc = rtiow_shared::enqueue_edit_influence(h))) return rc;
         }
     }
     on_guides_rendered(h->preview);
@@ -551,16 +562,16 @@ int launch_guides(rtiow_handle_s* h) {
 
 // The coverage layers of every local pixel (rtiow_render_coverage) into h->cov_ic / h->cov_nz: coverage_kernel on the layout and grid of
 // launch_guides, with `grid` sub-samples per side (2 or 4: the caller has checked).
-template <class T>
-int launch_coverage(rtiow_handle_s* h, int grid) {
+template <class T, class Scene>
+int launch_coverage(rtiow_handle_s* h, const Scene& scene, int grid) {
     Launch<T> L{make_params<T>(h)};
     const int threads = 256;
-    int rc = layout_lds<T>(h, L, threads, false, false);
+    int rc = scene.template layout<T>(h, L, threads, false, false);
     if (rc) return rc;
     const size_t npix = local_pixels(h);
     HIP_TRY(h, h->cov_ic.ensure(npix * sizeof(int4)));
     HIP_TRY(h, h->cov_nz.ensure(npix * 2 * sizeof(Vec4<T>)));
-    const auto k = by_source(L.lds_source, [](auto src) { return coverage_kernel<T, src>; });
+    const auto k = scene.by_source(L, [](auto src) { return coverage_kernel<T, src>; });
     HIP_TRY(h, allow_lds(k, L.lds));
     const int tiles = ((L.p.cold.W + 7) / 8) * ((h->local_rows + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + 3) / 4)), dim3(threads), L.lds, h->stream, L.p, grid, h->cov_ic.as<int4>(), h->cov_nz.as<Vec4<T>>());

@@ -29,6 +29,54 @@
 // with -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt, denormals preserved.
 
 #include "library/unit.h"
+#include "library/scene_calls.h"
+
+// The kernels of launch.h's rtiow_shared: instantiated here alone, enqueued from the handle's own buffers in its precision.
+namespace rtiow_shared {
+int enqueue_adaptive_select(rtiow_handle_s* h, int samples, int min_samples, int max_samples, bool budget, double rel_error, double target,
+                            const unsigned char* mid_in, unsigned char* mid_out) {
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        const int W = img_w(h);
+        const dim3 select_grid((unsigned)((plan_tiles(W, h->local_rows) + 3) / 4));
+        if (budget)
+            hipLaunchKernelGGL(budget_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
+                               (T)target, h->adapt_counts, h->plan_m.as<const T>(), h->rng, mid_in, mid_out, h->order, h->adapt_ctr);
+        else
+            hipLaunchKernelGGL(adaptive_select_kernel<T>, select_grid, dim3(256), 0, h->stream, FrameShape{W, h->local_rows}, samples, min_samples, max_samples,
+                               rel_error, h->adapt_counts, h->adapt_err, h->rng, mid_in, mid_out, h->order, h->adapt_ctr);
+        HIP_TRY(h, hipGetLastError());
+        return 0;
+    });
+}
+int enqueue_adaptive_finish(rtiow_handle_s* h, const unsigned char* mid_out) {
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        const size_t npix = local_pixels(h);
+        hipLaunchKernelGGL(adaptive_finish_kernel<T>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, npix, mid_out,
+                           (T*)h->fb, h->adapt_counts, h->adapt_err, h->adapt_ctr + 1);
+        HIP_TRY(h, hipGetLastError());
+        return 0;
+    });
+}
+int enqueue_edit_influence(rtiow_handle_s* h) {
+    return by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        const auto& c = camera<T>(h);
+        InfluenceParams<T> ip{};
+        ip.O = {c.center[0], c.center[1], c.center[2]}; ip.pixel00 = {c.pixel00_loc[0], c.pixel00_loc[1], c.pixel00_loc[2]};
+        ip.du = {c.pixel_delta_u[0], c.pixel_delta_u[1], c.pixel_delta_u[2]}; ip.dv = {c.pixel_delta_v[0], c.pixel_delta_v[1], c.pixel_delta_v[2]};
+        ip.kappa = (T)h->edit_kappa;
+        ip.W = c.img_width; ip.local_rows = h->local_rows; ip.strip_rows = h->strip_rows; ip.nranks = h->preview.nranks; ip.rank = h->rank;
+        ip.entries = h->edit_entries;
+        hipLaunchKernelGGL(edit_influence_kernel<T>, dim3((unsigned)((ip.W + 15) / 16), (unsigned)((ip.local_rows + 15) / 16)), dim3(256), 0, h->stream, ip, h->guide_nd.as<const Vec4<T>>(),
+                           (const int32_t*)h->motion_ids, h->edit_list.as<const Vec4<T>>(), (const int32_t*)h->edit_owner, h->motion_qc.as<Vec4<T>>(),
+                           h->edit_lambda.as<T>());
+        HIP_TRY(h, hipGetLastError());
+        return 0;
+    });
+}
+}  // namespace rtiow_shared
 
 extern "C" {
 
@@ -80,9 +128,6 @@ static void release_stream(int device, hipStream_t s) {
 
 // The snapshot of the scene the base was committed under goes wherever the base goes (rtiow_history_reset, rtiow_set_scene, rtiow_set_shard).
 void drop_snapshot(rtiow_handle_s* h) { h->snap_geom.clear(); h->snap_mat.clear(); h->from_snapshot.clear(); }
-
-// The times a render call on a shard without rows reports.
-void zero_times(rtiow_handle_s* h) { h->stats.render_ms = 0; h->stats.prepass_ms = 0; h->stats.main_ms = 0; }
 
 }  // namespace
 
@@ -411,27 +456,7 @@ int rtiow_accumulate_reset(rtiow_handle h) {
 int rtiow_accumulate(rtiow_handle h, int samples, int threads_per_block_row, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
     (void)threads_per_block_row;                         // chunks always run through the persistent hand-out
-    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_accumulate"));
-    PREVIEW_TRY(h, need_rng(h->preview, "rtiow_accumulate"));
-    if (samples <= 0 || samples > 0x7fffffff - h->preview.acc_samples) return fail_arg(h, RTIOW_E_BADARG, "rtiow_accumulate: samples must be > 0 and keep the total below 2^31");
-    PREVIEW_TRY(h, need_no_chunk_of(h->preview, "rtiow_accumulate", ACC_MODE_ADAPTIVE));
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_framebuffer(h);
-    if (rc) return rc;
-    h->render_pending = false;                           // the chunk reuses the start / stop events of rtiow_render_async
-    if (kernel_ms) *kernel_ms = 0;
-    on_chunk_begin(h->preview);
-    if (h->local_rows == 0) { zero_times(h); on_plain_chunk(h->preview, samples); return 0; }
-    const bool timed = kernel_ms != nullptr;
-    if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
-    if ((rc = by_precision(h, [&](auto t) { return launch_accumulate<decltype(t)>(h, samples, timed); }))) return rc;
-    on_plain_chunk(h->preview, samples);
-    h->stats.prepass_ms = 0; h->stats.place_ms = 0;
-    if (timed) {                                         // the start event: launch_accumulate, behind its allocations
-        if ((rc = timed_end(h, kernel_ms))) return rc;
-        h->stats.render_ms = *kernel_ms; h->stats.main_ms = *kernel_ms;
-    }
-    return 0;
+    return accumulate_call(h, "rtiow_accumulate", StagedScene{}, samples, kernel_ms);
 }
 
 int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
@@ -450,58 +475,15 @@ int rtiow_accumulated_samples(rtiow_handle h, int* samples) {
     return 0;
 }
 
-namespace {
-// What rtiow_accumulate_adaptive and rtiow_accumulate_budget (`call`) share: the checks (rule_ok, rule_text: the rule's own argument), the chunk and its times.
-int adaptive_chunk(rtiow_handle_s* h, const char* call, int samples, int min_samples, AdaptiveRule rule, bool rule_ok, const char* rule_text,
-                   int max_samples, float* kernel_ms, int* active_pixels) {
-    if (active_pixels) *active_pixels = 0;
-    if (kernel_ms) *kernel_ms = 0;
-    PREVIEW_TRY(h, need_scene(h->preview, call));
-    PREVIEW_TRY(h, need_rng(h->preview, call));
-    if (samples <= 0 || min_samples < 0 || max_samples < min_samples || !rule_ok)
-        return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": need samples > 0, 0 <= min_samples <= max_samples, " + rule_text).c_str());
-    if (!plan_order_fits(img_w(h), h->local_rows))
-        return fail_arg(h, RTIOW_E_BADARG, (std::string(call) + ": frames wider than 65535 or with more than 32767 local rows are not supported").c_str());
-    PREVIEW_TRY(h, need_no_chunk_of(h->preview, call, ACC_MODE_PLAIN));
-    if (rule.budget) PREVIEW_TRY(h, need_plan(h->preview, call));
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_framebuffer(h);
-    if (rc) return rc;
-    h->render_pending = false;                           // the chunk reuses the events of rtiow_render_async
-    on_chunk_begin(h->preview);
-    if (h->local_rows == 0) { zero_times(h); h->stats.primary_rays = 0; on_adaptive_chunk(h->preview); return 0; }
-    const bool timed = kernel_ms != nullptr;
-    if (h->clock_stamps) std::memset(h->clock_stamps, 0, 8 * sizeof(unsigned long long));
-    int active = 0;
-    rc = by_precision(h, [&](auto t) { return launch_adaptive<decltype(t)>(h, samples, min_samples, rule, max_samples, timed, active); });
-    if (rc) return rc;
-    on_adaptive_chunk(h->preview);
-    if (active_pixels) *active_pixels = active;
-    h->stats.prepass_ms = 0; h->stats.place_ms = 0;
-    if (timed) {
-        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(h, hipEventSynchronize(h->ev1));
-        float a = 0, b = 0;
-        HIP_TRY(h, hipEventElapsedTime(&a, h->ev0, h->ev_a));
-        HIP_TRY(h, hipEventElapsedTime(&b, h->ev_b, h->ev1));
-        *kernel_ms = a + b;
-        h->stats.render_ms = a + b; h->stats.main_ms = a + b;
-    }
-    return 0;
-}
-}  // namespace
-
 int rtiow_accumulate_adaptive(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels) {
     if (!h) return RTIOW_E_BADARG;
-    return adaptive_chunk(h, "rtiow_accumulate_adaptive", samples, min_samples, AdaptiveRule{false, rel_error, 0.0}, rel_error >= 0, "rel_error >= 0",
-                          max_samples, kernel_ms, active_pixels);
+    return adaptive_call(h, "rtiow_accumulate_adaptive", StagedScene{}, samples, min_samples, rel_error, max_samples, kernel_ms, active_pixels);
 }
 
 // ---- History-guided sample budgets
 int rtiow_accumulate_budget(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels) {
     if (!h) return RTIOW_E_BADARG;
-    return adaptive_chunk(h, "rtiow_accumulate_budget", samples, min_samples, AdaptiveRule{true, 0.0, target}, target > 0, "target > 0 (+inf: everybody)",
-                          max_samples, kernel_ms, active_pixels);
+    return budget_call(h, "rtiow_accumulate_budget", StagedScene{}, samples, min_samples, target, max_samples, kernel_ms, active_pixels);
 }
 
 int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, size_t npix) {
@@ -523,7 +505,7 @@ int rtiow_read_adaptive_state(rtiow_handle h, int32_t* counts, float* rel_err, s
 // ---- Denoised previews
 namespace {
 int render_guides(rtiow_handle_s* h) {
-    return by_precision(h, [&](auto t) { return launch_guides<decltype(t)>(h); });
+    return by_precision(h, [&](auto t) { return launch_guides<decltype(t)>(h, StagedScene{}); });
 }
 // What the calls that filter, reproject or plan share once they have checked their arguments and the state: the pass, enqueued by
 // pass(T()) in the handle's precision, between the events of kernel_ms and behind guides that are current (extern "C++": a template).
@@ -573,14 +555,7 @@ int rtiow_read_linear(rtiow_handle h, void* host_rgb, size_t bytes) {
 
 int rtiow_render_guides(rtiow_handle h, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
-    if (kernel_ms) *kernel_ms = 0;
-    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_render_guides"));
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->local_rows == 0) { on_guides_rendered(h->preview); return 0; }
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if ((rc = render_guides(h))) return rc;
-    return timed_end(h, kernel_ms);
+    return guides_call(h, "rtiow_render_guides", StagedScene{}, kernel_ms);
 }
 
 namespace {
@@ -859,15 +834,7 @@ int rtiow_read_history_variance(rtiow_handle h, void* var, size_t npix) {
 // ---- Edge resolve
 int rtiow_render_coverage(rtiow_handle h, int subsamples_per_side, float* kernel_ms) {
     if (!h) return RTIOW_E_BADARG;
-    if (kernel_ms) *kernel_ms = 0;
-    PREVIEW_TRY(h, check_coverage_grid("rtiow_render_coverage", subsamples_per_side));
-    PREVIEW_TRY(h, need_scene(h->preview, "rtiow_render_coverage"));
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->local_rows == 0) { on_coverage_rendered(h->preview, subsamples_per_side); return 0; }
-    int rc = timed_begin(h, kernel_ms);
-    if (rc) return rc;
-    if ((rc = by_precision(h, [&](auto t) { return launch_coverage<decltype(t)>(h, subsamples_per_side); }))) return rc;
-    return timed_end(h, kernel_ms);
+    return coverage_call(h, "rtiow_render_coverage", StagedScene{}, subsamples_per_side, kernel_ms);
 }
 
 int rtiow_read_coverage(rtiow_handle h, int32_t* ids, int32_t* counts, void* normal, void* depth, size_t npix) {
@@ -901,7 +868,7 @@ int rtiow_resolve_edges(rtiow_handle h, int radius, double sigma_normal, double 
     auto pass = [&](auto t) {                                // stale layers first, like run_pass's stale guides: inside kernel_ms
         using T = decltype(t);
         if (!h->preview.coverage_ok) {
-            if (int rc = launch_coverage<T>(h, grid)) return rc;
+            if (int rc = launch_coverage<T>(h, StagedScene{}, grid)) return rc;
         }
         return launch_edge_resolve<T>(h, radius, inv2, prior);
     };
