@@ -772,7 +772,7 @@ int rtiow_upscaled_device_ptr(rtiow_handle h, void** device_ptr, size_t* bytes);
  *   the gamma store; *covered_pixels; the guides are the FIRST-HIT buffers whatever the guide mode and lens knob; stale guides and, with
  *   the share, stale layers are rendered first inside kernel_ms; both out-pointers NULL: asynchronous on the handle's stream.
  * The call writes the handle's upscaled buffer: rtiow_read_upscaled and rtiow_upscaled_device_ptr serve whichever of rtiow_upscale and
- * rtiow_upscale_wide ran last, and the image goes stale by the same rule.
+ * rtiow_upscale_wide (or of their _large twins below) ran last, and the image goes stale by the same rule.
  * Refusals: rtiow_upscale's, in its order, under this call's name; a sharded handle is refused; not available on groups.  A NULL
  * handle: -1 before any device work.  A failing call leaves the handle as it was. */
 int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
@@ -792,8 +792,8 @@ int rtiow_upscale_wide(rtiow_handle h, int factor, int source, double sigma_norm
  * scene or a camera and when the grid does not suit the scene (fewer than 24 spheres, fewer than 16 of them small enough for a cell,
  * or a list of big spheres longer than max(8, n / 6) or 2048): use rtiow_render -- there is no silent fall-back.  RTIOW_E_STATE
  * before rtiow_init_rng.
- * The accumulate / adaptive / budget calls, every preview call and the groups keep rtiow_render's sources; the chunks, the guides and
- * the coverage layers have _large twins of their own (below). */
+ * The accumulate / adaptive / budget calls, every preview call and the groups keep rtiow_render's sources; the chunks, the guides, the
+ * coverage layers and the two upscalers have _large twins of their own (below). */
 int rtiow_render_large(rtiow_handle h, float* kernel_ms);
 typedef struct {
     int32_t  usable;             /* 1: rtiow_render_large renders this scene; 0: it refuses (every other field is then 0)  */
@@ -833,6 +833,26 @@ int rtiow_accumulate_budget_large(rtiow_handle h, int samples, int min_samples, 
 int rtiow_render_guides_large(rtiow_handle h, float* kernel_ms);
 /* rtiow_render_coverage: subsamples_per_side 2 or 4. */
 int rtiow_render_coverage_large(rtiow_handle h, int subsamples_per_side, float* kernel_ms);
+
+/* ---- Guided upscaling on large scenes: the upscalers through the device grid.
+ * rtiow_upscale and rtiow_upscale_wide trace one primary ray for every output pixel through the handle's scene source: on a scene beyond
+ * the LDS that is the exact loop over every sphere, factor x factor times per traced pixel.  These two opt-in calls are their twins in
+ * the sense of the five calls above -- the same buffers, state, checks, refusals (under the new name), image and *covered_pixels, bit for
+ * bit -- with that ray traced through the device grid of rtiow_render_large.  They write the handle's upscaled buffer:
+ * rtiow_read_upscaled and rtiow_upscaled_device_ptr serve whichever of the four upscale calls ran last, and the image goes stale by
+ * rtiow_upscale's rule and by nothing else.  Stale guides and, with use_coverage, stale layers are rendered first inside kernel_ms as by
+ * the twin, but through rtiow_render_guides_large and rtiow_render_coverage_large (the layers at the twin's subsamples_per_side): other
+ * kernels, the same bits.  rtiow_stats reports scene_source == RTIOW_SCENE_DEVICE_GRID and the grid_* fields afterwards.
+ * Refusals: the twin's, in its order, under this call's name (a sharded handle among them); behind them, and before anything changes --
+ * an image of an earlier call stays readable with its bits --, a scene the device grid does not suit: RTIOW_E_BADARG, "<call>: the
+ * device grid does not suit this scene (...); use <twin>".  There is no silent fall-back.  The LDS refusal of the twin stays, in front
+ * of the buffers.  A NULL handle: -1 before any device work.  Not available on groups. */
+/* rtiow_upscale. */
+int rtiow_upscale_large(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                        int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+/* rtiow_upscale_wide. */
+int rtiow_upscale_wide_large(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                             int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

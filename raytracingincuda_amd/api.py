@@ -170,6 +170,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_accumulate_budget_large": (_H, _int, _int, _dbl, _int, _f32p, _intp),
     "rtiow_render_guides_large": (_H, _f32p),
     "rtiow_render_coverage_large": (_H, _int, _f32p),
+    "rtiow_upscale_large": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
+    "rtiow_upscale_wide_large": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -1049,8 +1051,31 @@ class Renderer:
                                                  int(use_coverage), ms_out, n_out))
         return int(n.value) if sync else None
 
+    # Guided upscaling on large scenes: the twins of upscale() and upscale_wide() with every output pixel's ray
+    # traced through the device grid of render_large().  Same buffer, state, refusals and bits; RtiowError (RTIOW_E_BADARG) when the grid
+    # does not suit the scene -- use the twin then.  Stale guides and layers are rendered through the grid as well.
+    def upscale_large(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_SIGMA_NORMAL, sigma_albedo=UPSCALE_SIGMA_ALBEDO,
+                      sigma_depth=UPSCALE_SIGMA_DEPTH, use_coverage=UPSCALE_COVERAGE, sync=True):
+        """upscale() through the device grid.  Returns the number of output pixels the share decided (None when sync=False)."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage_large(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale_large(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                  int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
+    def upscale_wide_large(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_WIDE_SIGMA_NORMAL, sigma_albedo=UPSCALE_WIDE_SIGMA_ALBEDO,
+                           sigma_depth=UPSCALE_WIDE_SIGMA_DEPTH, use_coverage=UPSCALE_WIDE_COVERAGE, sync=True):
+        """upscale_wide() through the device grid.  Returns the number of output pixels the share decided (None when sync=False)."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage_large(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale_wide_large(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                       int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
     def read_upscaled(self):
-        """The image of the last upscale() or upscale_wide(), [factor * rows, factor * W, 3], gamma-encoded like the preview."""
+        """The image of the last upscale(), upscale_wide() or _large twin of theirs, [factor * rows, factor * W, 3], gamma-encoded like the preview."""
         _, nbytes = self.upscaled_device_ptr()
         F = math.isqrt(nbytes // (self.local_rows * self.width * 3 * np.dtype(self.dtype).itemsize))     # the buffer holds F x F traced frames
         out = np.empty((F * self.local_rows, F * self.width, 3), self.dtype)

@@ -47,7 +47,8 @@ def _newer(target, sources):
 
 
 # The translation units of librtiow_hip.so, in link order (the build id hashes them in this order).
-HIP_UNITS = ("rtiow_hip.hip", "rtiow_group.hip", "rtiow_upscale.hip", "rtiow_upscale_wide.hip", "rtiow_large.hip", "rtiow_large_preview.hip")
+HIP_UNITS = ("rtiow_hip.hip", "rtiow_group.hip", "rtiow_upscale.hip", "rtiow_upscale_wide.hip", "rtiow_large.hip", "rtiow_large_preview.hip",
+             "rtiow_large_upscale.hip")
 
 
 def hip_units(csrc=None):

@@ -1,6 +1,6 @@
 // hit_device_grid.h -- hit_world over a uniform grid that stays in device memory (RTIOW_SCENE_DEVICE_GRID, rtiow_render_large), and the
-// scene staging that goes with it.  Included by rtiow_large.hip alone, behind the headers every unit shares: the other code objects do
-// not see it and keep their kernels.
+// scene staging that goes with it.  Included by rtiow_large.hip, rtiow_large_preview.hip and rtiow_large_upscale.hip alone, behind the
+// headers every unit shares: the other code objects do not see it and keep their kernels.
 #pragma once
 #include "hit_grid.h"
 #include "pixel_io.h"

@@ -2,7 +2,8 @@
 // ray -- a sub-pixel of the traced pixel it lies in, the lattice rtiow_render_coverage traces -- and gathers the colour of the four traced
 // pixels around it, each weighed bilinearly, by how well its first-hit guides match what the output pixel's ray hit, and (use_coverage) by
 // the share of it that is the surface the output pixel sees.
-// Part of the gfx950 translation unit rtiow_upscale.hip, the only one that instantiates the kernel (internal linkage).
+// Part of the gfx950 translation units rtiow_upscale.hip and, over the device grid, rtiow_large_upscale.hip: the only ones that
+// instantiate the kernel (internal linkage).
 //
 // Every value is defined operation by operation and evaluated in T with plain * + - / and sqrt, as in
 // denoise.h: no RT_FMA, madd3 or dot3 for a stored value.  -ffp-contract=off keeps the plain operations unfused, so a numpy restatement

@@ -2,7 +2,8 @@
 // where that call has four under the bilinear hat.  Every output pixel traces the same primary ray of its own and gathers the 4 x 4 traced
 // pixels around it, each weighed by the B-spline, by how well its first-hit guides match what the output pixel's ray hit, and
 // (use_coverage) by the share of it that is the surface the output pixel sees.
-// Part of the gfx950 translation unit rtiow_upscale_wide.hip, the only one that instantiates the kernel (internal linkage).
+// Part of the gfx950 translation units rtiow_upscale_wide.hip and, over the device grid, rtiow_large_upscale.hip: the only ones that
+// instantiate the kernel (internal linkage).
 //
 // Every value is defined operation by operation and evaluated in T with plain * + - / and sqrt, as in
 // upscale.h: no RT_FMA, madd3 or dot3 for a stored value.  -ffp-contract=off keeps the plain operations unfused, so a numpy restatement
@@ -71,7 +72,8 @@ __global__ void __launch_bounds__(64 * UPSCALE_WAVES) upscale_wide_kernel(const 
         }
     }
     const T* lds_geom = stage_scene<T, SRC>(p);
-    if (!(SRC == RTIOW_SCENE_LDS || p.shade_in_lds)) __syncthreads();     // stage_scene's own barrier otherwise (uniform: a kernel argument)
+    // stage_scene's own barrier otherwise (uniform: a kernel argument); stage_device_grid always ends in one
+    if (!(SRC == RTIOW_SCENE_LDS || SRC == RTIOW_SCENE_DEVICE_GRID || p.shade_in_lds)) __syncthreads();
     const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
     const int I = I0 + (wave & 1) * 8 + (lane & 7), J = J0 + (wave >> 1) * 8 + (lane >> 3);
     bool shared_tap = false;

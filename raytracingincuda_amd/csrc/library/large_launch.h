@@ -1,6 +1,7 @@
 // large_launch.h -- what the launches over the device grid share (INTEGRATION.md sections 24 and 25): the grid of the current scene built
 // once per upload (ensure_large_grid), the parameters and LDS layout of a launch over it (layout_large), the refusal of a scene it does
-// not suit and the grid_* fields of rtiow_stats.  Host side of librtiow_hip.so; part of rtiow_large.hip and rtiow_large_preview.hip,
+// not suit, the grid_* fields of rtiow_stats and the scene binding that hands all of it to the launches of launch.h (DeviceGridScene).
+// Host side of librtiow_hip.so; part of rtiow_large.hip, rtiow_large_preview.hip and rtiow_large_upscale.hip,
 // behind library/unit.h, device/hit_device_grid.h and library/device_grid.h (internal linkage).
 #pragma once
 #include "handle.h"
@@ -48,28 +49,25 @@ int ensure_large_grid(rtiow_handle_s* h) {
     return 0;
 }
 
-// The parameters and LDS layout of a launch over the device grid: the direct table and its ids at the start of LDS (stage_device_grid),
-// the shade records behind them while they fit by layout_lds's rule, the drain scratch last (persistent launches only: the tile
-// kernels of the guides and the coverage layers have none, as layout_lds(..., persistent = false) has none).  The caller has found the grid usable.
+// The parameters and LDS layout of a launch over the device grid (lds_placement.h: place_large_lds): the direct table and its ids at the
+// start of LDS (stage_device_grid), the shade records behind them while they fit by layout_lds's rule, the drain scratch last (persistent
+// launches only: the tile kernels of the guides, the coverage layers and the upscalers have none, as layout_lds(..., persistent = false)
+// has none).  The caller has found the grid usable.
 template <class T>
 void layout_large(const rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent) {
     RenderParams<T>& p = L.p;
     const GridParams& g = h->large_grid;
-    size_t lds = (size_t)g.n_direct_padded * 4 * sizeof(T) + (size_t)g.n_direct_padded * sizeof(int);       // a multiple of 16
-    p.use_screen = 0; p.screen_offset = (int)lds;
+    const size_t waves_in_block = (size_t)((threads + 63) / 64);
+    const LargeLds at = place_large_lds(g.n_direct_padded, sizeof(T), h->n, threads, persistent ? waves_in_block * COOP_SLOTS * sizeof(CoopSlot<T>) : 0);
+    p.use_screen = 0; p.screen_offset = (int)at.direct_bytes;
     p.screen.geom_s = nullptr;
     p.screen.ctr_x = (T)h->large_ctr[0]; p.screen.ctr_y = (T)h->large_ctr[1]; p.screen.ctr_z = (T)h->large_ctr[2]; p.screen.omax2 = (T)0;
-    const size_t waves_in_block = (size_t)((threads + 63) / 64);
-    const size_t coop_bytes = persistent ? waves_in_block * COOP_SLOTS * sizeof(CoopSlot<T>) : 0;
-    const size_t shade_bytes = (sizeof(T) * 12 * (size_t)h->n + 15) / 16 * 16;
-    p.shade_offset = (int)lds;
-    p.shade_in_lds = (lds + shade_bytes + coop_bytes <= 32 * 1024 && (lds + shade_bytes + coop_bytes) / waves_in_block <= 6656) ? 1 : 0;
-    if (p.shade_in_lds) lds += shade_bytes;
-    p.coop_offset = (int)lds;
-    lds += coop_bytes;
+    p.shade_offset = (int)at.shade_offset;
+    p.shade_in_lds = at.shade_in_lds ? 1 : 0;
+    p.coop_offset = (int)at.coop_offset;
     p.grid = g;
     p.use_grid = 1;            // persistent_body: the drain shares a sphere loop among idle lanes only while a ray's share of it is short
-    L.lds = lds;
+    L.lds = at.lds;
     L.lds_source = false;
     L.effective_source = RTIOW_SCENE_DEVICE_GRID;
 }
@@ -86,5 +84,29 @@ inline int refuse_unsuited(rtiow_handle_s* h, const char* call, const char* twin
     h->err = std::string(call) + LARGE_UNSUITED + twin;
     return RTIOW_E_BADARG;
 }
+
+// The scene binding of the _large calls (launch.h: StagedScene is the twins'): the device grid of the current scene, built at first use
+// after an upload; a scene it does not suit is refused under the call's name with the twin's; layout_large; the tile kernels over
+// RTIOW_SCENE_DEVICE_GRID; stale guides and layers made current through the grid as well.  rtiow_stats reports the source and the grid
+// as rtiow_render_large does.  The persistent kernels of a chunk are added where they live (rtiow_large_preview.hip).
+struct DeviceGridScene {
+    const char* twin;
+    int prepare(rtiow_handle_s* h, const char* call) const {
+        if (int rc = by_precision(h, [&](auto t) { return ensure_large_grid<decltype(t)>(h); })) return rc;
+        if (!h->large_info.usable) return refuse_unsuited(h, call, twin);
+        return 0;
+    }
+    template <class T>
+    int layout(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bool) const {
+        layout_large<T>(h, L, threads, persistent);
+        h->stats.scene_source = L.effective_source;
+        record_large_grid(h);
+        return 0;
+    }
+    template <class T, class F>
+    auto by_source(const Launch<T>&, F f) const { return f(std::integral_constant<int, RTIOW_SCENE_DEVICE_GRID>()); }
+    int render_guides(rtiow_handle_s* h) const { return rtiow_render_guides_large(h, nullptr); }
+    int render_coverage(rtiow_handle_s* h, int subsamples_per_side) const { return rtiow_render_coverage_large(h, subsamples_per_side, nullptr); }
+};
 
 }  // namespace

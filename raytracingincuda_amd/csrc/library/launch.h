@@ -2,13 +2,16 @@
 // (static / persistent / sorted with prepass + cost sort + solo waves, or in the order an earlier render left: order_key.h), launch_accumulate (one chunk of progressive rendering),
 // launch_adaptive (one adaptive chunk), each as: layout and kernel pick -> plan (launch_plan.h: every integer of the schedule; the occupancy
 // queries it asks for are made here) -> buffers -> enqueue -> record; launch_guides / launch_linear / launch_denoise: the denoised previews; launch_variance_plane /
-// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; prepare_upscale / finish_upscale: what the upscale launches share; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip alone); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip alone); upscale_call: the body of both entry points
-// launch_accumulate, launch_adaptive, launch_guides and launch_coverage take the scene binding of the call (StagedScene below for the calls
-// that stage the scene by the handle's scene source; rtiow_large_preview.hip's for the device grid): each launch is stated once.
+// launch_denoise_variance: the variance-guided filter (from_history: of the temporal image, by launch_temporal_noise's plane); launch_history: the temporal reprojection, plain or with the neighbourhood clamp; launch_history_plan: its history length alone; launch_coverage / launch_edge_resolve: the coverage layers and the resolve of the mixed pixels; prepare_upscale / finish_upscale: what the upscale launches share; launch_upscale: the preview at a multiple of the traced resolution (instantiated by rtiow_upscale.hip and, over the device grid, rtiow_large_upscale.hip); launch_upscale_wide: the same with 4 x 4 taps (instantiated by rtiow_upscale_wide.hip and rtiow_large_upscale.hip); upscale_call (pass.h): the body of the four entry points
+// launch_accumulate, launch_adaptive, launch_guides, launch_coverage, prepare_upscale, launch_upscale and launch_upscale_wide take the scene
+// binding of the call (StagedScene below for the calls that stage the scene by the handle's scene source; large_launch.h's DeviceGridScene
+// for the device grid): each launch is stated once.
 // Host side of librtiow_hip.so; part of the translation unit rtiow_hip.hip, of rtiow_upscale.hip for launch_upscale, of rtiow_upscale_wide.hip
-// for launch_upscale_wide and of rtiow_large_preview.hip for the four launches over the device grid (internal linkage).
+// for launch_upscale_wide, of rtiow_large_preview.hip for the four launches over the device grid and of rtiow_large_upscale.hip for the
+// two upscale launches over it (internal linkage).
 #pragma once
 #include "scene_tables.h"
+#include "lds_placement.h"
 #include "../device/render_kernels.h"
 #include "../device/adaptive.h"
 #include "../device/cost_sort.h"
@@ -141,7 +144,8 @@ int layout_lds(rtiow_handle_s* h, Launch<T>& L, int threads, bool persistent, bo
 // before it changes any state (a refusal under the call's name); layout: the parameters and the LDS of the launch; by_source: the scene-source
 // template argument of the kernels for that layout; accumulate_kernel / adaptive_kernel: the persistent kernels of a chunk.  This one is
 // the binding of every call that stages the scene by the handle's scene source: layout_lds, RTIOW_SCENE_LDS or RTIOW_SCENE_SCALAR, the
-// render_* kernels.  The device grid's is rtiow_large_preview.hip's.
+// render_* kernels.  The device grid's is large_launch.h's DeviceGridScene (rtiow_large_preview.hip adds its persistent kernels).  render_guides /
+// render_coverage: how a call that reads guides and layers makes stale ones current (pass.h: upscale_call).
 struct StagedScene {
     int prepare(rtiow_handle_s*, const char*) const { return 0; }
     template <class T>
@@ -152,6 +156,9 @@ struct StagedScene {
     RenderFn<T> accumulate_kernel(SRC, BOUNDED) const { return render_accumulate_kernel<T, SRC::value, BOUNDED::value>; }
     template <class T, class SRC, class BOUNDED>
     RenderFn<T> adaptive_kernel(SRC, BOUNDED) const { return render_adaptive_kernel<T, SRC::value, BOUNDED::value>; }
+    // stale guides and layers made current for a call that reads them (upscale_call): the library's own calls in their asynchronous form
+    int render_guides(rtiow_handle_s* h) const { return rtiow_render_guides(h, nullptr); }
+    int render_coverage(rtiow_handle_s* h, int subsamples_per_side) const { return rtiow_render_coverage(h, subsamples_per_side, nullptr); }
 };
 
 // The setup the persistent launches share (launch_render's dynamic schedules, launch_accumulate, launch_adaptive): four-wave 16 x 16
@@ -759,16 +766,18 @@ struct UpscaleLaunch {
     size_t lds = 0;             // own_offset + own_lds
 };
 
-// Parameters, the layout of launch_guides with the kernel's own_lds bytes behind it, h->upscaled, the zeroed counters and u.  A scene that
+// Parameters, the layout of launch_guides by the call's scene binding with the kernel's own_lds bytes behind it (lds_placement.h:
+// place_own_lds), h->upscaled, the zeroed counters and u.  A scene that
 // does not fit is refused here, before h->upscaled is touched: growing it loses the image of an earlier call, which stays readable.
-template <class T>
-int prepare_upscale(rtiow_handle_s* h, UpscaleLaunch<T>& U, size_t own_lds, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+template <class T, class Scene>
+int prepare_upscale(rtiow_handle_s* h, const Scene& scene, UpscaleLaunch<T>& U, size_t own_lds, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
     U.L = Launch<T>{make_params<T>(h)};
-    int rc = layout_lds<T>(h, U.L, 64 * UPSCALE_WAVES, false, false);
+    int rc = scene.template layout<T>(h, U.L, 64 * UPSCALE_WAVES, false, false);
     if (rc) return rc;
-    U.own_offset = (U.L.lds + 15) / 16 * 16;
-    U.lds = U.own_offset + own_lds;
-    if (U.lds > 160 * 1024) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
+    const OwnLds own = place_own_lds(U.L.lds, own_lds);
+    U.own_offset = own.offset;
+    U.lds = own.end;
+    if (!own.fits) return fail_arg(h, RTIOW_E_BADARG, "scene too large for LDS staging; use RTIOW_SCENE_SCALAR");
     HIP_TRY(h, h->upscaled.ensure(out_bytes));
     constexpr size_t ctr_bytes = (size_t)UPSCALE_COUNTERS * UPSCALE_COUNTER_STRIDE * sizeof(unsigned);
     HIP_TRY(h, h->upscale_ctr.ensure(ctr_bytes));
@@ -794,14 +803,14 @@ inline int finish_upscale(rtiow_handle_s* h, int factor, size_t out_bytes) {
     return 0;
 }
 
-// upscale_kernel over the traced frame into h->upscaled (rtiow_upscale): one word per wave behind the staged scene for the count, one 8x8
+// upscale_kernel over the traced frame into h->upscaled (rtiow_upscale; rtiow_upscale_large with the device grid's binding): one word per wave behind the staged scene for the count, one 8x8
 // tile of the factor x larger image per wave.
-template <class T>
-int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+template <class T, class Scene>
+int launch_upscale(rtiow_handle_s* h, const Scene& scene, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
     UpscaleLaunch<T> U;
-    if (int rc = prepare_upscale<T>(h, U, UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
+    if (int rc = prepare_upscale<T>(h, scene, U, UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
     U.u.tally_offset = (int)U.own_offset;
-    const auto k = by_source(U.L.lds_source, [](auto src) { return upscale_kernel<T, src>; });
+    const auto k = scene.by_source(U.L, [](auto src) { return upscale_kernel<T, src>; });
     HIP_TRY(h, allow_lds(k, U.lds));
     const int tiles = ((U.L.p.cold.W * factor + 7) / 8) * ((h->local_rows * factor + 7) / 8);
     hipLaunchKernelGGL(k, dim3((unsigned)((tiles + UPSCALE_WAVES - 1) / UPSCALE_WAVES)), dim3(64 * UPSCALE_WAVES), U.lds, h->stream, U.L.p, U.u, h->upscaled.as<T>(),
@@ -809,16 +818,16 @@ int launch_upscale(rtiow_handle_s* h, int factor, int source, const double inv2[
     return finish_upscale(h, factor, out_bytes);
 }
 
-// upscale_wide_kernel over the traced frame into h->upscaled (rtiow_upscale_wide): one workgroup of 256 per 16 x 16 block of the factor x
+// upscale_wide_kernel over the traced frame into h->upscaled (rtiow_upscale_wide; rtiow_upscale_wide_large with the device grid's binding): one workgroup of 256 per 16 x 16 block of the factor x
 // larger image.  Behind the staged scene the LDS holds the block's footprint of traced pixels (upscale_wide_stage_bytes) and, behind that,
 // the word per wave of the count.  check_upscale_extent's limits on 8 x 8 tiles hold a fortiori for 16 x 16 blocks.
-template <class T>
-int launch_upscale_wide(rtiow_handle_s* h, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
+template <class T, class Scene>
+int launch_upscale_wide(rtiow_handle_s* h, const Scene& scene, int factor, int source, const double inv2[3], int use_coverage, size_t out_bytes) {
     UpscaleLaunch<T> U;
-    if (int rc = prepare_upscale<T>(h, U, upscale_wide_stage_bytes<T>() + UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
+    if (int rc = prepare_upscale<T>(h, scene, U, upscale_wide_stage_bytes<T>() + UPSCALE_TALLY_BYTES, factor, source, inv2, use_coverage, out_bytes)) return rc;
     const size_t stage_offset = U.own_offset;
     U.u.tally_offset = (int)(stage_offset + upscale_wide_stage_bytes<T>());
-    const auto k = by_source(U.L.lds_source, [](auto src) { return upscale_wide_kernel<T, src>; });
+    const auto k = scene.by_source(U.L, [](auto src) { return upscale_wide_kernel<T, src>; });
     HIP_TRY(h, allow_lds(k, U.lds));
     const int blocks = ((U.L.p.cold.W * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK) * ((h->local_rows * factor + UPSCALE_WIDE_BLOCK - 1) / UPSCALE_WIDE_BLOCK);
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * UPSCALE_WAVES), U.lds, h->stream, U.L.p, U.u, (int)stage_offset, h->upscaled.as<T>(), (unsigned*)h->upscale_ctr);

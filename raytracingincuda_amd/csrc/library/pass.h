@@ -1,5 +1,5 @@
 // pass.h -- what the entry points of the gfx950 translation units share around a timed pass: the events of kernel_ms and the copy of a
-// result to the host; and upscale_call, the body of rtiow_upscale and rtiow_upscale_wide.
+// result to the host; and upscale_call, the body of rtiow_upscale, rtiow_upscale_wide and their _large twins.
 // Host side of librtiow_hip.so (internal linkage).
 #pragma once
 #include "handle.h"
@@ -31,10 +31,12 @@ int copy_out(rtiow_handle_s* h, void* host, const void* dev, size_t bytes) {
     return 0;
 }
 
-// rtiow_upscale and rtiow_upscale_wide under the call's name (INTEGRATION.md sections 22 and 23): the checks in their order, stale guides and
-// -- with the share -- stale layers made current inside kernel_ms, launch(inv2, out_bytes), and the count summed over its words.
-template <class LaunchFn>
-int upscale_call(const char* call, rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth, int use_coverage,
+// rtiow_upscale, rtiow_upscale_wide and their _large twins under the call's name (INTEGRATION.md sections 22, 23 and 26): the checks in their
+// order, what the scene binding asks last of them (launch.h: StagedScene nothing; the device grid's a scene it suits), stale guides and
+// -- with the share -- stale layers made current through the same binding inside kernel_ms, launch(inv2, out_bytes), and the count summed
+// over its words.
+template <class Scene, class LaunchFn>
+int upscale_call(const char* call, const Scene& scene, rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth, int use_coverage,
                  float* kernel_ms, uint64_t* covered_pixels, LaunchFn launch) {
     if (!h) return RTIOW_E_BADARG;
     if (kernel_ms) *kernel_ms = 0;
@@ -50,12 +52,13 @@ int upscale_call(const char* call, rtiow_handle h, int factor, int source, doubl
     uint64_t out_bytes = 0;
     PREVIEW_TRY(h, check_upscale_extent(call, factor, img_w(h), h->local_rows, (int64_t)elem_size(h), &out_bytes));
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = timed_begin(h, kernel_ms);
+    int rc = scene.prepare(h, call);                     // the binding's refusal: behind the call's own, before anything changes
     if (rc) return rc;
+    if ((rc = timed_begin(h, kernel_ms))) return rc;
     // stale guides and, with the share, stale layers first, inside kernel_ms: the library's own calls in their asynchronous form (their
-    // kernels live in rtiow_hip.hip's code object)
-    if (!h->preview.guides_ok && (rc = rtiow_render_guides(h, nullptr))) return rc;
-    if (use_coverage && !h->preview.coverage_ok && (rc = rtiow_render_coverage(h, coverage_grid_or_default(h->preview), nullptr))) return rc;
+    // kernels live in another unit's code object)
+    if (!h->preview.guides_ok && (rc = scene.render_guides(h))) return rc;
+    if (use_coverage && !h->preview.coverage_ok && (rc = scene.render_coverage(h, coverage_grid_or_default(h->preview)))) return rc;
     if ((rc = launch(inv2, (size_t)out_bytes))) return rc;
     if ((rc = timed_end(h, kernel_ms))) return rc;
     if (!covered_pixels) return 0;

@@ -14,8 +14,8 @@ extern "C" {
 // ---- Guided upscaling
 int rtiow_upscale(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth, int use_coverage,
                   float* kernel_ms, uint64_t* covered_pixels) {
-    return upscale_call("rtiow_upscale", h, factor, source, sigma_normal, sigma_albedo, sigma_depth, use_coverage, kernel_ms, covered_pixels, [&](const double* inv2, size_t out_bytes) {
-        return by_precision(h, [&](auto t) { return launch_upscale<decltype(t)>(h, factor, source, inv2, use_coverage, out_bytes); });
+    return upscale_call("rtiow_upscale", StagedScene{}, h, factor, source, sigma_normal, sigma_albedo, sigma_depth, use_coverage, kernel_ms, covered_pixels, [&](const double* inv2, size_t out_bytes) {
+        return by_precision(h, [&](auto t) { return launch_upscale<decltype(t)>(h, StagedScene{}, factor, source, inv2, use_coverage, out_bytes); });
     });
 }
 
