@@ -52,6 +52,8 @@ extern "C" {
 #define RTIOW_SCENE_DEVICE_GRID 4 /* rtiow_render_large and the _large preview calls only (rtiow_set_scene_source refuses it): a uniform grid
                                  * whose cells, index lists and spheres stay in device memory; what
                                  * rtiow_stats.scene_source reads after that call                    */
+#define RTIOW_SCENE_VOLUME_GRID 5 /* rtiow_render_volume only (rtiow_set_scene_source refuses it): a uniform grid over x, y and z in
+                                 * device memory; what rtiow_stats.scene_source reads after that call */
 
 /* Pixel scheduling (same image either way):
  * STATIC     = the reference's launch geometry: grid of T x T blocks, one lane per pixel
@@ -853,6 +855,38 @@ int rtiow_upscale_large(rtiow_handle h, int factor, int source, double sigma_nor
 /* rtiow_upscale_wide. */
 int rtiow_upscale_wide_large(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
                              int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+
+/* ---- Volume scenes: rtiow_render through a THREE-axis uniform grid walked in device memory.
+ * The device grid of rtiow_render_large runs over x and z and holds the y extent as one slab: a scene that fills a volume (a particle
+ * cloud, a molecule, a stack of layers) puts a whole column of spheres into every cell's list.  rtiow_render_volume is rtiow_render_large
+ * over a grid of nx x ny x nz cells of its own: the same framebuffer, shard, RNG states (read from where rtiow_init_rng left them and
+ * left there), timing and rtiow_stats, and the image is rtiow_render's bit for bit.  Opt-in: no call selects it, and the knobs of
+ * rtiow_set_scene_source and rtiow_set_schedule do not apply (rtiow_stats.schedule reads RTIOW_SCHED_PERSISTENT, scene_source
+ * RTIOW_SCENE_VOLUME_GRID; grid_nx, grid_nz, grid_cell, grid_registered and grid_direct describe the volume grid, rtiow_read_volume_grid
+ * has ny).  Plan and device tables are built at the first call after rtiow_set_scene / rtiow_edit_scene(_mapped), before the start event;
+ * the time goes to rtiow_stats.scene_prepare_ms.  The grid of rtiow_render_large and this one may both exist on a handle.
+ * kernel_ms NULL: asynchronous on the handle's stream.  Refusals: rtiow_render_large's, in its order, under this call's name; a scene
+ * the volume grid does not suit (fewer than 24 spheres, fewer than 16 small enough for a cell, or a list of big spheres longer than
+ * max(8, n / 6) or 2048) gets RTIOW_E_BADARG and "rtiow_render_volume: the volume grid does not suit this scene (...); use rtiow_render"
+ * -- there is no silent fall-back.  RTIOW_E_STATE before rtiow_init_rng.  A NULL handle: -1 before any device work.
+ * The chunks, guides, coverage layers and upscalers have no _volume twins yet.  Not available on groups. */
+int rtiow_render_volume(rtiow_handle h, float* kernel_ms);
+typedef struct {
+    int32_t  usable;             /* 1: rtiow_render_volume renders this scene; 0: it refuses (every other field is then 0)  */
+    int32_t  nx, ny, nz;         /* cells along x, y and z                                                                  */
+    double   cell;               /* cell width                                                                              */
+    double   rfar;               /* origins farther than this from the scene's centre send their wave through the exact loop */
+    int32_t  registered;         /* spheres in the grid                                                                     */
+    int32_t  direct;             /* spheres too big for a cell: tested by every ray                                         */
+    uint64_t index_entries;      /* entries of the index array (a sphere is listed in at most 8 cells)                      */
+    uint64_t occupied_cells;     /* cells with a list                                                                       */
+    int32_t  longest_list;       /* spheres in the fullest cell                                                             */
+    int32_t  reserved;
+    uint64_t blob_bytes;         /* device memory of cells, indices, sphere table and direct list                           */
+} rtiow_volume_grid_info;
+/* The volume grid of the handle's scene in the handle's precision, built here if no rtiow_render_volume has built it yet (host work and
+ * one upload; no kernel).  RTIOW_E_BADARG without a scene. */
+int rtiow_read_volume_grid(rtiow_handle h, rtiow_volume_grid_info* out);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

@@ -89,6 +89,19 @@ int rtiow_debug_large_grid_plan(int n, const double* center_radius, const double
  * cells its walk read, or -1 when its wave took the exact loop (a far, NaN or huge ray among its 64).  RTIOW_E_BADARG when the grid
  * does not suit the scene. */
 int rtiow_debug_hit_world_large(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out, int32_t* cells_out);
+/* The volume grid's plan (rtiow_render_volume, csrc/library/volume_grid.h) for n spheres {cx,cy,cz,r} (doubles) around the recentring
+ * point centre3, as the library builds it.  Host arithmetic only (no GPU needed).  max_cells <= 0: the library's cap (2^20); a smaller
+ * one makes the loop that widens the cells run; a larger one is refused (RTIOW_E_BADARG: a record's byte offset must stay in 32 bits).  dims8 = {nx, ny, nz, registered spheres, direct-list length, index entries, longest cell
+ * list, occupied cells}; params8 = {x0, y0, z0, cell, rfar, eps, cmax, 0}; cells (optional) = nx*ny*nz {first, count} pairs, cell
+ * (ix, iy, iz) at (iy nz + iz) nx + ix, into indices (optional); direct (optional) = the direct list; halfwidth (optional, n entries).
+ * A first call with NULL buffers gives the sizes.  Returns 1 when rtiow_render_volume would render the scene, 0 when it would refuse,
+ * negative on bad arguments. */
+int rtiow_debug_volume_grid_plan(int n, const double* center_radius, const double* centre3, int64_t max_cells, int32_t* dims8, double* params8,
+                                 uint32_t* cells, size_t cells_cap, uint32_t* indices, size_t indices_cap, int32_t* direct, size_t direct_cap, double* halfwidth);
+/* rtiow_debug_hit_world through the volume grid of rtiow_render_volume (whatever the handle's scene source), and per ray the number of
+ * cells its walk read, or -1 when its wave took the exact loop (a far, NaN or huge ray among its 64).  RTIOW_E_BADARG when the grid
+ * does not suit the scene. */
+int rtiow_debug_hit_world_volume(rtiow_handle h, int n, const void* rays, void* t_out, int32_t* index_out, int32_t* cells_out);
 
 /* Test hook, host only (no GPU, no RCCL): the exchange's schedule -- the very function rtiow_group_gather runs --
  * against a recording table instead of HIP / RCCL, for n ranks on `devices` with `rows` local rows each.

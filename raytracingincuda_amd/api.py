@@ -25,6 +25,7 @@ import numpy as np
 LAMBERTIAN, METAL, DIELECTRIC = 0, 1, 2
 SCENE_LDS, SCENE_SCALAR, SCENE_LDS_EXACT, SCENE_GRID = 0, 1, 2, 3
 SCENE_DEVICE_GRID = 4                                       # what stats()["scene_source"] reads after render_large(); set_scene_source refuses it
+SCENE_VOLUME_GRID = 5                                       # what stats()["scene_source"] reads after render_volume(); set_scene_source refuses it
 SCHED_STATIC, SCHED_PERSISTENT, SCHED_SORTED = 0, 1, 2
 GATHER_AUTO, GATHER_RCCL, GATHER_PEER, GATHER_HOST = 0, 1, 2, 3
 GUIDES_FIRST_HIT, GUIDES_SPECULAR = 0, 1  # rtiow_set_guide_mode
@@ -85,6 +86,13 @@ class LargeGridInfo(ctypes.Structure):
     _fields_ = [("usable", ctypes.c_int32), ("nx", ctypes.c_int32), ("nz", ctypes.c_int32), ("cell", ctypes.c_double), ("rfar", ctypes.c_double),
                 ("registered", ctypes.c_int32), ("direct", ctypes.c_int32), ("index_entries", ctypes.c_uint64), ("longest_list", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("blob_bytes", ctypes.c_uint64)]
+
+
+class VolumeGridInfo(ctypes.Structure):
+    """rtiow_volume_grid_info (include/rtiow.h)."""
+    _fields_ = [("usable", ctypes.c_int32), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("cell", ctypes.c_double),
+                ("rfar", ctypes.c_double), ("registered", ctypes.c_int32), ("direct", ctypes.c_int32), ("index_entries", ctypes.c_uint64),
+                ("occupied_cells", ctypes.c_uint64), ("longest_list", ctypes.c_int32), ("reserved", ctypes.c_int32), ("blob_bytes", ctypes.c_uint64)]
 
 
 class GroupStats(ctypes.Structure):
@@ -172,6 +180,8 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_render_coverage_large": (_H, _int, _f32p),
     "rtiow_upscale_large": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_upscale_wide_large": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
+    "rtiow_render_volume": (_H, _f32p),
+    "rtiow_read_volume_grid": (_H, ctypes.POINTER(VolumeGridInfo)),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -217,6 +227,8 @@ DEBUG_ABI = {
     "rtiow_debug_grid_plan": (_int, _f64p, _f64p, _i32p, _f64p, _u16p, _size, _i32p, _size, _f64p),
     "rtiow_debug_large_grid_plan": (_int, _f64p, _f64p, _i32p, _f64p, _u32p, _size, _u32p, _size, _i32p, _size, _f64p),
     "rtiow_debug_hit_world_large": (_H, _int, _vp, _vp, _i32p, _i32p),
+    "rtiow_debug_volume_grid_plan": (_int, _f64p, _f64p, ctypes.c_int64, _i32p, _f64p, _u32p, _size, _u32p, _size, _i32p, _size, _f64p),
+    "rtiow_debug_hit_world_volume": (_H, _int, _vp, _vp, _i32p, _i32p),
     "rtiow_debug_gather_schedule": (_int, _intp, _intp, _int, _int, _int, _int, _i64p, _size, _intp),
 }
 HOST_ABI = {                                                # include/rtiow_host.h: librtiow_host.so
@@ -664,6 +676,17 @@ class Renderer:
         self._check(self._lib.rtiow_debug_hit_world_large(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data_as(_i32p), cells.ctypes.data_as(_i32p)))
         return t, idx, cells
 
+    def debug_hit_world_volume(self, rays):
+        """debug_hit_world() through the volume grid of render_volume(): (t [n], sphere index [n], cells [n]) -- cells: how many cells the
+        ray's walk read, or -1 when its wave took the exact loop."""
+        self._need_debug()
+        dt = _dtype(self.precision)
+        rays = np.ascontiguousarray(rays, dt)
+        n = rays.shape[0]
+        t = np.zeros(n, dt); idx = np.zeros(n, np.int32); cells = np.zeros(n, np.int32)
+        self._check(self._lib.rtiow_debug_hit_world_volume(self._h, n, rays.ctypes.data, t.ctypes.data, idx.ctypes.data_as(_i32p), cells.ctypes.data_as(_i32p)))
+        return t, idx, cells
+
     def debug_scatter(self, form, O, D, closest, hit, atten, sky_uy, depth, states):
         """The scatter step alone, one call per lane (calls 64 w ... 64 w + 63 share wave w), from caller-supplied (closest, hit).
         form 0: shade_step; 1: the bounded shade_step until it stops retrying; 2 (fp64): shade_front, merged_rounds, shade_back.
@@ -722,6 +745,22 @@ class Renderer:
         info = LargeGridInfo()
         self._check(self._lib.rtiow_read_large_grid(self._h, ctypes.byref(info)))
         return {name: getattr(info, name) for name, _ in LargeGridInfo._fields_ if name != "reserved"}
+
+    def render_volume(self, sync=True):
+        """render() through a three-axis uniform grid walked in device memory, for scenes that fill a volume
+        (a particle cloud, a stack of layers), where render_large()'s grid over x and z holds a whole column in every cell: the same
+        framebuffer, bit for bit.  Raises RtiowError (RTIOW_E_BADARG) when the grid does not suit the scene -- use render() then.
+        Returns the HIP-event kernel time in ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_volume(self._h, ms_out))
+        return ms.value if sync else None
+
+    def volume_grid(self):
+        """The volume grid render_volume() uses for the current scene: a dict of usable, nx, ny, nz, cell, rfar, registered, direct,
+        index_entries, occupied_cells, longest_list and blob_bytes (all 0 when the grid does not suit the scene)."""
+        info = VolumeGridInfo()
+        self._check(self._lib.rtiow_read_volume_grid(self._h, ctypes.byref(info)))
+        return {name: getattr(info, name) for name, _ in VolumeGridInfo._fields_ if name != "reserved"}
 
     # The preview chain on large scenes (INTEGRATION.md section 25): each the twin of the method it is named after, with the scene read
     # through the device grid of render_large().  Same buffers, state, refusals and bits; the two are interchangeable at every point of a
@@ -1265,6 +1304,36 @@ def debug_large_grid_plan(center_radius, centre=None, tables=False):
                                              direct.ctypes.data_as(_i32p), direct.size, half.ctypes.data_as(_f64p))
         if rc < 0:
             raise RtiowError(rc, "rtiow_debug_large_grid_plan")
+        out.update(cells=cells, indices=indices[:out["index_entries"]], direct_list=direct[:out["direct"]], halfwidth=half)
+    return out
+
+
+def debug_volume_grid_plan(center_radius, centre=None, tables=False, max_cells=0):
+    """The volume grid's plan (render_volume) for spheres [n, 4] = {cx, cy, cz, r} around `centre` (default: the library's own recentring
+    point, the centroid of the finite spheres with r < 100 rounded to fp32), on the host: no GPU needed.  max_cells = 0: the library's
+    cap on nx ny nz.  A dict of usable, nx, ny, nz, registered, direct, index_entries, longest_list, occupied_cells, x0, y0, z0, cell,
+    rfar, eps, cmax; tables=True adds cells [ny, nz, nx, 2] ({first, count}), indices, direct_list and halfwidth."""
+    lib = load_hip_library(debug=True)
+    cr = np.ascontiguousarray(center_radius, np.float64).reshape(-1, 4)
+    n = len(cr)
+    if centre is None:
+        keep = (cr[:, 3] < 100.0) & np.isfinite(cr[:, :3]).all(axis=1)
+        centre = cr[keep, :3].mean(axis=0).astype(np.float32) if keep.any() else np.zeros(3)
+    centre = np.ascontiguousarray(centre, np.float64)
+    dims, params = (ctypes.c_int32 * 8)(), (ctypes.c_double * 8)()
+    args = (n, cr.ctypes.data_as(_f64p), centre.ctypes.data_as(_f64p), int(max_cells), dims, params)
+    rc = lib.rtiow_debug_volume_grid_plan(*args, None, 0, None, 0, None, 0, None)
+    if rc < 0:
+        raise RtiowError(rc, "rtiow_debug_volume_grid_plan")
+    out = dict(zip(("nx", "ny", "nz", "registered", "direct", "index_entries", "longest_list", "occupied_cells"), dims), usable=bool(rc))
+    out.update(zip(("x0", "y0", "z0", "cell", "rfar", "eps", "cmax"), params))
+    if tables and out["nx"] > 0:
+        cells = np.zeros((out["ny"], out["nz"], out["nx"], 2), np.uint32); indices = np.zeros(max(1, out["index_entries"]), np.uint32)
+        direct = np.zeros(max(1, out["direct"]), np.int32); half = np.zeros(n, np.float64)
+        rc = lib.rtiow_debug_volume_grid_plan(*args, cells.ctypes.data_as(_u32p), cells.size, indices.ctypes.data_as(_u32p), indices.size,
+                                              direct.ctypes.data_as(_i32p), direct.size, half.ctypes.data_as(_f64p))
+        if rc < 0:
+            raise RtiowError(rc, "rtiow_debug_volume_grid_plan")
         out.update(cells=cells, indices=indices[:out["index_entries"]], direct_list=direct[:out["direct"]], halfwidth=half)
     return out
 

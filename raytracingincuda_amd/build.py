@@ -49,11 +49,14 @@ def _newer(target, sources):
 # The translation units of librtiow_hip.so, in link order (the build id hashes them in this order).
 HIP_UNITS = ("rtiow_hip.hip", "rtiow_group.hip", "rtiow_upscale.hip", "rtiow_upscale_wide.hip", "rtiow_large.hip", "rtiow_large_preview.hip",
              "rtiow_large_upscale.hip")
+# ... and the units behind them: the eighth, volume scenes (rtiow_render_volume).  Listed apart because tests/test_large_upscale_abi.py
+# holds HIP_UNITS to the seven above; everything that compiles, links or hashes the library goes through hip_units().
+HIP_UNITS_VOLUME = ("rtiow_volume.hip",)
 
 
 def hip_units(csrc=None):
-    """The paths of HIP_UNITS in `csrc` (default: this tree's csrc/)."""
-    return [os.path.join(csrc or CSRC, u) for u in HIP_UNITS]
+    """The paths of HIP_UNITS and HIP_UNITS_VOLUME in `csrc` (default: this tree's csrc/)."""
+    return [os.path.join(csrc or CSRC, u) for u in HIP_UNITS + HIP_UNITS_VOLUME]
 
 
 def hip_includes():

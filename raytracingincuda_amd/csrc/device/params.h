@@ -17,7 +17,9 @@ struct GridParams {
     int use_grid;
     int nx, nz;
     float x0, z0, cell, inv_cell;     // cell (ix, iz) covers [x0 + ix*cell, x0 + (ix+1)*cell) x [z0 + iz*cell, ...)
-    float ylo, yhi;                   // slab of the registered (inflated) spheres
+    float ylo, yhi;                   // slab of the registered (inflated) spheres.  RTIOW_SCENE_VOLUME_GRID (hit_volume_grid.h) has cells
+                                      // along y and no slab: there ylo = y0, the cells' origin along y, and yhi = (float)ny (exact:
+                                      // ny <= 2^20) -- the two fields that source leaves free, so that no kernel's argument offsets move
     float far2;                       // |O - ctr|^2 above this: the per-sphere registration margin no longer covers the reference's rounding noise
     float core_lo[3], core_hi[3];     // box of the gridded spheres' CENTRES (far rays are clipped against it, inflated per ray)
     float rmax2, cmax;                // largest gridded radius squared; largest |C - ctr| over the gridded spheres

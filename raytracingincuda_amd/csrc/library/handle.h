@@ -182,6 +182,14 @@ struct rtiow_handle_s {
     double large_ctr[3] = {0, 0, 0};
     bool large_dirty = true;
     rtiow_large_grid_info large_info{};
+    // volume scenes (rtiow_render_volume, rtiow_volume.hip): the three-axis grid of the current scene, kept beside the device grid in
+    // the same form (volume_dirty, set by upload_scene; the recentring point is large_centre's, held here so that either grid may be
+    // built without the other)
+    DeviceBuffer<> volume_blob;
+    GridParams volume_grid{};
+    double volume_ctr[3] = {0, 0, 0};
+    bool volume_dirty = true;
+    rtiow_volume_grid_info volume_info{};
     int waves_per_simd = 0;
     int num_cus = 256;
     int last_count_blocks = 0, last_count_waves_per_block = 0;

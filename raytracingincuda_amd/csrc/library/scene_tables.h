@@ -38,6 +38,7 @@ int upload_scene(rtiow_handle_s* h, int n, const T* cr, const T* af, const T* ri
         if (!valid || valid[i]) for (int k = 0; k < 4; ++k) h->host_cr.push_back((double)cr[4 * i + k]);
     h->screen_dirty = true;
     h->large_dirty = true;
+    h->volume_dirty = true;
     HIP_TRY(h, h->geom_a.reset());
     HIP_TRY(h, h->shade_tbl.reset());
     HIP_TRY(h, h->geom_a.ensure(sizeof(T) * 4 * mp));
