@@ -52,8 +52,8 @@ extern "C" {
 #define RTIOW_SCENE_DEVICE_GRID 4 /* rtiow_render_large and the _large preview calls only (rtiow_set_scene_source refuses it): a uniform grid
                                  * whose cells, index lists and spheres stay in device memory; what
                                  * rtiow_stats.scene_source reads after that call                    */
-#define RTIOW_SCENE_VOLUME_GRID 5 /* rtiow_render_volume only (rtiow_set_scene_source refuses it): a uniform grid over x, y and z in
-                                 * device memory; what rtiow_stats.scene_source reads after that call */
+#define RTIOW_SCENE_VOLUME_GRID 5 /* rtiow_render_volume and the _volume preview calls only (rtiow_set_scene_source refuses it): a uniform
+                                 * grid over x, y and z in device memory; what rtiow_stats.scene_source reads after such a call */
 
 /* Pixel scheduling (same image either way):
  * STATIC     = the reference's launch geometry: grid of T x T blocks, one lane per pixel
@@ -841,7 +841,7 @@ int rtiow_render_coverage_large(rtiow_handle h, int subsamples_per_side, float* 
  * the LDS that is the exact loop over every sphere, factor x factor times per traced pixel.  These two opt-in calls are their twins in
  * the sense of the five calls above -- the same buffers, state, checks, refusals (under the new name), image and *covered_pixels, bit for
  * bit -- with that ray traced through the device grid of rtiow_render_large.  They write the handle's upscaled buffer:
- * rtiow_read_upscaled and rtiow_upscaled_device_ptr serve whichever of the four upscale calls ran last, and the image goes stale by
+ * rtiow_read_upscaled and rtiow_upscaled_device_ptr serve whichever of the upscale calls ran last, and the image goes stale by
  * rtiow_upscale's rule and by nothing else.  Stale guides and, with use_coverage, stale layers are rendered first inside kernel_ms as by
  * the twin, but through rtiow_render_guides_large and rtiow_render_coverage_large (the layers at the twin's subsamples_per_side): other
  * kernels, the same bits.  rtiow_stats reports scene_source == RTIOW_SCENE_DEVICE_GRID and the grid_* fields afterwards.
@@ -869,7 +869,7 @@ int rtiow_upscale_wide_large(rtiow_handle h, int factor, int source, double sigm
  * the volume grid does not suit (fewer than 24 spheres, fewer than 16 small enough for a cell, or a list of big spheres longer than
  * max(8, n / 6) or 2048) gets RTIOW_E_BADARG and "rtiow_render_volume: the volume grid does not suit this scene (...); use rtiow_render"
  * -- there is no silent fall-back.  RTIOW_E_STATE before rtiow_init_rng.  A NULL handle: -1 before any device work.
- * The chunks, guides, coverage layers and upscalers have no _volume twins yet.  Not available on groups. */
+ * The chunks, guides, coverage layers and upscalers have _volume twins of their own (below).  Not available on groups. */
 int rtiow_render_volume(rtiow_handle h, float* kernel_ms);
 typedef struct {
     int32_t  usable;             /* 1: rtiow_render_volume renders this scene; 0: it refuses (every other field is then 0)  */
@@ -887,6 +887,36 @@ typedef struct {
 /* The volume grid of the handle's scene in the handle's precision, built here if no rtiow_render_volume has built it yet (host work and
  * one upload; no kernel).  RTIOW_E_BADARG without a scene. */
 int rtiow_read_volume_grid(rtiow_handle h, rtiow_volume_grid_info* out);
+
+/* ---- A session on a volume scene: chunks, guides, coverage layers and both upscalers through the volume grid (INTEGRATION.md
+ * section 28).  Seven opt-in calls, each the twin of the call it is named after in the sense of the _large calls above: the same
+ * parameters, buffers, preview state, checks, refusals (under the new name), statistics and bits, with the scene read through the volume
+ * grid of rtiow_render_volume instead of the handle's scene source.  A _volume call, its twin and its _large twin are interchangeable at
+ * every point of a session.  rtiow_stats reports scene_source == RTIOW_SCENE_VOLUME_GRID and the grid_* fields as after
+ * rtiow_render_volume.  A scene the volume grid does not suit is refused as rtiow_render_volume refuses it, RTIOW_E_BADARG with the text
+ * "<call>: the volume grid does not suit this scene (...); use <twin>", after the twin's own checks of state and arguments and before
+ * anything changes -- an image of an earlier call stays readable --; it is never rendered another way.  The chunk and guide calls
+ * remember nothing: a filter call that finds the guides or the layers stale renders them through the handle's scene source, so the
+ * caller renders them with the _volume call after each change of camera or scene.  The two upscalers render stale guides and, with
+ * use_coverage, stale layers through rtiow_render_guides_volume and rtiow_render_coverage_volume; rtiow_read_upscaled and
+ * rtiow_upscaled_device_ptr serve whichever of the six upscale calls ran last.  No call selects these by itself, and
+ * rtiow_set_scene_source keeps refusing RTIOW_SCENE_VOLUME_GRID.  A NULL handle: -1 before any device work.  Not available on groups. */
+/* rtiow_accumulate (threads_per_block_row has no twin: chunks always run through the persistent hand-out). */
+int rtiow_accumulate_volume(rtiow_handle h, int samples, float* kernel_ms);
+/* rtiow_accumulate_adaptive. */
+int rtiow_accumulate_adaptive_volume(rtiow_handle h, int samples, int min_samples, double rel_error, int max_samples, float* kernel_ms, int* active_pixels);
+/* rtiow_accumulate_budget: RTIOW_E_STATE before a plan that is current. */
+int rtiow_accumulate_budget_volume(rtiow_handle h, int samples, int min_samples, double target, int max_samples, float* kernel_ms, int* active_pixels);
+/* rtiow_render_guides: what it launches, in its order and under its conditions. */
+int rtiow_render_guides_volume(rtiow_handle h, float* kernel_ms);
+/* rtiow_render_coverage: subsamples_per_side 2 or 4. */
+int rtiow_render_coverage_volume(rtiow_handle h, int subsamples_per_side, float* kernel_ms);
+/* rtiow_upscale. */
+int rtiow_upscale_volume(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                         int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
+/* rtiow_upscale_wide. */
+int rtiow_upscale_wide_volume(rtiow_handle h, int factor, int source, double sigma_normal, double sigma_albedo, double sigma_depth,
+                              int use_coverage, float* kernel_ms, uint64_t* covered_pixels);
 
 /* Framebuffer: `vec3 pixel_buffer[]` (main.cu:133-134), local_rows x width x 3 T, row-major.
  * By default device memory owned by the library; rtiow_bind_framebuffer lets the caller

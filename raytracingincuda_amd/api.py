@@ -182,6 +182,13 @@ HIP_ABI = {                                                 # include/rtiow.h: l
     "rtiow_upscale_wide_large": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_render_volume": (_H, _f32p),
     "rtiow_read_volume_grid": (_H, ctypes.POINTER(VolumeGridInfo)),
+    "rtiow_accumulate_volume": (_H, _int, _f32p),
+    "rtiow_accumulate_adaptive_volume": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_accumulate_budget_volume": (_H, _int, _int, _dbl, _int, _f32p, _intp),
+    "rtiow_render_guides_volume": (_H, _f32p),
+    "rtiow_render_coverage_volume": (_H, _int, _f32p),
+    "rtiow_upscale_volume": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
+    "rtiow_upscale_wide_volume": (_H, _int, _int, _dbl, _dbl, _dbl, _int, _f32p, _u64p),
     "rtiow_bind_framebuffer": (_H, _vp, _size),
     "rtiow_framebuffer_device_ptr": (_H, _vpp, _sizep),
     "rtiow_read_framebuffer": (_H, _vp, _size),
@@ -803,6 +810,47 @@ class Renderer:
         self._coverage_grid = int(subsamples_per_side)
         return ms.value if sync else None
 
+    # A session on a volume scene: each the twin of the method it is named after, with the scene read through
+    # the volume grid of render_volume().  Same buffers, state, refusals and bits; a _volume method, its twin and its _large twin are
+    # interchangeable at every point of a session.  RtiowError (RTIOW_E_BADARG) when the grid does not suit the scene -- use the twin
+    # then.  The calls remember nothing: a filter that finds the guides or the layers stale renders them through the handle's scene
+    # source, so call these after each change of camera or scene.
+    def accumulate_volume(self, samples, sync=True):
+        """accumulate() through the volume grid.  Returns the HIP-event kernel time in ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_volume(self._h, int(samples), ms_out))
+        return ms.value if sync else None
+
+    def accumulate_adaptive_volume(self, samples, rel_error, min_samples=0, max_samples=2 ** 31 - 1, sync=True):
+        """accumulate_adaptive() through the volume grid.  Returns (kernel ms or None when sync=False, active pixels)."""
+        active = ctypes.c_int(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_adaptive_volume(self._h, int(samples), int(min_samples), float(rel_error), int(max_samples),
+                                                               ms_out, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
+
+    def accumulate_budget_volume(self, samples=BUDGET_CHUNK, target=BUDGET_TARGET, min_samples=BUDGET_MIN_SAMPLES, max_samples=2 ** 31 - 1, sync=True):
+        """accumulate_budget() through the volume grid.  Returns (kernel ms or None when sync=False, active pixels)."""
+        active = ctypes.c_int(0)
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_accumulate_budget_volume(self._h, int(samples), int(min_samples), float(target), int(max_samples),
+                                                             ms_out, ctypes.byref(active)))
+        return (ms.value if sync else None), active.value
+
+    def render_guides_volume(self, sync=True):
+        """render_guides() through the volume grid: the first-hit guides, the lens guides or the specular chain, the motion plane and the
+        edit influence, as render_guides() renders them.  Returns the kernel ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_guides_volume(self._h, ms_out))
+        return ms.value if sync else None
+
+    def render_coverage_volume(self, subsamples_per_side=COVERAGE_GRID, sync=True):
+        """render_coverage() through the volume grid.  Returns the kernel ms (None when sync=False)."""
+        ms, ms_out = _out(ctypes.c_float, sync)
+        self._check(self._lib.rtiow_render_coverage_volume(self._h, int(subsamples_per_side), ms_out))
+        self._coverage_grid = int(subsamples_per_side)
+        return ms.value if sync else None
+
     def accumulate(self, samples, threads=0, sync=True):
         """Progressive rendering: add `samples` samples per pixel to the accumulation and write the preview to the framebuffer (bit for bit
         what render() gives with samples_per_pixel = accumulated_samples).  Returns the HIP-event kernel time in ms (None when sync=False)."""
@@ -1113,8 +1161,31 @@ class Renderer:
                                                        int(use_coverage), ms_out, n_out))
         return int(n.value) if sync else None
 
+    # Guided upscaling on volume scenes: the twins of upscale() and upscale_wide() with every output pixel's ray
+    # traced through the volume grid of render_volume().  Same buffer, state, refusals and bits; RtiowError (RTIOW_E_BADARG) when the grid
+    # does not suit the scene -- use the twin then.  Stale guides and layers are rendered through the volume grid as well.
+    def upscale_volume(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_SIGMA_NORMAL, sigma_albedo=UPSCALE_SIGMA_ALBEDO,
+                       sigma_depth=UPSCALE_SIGMA_DEPTH, use_coverage=UPSCALE_COVERAGE, sync=True):
+        """upscale() through the volume grid.  Returns the number of output pixels the share decided (None when sync=False)."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage_volume(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale_volume(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                   int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
+    def upscale_wide_volume(self, factor=UPSCALE_FACTOR, source=UPSCALE_DENOISED, sigma_normal=UPSCALE_WIDE_SIGMA_NORMAL, sigma_albedo=UPSCALE_WIDE_SIGMA_ALBEDO,
+                            sigma_depth=UPSCALE_WIDE_SIGMA_DEPTH, use_coverage=UPSCALE_WIDE_COVERAGE, sync=True):
+        """upscale_wide() through the volume grid.  Returns the number of output pixels the share decided (None when sync=False)."""
+        if use_coverage and self._coverage_is_stale():
+            self.render_coverage_volume(getattr(self, "_coverage_grid", COVERAGE_GRID), sync=False)
+        (_, ms_out), (n, n_out) = _out(ctypes.c_float, sync), _out(ctypes.c_uint64, sync)
+        self._check(self._lib.rtiow_upscale_wide_volume(self._h, int(factor), int(source), float(sigma_normal), float(sigma_albedo), float(sigma_depth),
+                                                        int(use_coverage), ms_out, n_out))
+        return int(n.value) if sync else None
+
     def read_upscaled(self):
-        """The image of the last upscale(), upscale_wide() or _large twin of theirs, [factor * rows, factor * W, 3], gamma-encoded like the preview."""
+        """The image of the last upscale(), upscale_wide() or _large / _volume twin of theirs, [factor * rows, factor * W, 3], gamma-encoded like the preview."""
         _, nbytes = self.upscaled_device_ptr()
         F = math.isqrt(nbytes // (self.local_rows * self.width * 3 * np.dtype(self.dtype).itemsize))     # the buffer holds F x F traced frames
         out = np.empty((F * self.local_rows, F * self.width, 3), self.dtype)

@@ -52,11 +52,21 @@ HIP_UNITS = ("rtiow_hip.hip", "rtiow_group.hip", "rtiow_upscale.hip", "rtiow_ups
 # ... and the units behind them: the eighth, volume scenes (rtiow_render_volume).  Listed apart because tests/test_large_upscale_abi.py
 # holds HIP_UNITS to the seven above; everything that compiles, links or hashes the library goes through hip_units().
 HIP_UNITS_VOLUME = ("rtiow_volume.hip",)
+# ... and the ninth and tenth: the preview chain and the upscalers on volume scenes.  Listed apart again because
+# tests/test_render_volume_abi.py holds HIP_UNITS_VOLUME to the one above and hip_units() to the first eight; everything that compiles,
+# links, hashes or checks the staleness of the library goes through all_hip_units().
+HIP_UNITS_VOLUME_PREVIEW = ("rtiow_volume_preview.hip", "rtiow_volume_upscale.hip")
 
 
 def hip_units(csrc=None):
-    """The paths of HIP_UNITS and HIP_UNITS_VOLUME in `csrc` (default: this tree's csrc/)."""
+    """The paths of HIP_UNITS and HIP_UNITS_VOLUME in `csrc` (default: this tree's csrc/): the first eight units only, which is what
+    tests/test_render_volume_abi.py pins this function to.  The library is made of all_hip_units()."""
     return [os.path.join(csrc or CSRC, u) for u in HIP_UNITS + HIP_UNITS_VOLUME]
+
+
+def all_hip_units(csrc=None):
+    """Every translation unit of librtiow_hip.so in link order: hip_units() and HIP_UNITS_VOLUME_PREVIEW behind them."""
+    return hip_units(csrc) + [os.path.join(csrc or CSRC, u) for u in HIP_UNITS_VOLUME_PREVIEW]
 
 
 def hip_includes():
@@ -74,7 +84,7 @@ def hip_build_id(extra_flags=()):
     they were measured on; bench.py uses a record only when it matches the library that is loaded."""
     import hashlib
     h = hashlib.sha256()
-    files = hip_units() + hip_includes() + [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_debug.h")]
+    files = all_hip_units() + hip_includes() + [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_debug.h")]
     for f in files:
         h.update(os.path.relpath(f, ROOT).encode() + b"\0")
         h.update(open(f, "rb").read())
@@ -96,7 +106,7 @@ def build_stats(verbose=True):
     (lib/librtiow_hip_stats.so, -DRTIOW_PATH_STATS; used by scripts/path_stats_probe.py only)."""
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, "librtiow_hip_stats.so")
-    _run([_hipcc()] + HIP_FLAGS + ["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API", '-DRTIOW_BUILD_ID="%s"' % hip_build_id(["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API"]), "-o", out] + hip_units() + HIP_LINK, verbose)
+    _run([_hipcc()] + HIP_FLAGS + ["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API", '-DRTIOW_BUILD_ID="%s"' % hip_build_id(["-DRTIOW_PATH_STATS", "-DRTIOW_DEBUG_API"]), "-o", out] + all_hip_units() + HIP_LINK, verbose)
     return out
 
 
@@ -108,7 +118,7 @@ def build_variant(name, defines=(), csrc=None, verbose=True):
     src = csrc or CSRC
     out = os.path.join(out_dir, name + ".so")
     flags = [f for f in HIP_FLAGS if not f.startswith("-I")] + ["-I" + (os.path.join(os.path.dirname(os.path.dirname(src)), "include") if csrc else INC)]
-    _run([_hipcc()] + flags + list(defines) + ['-DRTIOW_BUILD_ID="variant:%s"' % name, "-o", out] + [f for f in hip_units(src) if os.path.exists(f)] + HIP_LINK, verbose)
+    _run([_hipcc()] + flags + list(defines) + ['-DRTIOW_BUILD_ID="variant:%s"' % name, "-o", out] + [f for f in all_hip_units(src) if os.path.exists(f)] + HIP_LINK, verbose)
     return out
 
 
@@ -118,7 +128,7 @@ def build(force=False, verbose=True):
     headers = [os.path.join(INC, "rtiow.h"), os.path.join(INC, "rtiow_host.h"), os.path.join(INC, "rtiow_debug.h")]
     me = os.path.abspath(__file__)
 
-    hip_srcs = hip_units()
+    hip_srcs = all_hip_units()
     hip_so = os.path.join(LIB, "librtiow_hip.so")
     if force or _newer(hip_so, hip_srcs + hip_includes() + [me, os.path.join(CSRC, "librtiow_hip.map")] + headers):
         # librccl is NOT linked: rtiow_group.hip dlopens it on first use (-ldl for old glibc)

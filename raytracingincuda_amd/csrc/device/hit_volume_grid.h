@@ -1,5 +1,5 @@
-// hit_volume_grid.h -- hit_world over a THREE-axis uniform grid that stays in device memory (RTIOW_SCENE_VOLUME_GRID, rtiow_render_volume).
-// Included by rtiow_volume.hip alone, behind the headers every unit shares and device/hit_device_grid.h, whose staging
+// hit_volume_grid.h -- hit_world over a THREE-axis uniform grid that stays in device memory (RTIOW_SCENE_VOLUME_GRID, rtiow_render_volume
+// and the _volume preview calls).  Included by rtiow_volume.hip, rtiow_volume_preview.hip and rtiow_volume_upscale.hip alone, behind the headers every unit shares and device/hit_device_grid.h, whose staging
 // (stage_device_grid), sphere gather (list_slot) and cell tests (cell_list_tests) it calls as they are: the other code objects do not
 // see it and keep their kernels.
 #pragma once

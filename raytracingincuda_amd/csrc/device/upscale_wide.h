@@ -72,8 +72,8 @@ __global__ void __launch_bounds__(64 * UPSCALE_WAVES) upscale_wide_kernel(const 
         }
     }
     const T* lds_geom = stage_scene<T, SRC>(p);
-    // stage_scene's own barrier otherwise (uniform: a kernel argument); stage_device_grid always ends in one
-    if (!(SRC == RTIOW_SCENE_LDS || SRC == RTIOW_SCENE_DEVICE_GRID || p.shade_in_lds)) __syncthreads();
+    // stage_scene's own barrier otherwise (uniform: a kernel argument); stage_device_grid, which stages both grids in device memory, always ends in one
+    if (!(SRC == RTIOW_SCENE_LDS || SRC == RTIOW_SCENE_DEVICE_GRID || SRC == RTIOW_SCENE_VOLUME_GRID || p.shade_in_lds)) __syncthreads();
     const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
     const int I = I0 + (wave & 1) * 8 + (lane & 7), J = J0 + (wave >> 1) * 8 + (lane >> 3);
     bool shared_tap = false;

@@ -1,6 +1,7 @@
 // unit.h -- what every gfx950 translation unit of librtiow_hip.so that launches kernels starts from (rtiow_hip.hip, rtiow_upscale.hip,
-// rtiow_upscale_wide.hip, rtiow_large.hip, rtiow_large_preview.hip, rtiow_large_upscale.hip, rtiow_volume.hip): the system headers, the
-// C-ABI and the device and library headers, in the one order all seven are compiled in.  Internal linkage throughout: a template a unit does not call is not instantiated there, so which code object holds
+// rtiow_upscale_wide.hip, rtiow_large.hip, rtiow_large_preview.hip, rtiow_large_upscale.hip, rtiow_volume.hip,
+// rtiow_volume_preview.hip, rtiow_volume_upscale.hip): the system headers, the
+// C-ABI and the device and library headers, in the one order all nine are compiled in.  Internal linkage throughout: a template a unit does not call is not instantiated there, so which code object holds
 // which kernel is decided by the unit, not here.  A unit includes this first and then only what is its own.
 #pragma once
 

@@ -1,8 +1,9 @@
 // volume_launch.h -- what the launches over the volume grid share: the three-axis grid of the current scene
 // built once per upload (ensure_volume_grid), the parameters and LDS layout of a launch over it (layout_volume), the refusal of a scene
-// it does not suit, the grid_* fields of rtiow_stats and a scene binding shaped like large_launch.h's DeviceGridScene, for the preview
-// twins that may follow (VolumeGridScene).  Host side of librtiow_hip.so; part of rtiow_volume.hip, behind library/unit.h,
-// device/hit_volume_grid.h and library/volume_grid.h (internal linkage).
+// it does not suit, the grid_* fields of rtiow_stats and the scene binding that hands all of it to the launches of launch.h, shaped like
+// large_launch.h's DeviceGridScene (VolumeGridScene).  Host side of librtiow_hip.so; part of rtiow_volume.hip,
+// rtiow_volume_preview.hip and rtiow_volume_upscale.hip, behind library/unit.h, device/hit_volume_grid.h and library/volume_grid.h
+// (internal linkage).
 #pragma once
 #include "handle.h"
 #include "launch.h"
@@ -78,13 +79,12 @@ inline int refuse_unsuited_volume(rtiow_handle_s* h, const char* call, const cha
     return RTIOW_E_BADARG;
 }
 
-// The scene binding of calls over the volume grid, shaped like DeviceGridScene: the grid built at first use after an upload, a scene
-// it does not suit refused under the call's name with the twin's, layout_volume, the tile kernels over RTIOW_SCENE_VOLUME_GRID.  No
-// call uses it yet -- rtiow_render_volume is a persistent launch of its own, as rtiow_render_large is.
-// NOT usable as it stands: it has no render_guides / render_coverage members (the guides and layers a preview twin finds stale have no
-// volume calls to be rendered through yet), which upscale_call and the chunk calls ask of a binding, and device/upscale_wide.h skips
-// its own barrier for RTIOW_SCENE_DEVICE_GRID by name (stage_device_grid ends in one): source 5 needs the same there.  A pull request
-// that adds the twins completes both before it passes this binding to a launch.
+// The scene binding of the _volume calls (launch.h: StagedScene is the twins', large_launch.h: DeviceGridScene the _large calls'): the
+// volume grid of the current scene, built at first use after an upload; a scene it does not suit is refused under the call's name with
+// the twin's; layout_volume; the tile kernels over RTIOW_SCENE_VOLUME_GRID; stale guides and layers made current through the volume
+// grid as well.  rtiow_stats reports the source and the grid as rtiow_render_volume does.  device/upscale_wide.h skips its own barrier
+// for this source by name, as for RTIOW_SCENE_DEVICE_GRID: stage_device_grid, which stages both, ends in one.  The persistent kernels
+// of a chunk are added where they live (rtiow_volume_preview.hip); rtiow_render_volume stays a persistent launch of its own.
 struct VolumeGridScene {
     const char* twin;
     int prepare(rtiow_handle_s* h, const char* call) const {
@@ -101,6 +101,8 @@ struct VolumeGridScene {
     }
     template <class T, class F>
     auto by_source(const Launch<T>&, F f) const { return f(std::integral_constant<int, RTIOW_SCENE_VOLUME_GRID>()); }
+    int render_guides(rtiow_handle_s* h) const { return rtiow_render_guides_volume(h, nullptr); }
+    int render_coverage(rtiow_handle_s* h, int subsamples_per_side) const { return rtiow_render_coverage_volume(h, subsamples_per_side, nullptr); }
 };
 
 }  // namespace

@@ -1,6 +1,6 @@
 """Register / scratch / code-size figures of the render kernels for a set of -D defines, from the compiler's metadata
 (no GPU: hipcc cross-compiles gfx950).  Usage: kernel_resources.py [-DNAME=VALUE ...] [--filter substring] [--keep out.s]
-[--unit rtiow_large_preview.hip] [--json out.json]; --unit: another translation unit under csrc/ than rtiow_hip.hip; --json: the kernels
+[--unit rtiow_large_preview.hip ...] [--json out.json]; --unit: another translation unit under csrc/ than rtiow_hip.hip (repeatable); --json: the kernels
 the filter keeps as a record {unit, flags, kernels: {name without namespace and parameters: vgprs, sgprs, spills, scratch, instructions}}."""
 import os, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,12 +30,16 @@ if __name__ == "__main__":
         k = args.index("--filter"); filt = args[k + 1]; del args[k:k + 2]
     if "--keep" in args:
         k = args.index("--keep"); keep = args[k + 1]; del args[k:k + 2]
-    unit, out_json = "rtiow_hip.hip", None
-    if "--unit" in args:
-        k = args.index("--unit"); unit = args[k + 1]; del args[k:k + 2]
+    units, out_json = [], None
+    while "--unit" in args:                                  # --unit may be given more than once: one record of all their kernels
+        k = args.index("--unit"); units.append(args[k + 1]); del args[k:k + 2]
     if "--json" in args:
         k = args.index("--json"); out_json = args[k + 1]; del args[k:k + 2]
-    kept = {name: v for name, v in sorted(metadata(args, keep, unit).items()) if filt in name}
+    units = units or ["rtiow_hip.hip"]
+    unit = ", raytracingincuda_amd/csrc/".join(units)
+    kept = {}
+    for u in units:
+        kept.update({name: v for name, v in sorted(metadata(args, keep, u).items()) if filt in name})
     for name, v in kept.items():
         print(name, {k: x for k, x in v.items() if k != "symbol"})
     if out_json:
